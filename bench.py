@@ -14,13 +14,20 @@ N > 1: tiles are independent (pass 1 of infer_one_img shards embarrassingly, SUR
 rank runs its own batches — weak scaling, no data-path collective; weights are broadcast from rank 0
 over RCCL before the timed region.  Prints ONE JSON line on rank 0.
 
-The line also carries
+A plain run does only what the headline needs: set-up, warm-up, the timed steps, the outputs of the last
+step (--dump-outputs DIR: DIR/<name>.npy, float32) and the line.  With --full the line also carries
+  sustained     — the same step run for >= 3 s, with the shader clock under load;
   roofline      — the dominant kernel (the f16 MFMA GEMM, gemm_z192.hip / gemm.hip): algorithmic FLOPs of its launches
                   / their summed duration, measured with HIP events on the launch stream in an
                   instrumented pass of the same steps (events around every launch would perturb the
                   headline timing, so they are a separate pass over the same work);
   cpu_baseline  — the CPU oracle (oracle/, plain PyTorch fp32 eager = the reference's op sequence)
-                  timed on this host's cores on a bounded sample, rank 0 / N=1 only.
+                  timed on this host's cores on a bounded sample, rank 0 / N=1 only;
+  reference_gpu — the oracle on stock PyTorch-ROCm on the same GPU (fp32 eager and fp16 autocast), and
+                  vs_baseline against its fp32 leg;
+  workloads     — BASELINE configs[2] and configs[4] and the 1024-px config beside the headline;
+  scene         — ms per synthetic 2048 x 2048 scene, end to end to the edge list.
+The --no-* options switch single legs of a --full run off.
 """
 import argparse
 import json
@@ -101,8 +108,30 @@ def build_workload(name, batch, rank, dev, distributed, net=None, sd=None):
         pairs_t = torch.as_tensor(_collate([q[2] for q in qs])).to(dev)
         valid_t = torch.as_tensor(_collate([q[3] for q in qs])).to(dev)
         step = lambda: net(rgb, pts_t, pairs_t, valid_t)[1::2]
+        step.output_names = ("mask_scores", "topo_scores")
+    else:
+        step.output_names = ("mask_scores", "img_features")
     step.rgb = rgb
     return net, sd, cfg, step, B, P, WL
+
+
+DUMP_BYTES = 60 * 10**6     # --dump-outputs budget over all files (below 64 MB with the .npy headers)
+
+
+def dump_outputs(out_dir, names, outputs):
+    """What the timed path returned in its last step, as out_dir/<name>.npy in float32, in the shapes a caller receives.  If the
+    outputs together exceed DUMP_BYTES, every one is replaced by the same fixed, seeded sample of its flattened elements (sorted
+    indices, the same fraction of each), so that two builds run with the same arguments are compared element for element."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrs = [x.detach().float().cpu().contiguous().numpy() for x in outputs]
+    total = sum(a.size * 4 for a in arrs)
+    for name, a in zip(names, arrs):
+        if total > DUMP_BYTES:
+            n = max(1, a.size * DUMP_BYTES // total)
+            idx = np.sort(np.random.default_rng(0).choice(a.size, size=n, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
 
 
 def instrumented_rows(ctx, step, dev, nrep):
@@ -354,6 +383,11 @@ def main():
                     help="encdec: BASELINE configs[1] (headline: ViT-B 512^2 B=16, encoder + map_decoder); "
                          "full: configs[2] (the same + sampler + TopoNet, 256 points per tile = SAMRoad.forward); "
                          "vith256: configs[4] (toponet_vith_256.yaml, ViT-H 256^2 tiles, B=8, encoder + map_decoder)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beside the headline: sustained, roofline, cpu_baseline, reference_gpu, workloads, scene "
+                         "(a plain run times the headline steps only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path returned in its last timed step as DIR/<name>.npy (float32, at most 64 MB in all)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-reference-gpu", action="store_true", help="skip the bounded reference-PyTorch-on-this-GPU leg")
     ap.add_argument("--no-roofline", action="store_true")
@@ -367,6 +401,9 @@ def main():
                     help="NO measurement: run the N-rank launch contract and the tile-sharded scene block on CPU / gloo with the tests' "
                          "oracle stand-in model (tests/test_distributed_cpu.py) — checks env handling, collectives and the JSON line without a GPU")
     args = ap.parse_args()
+    if not args.full:
+        args.no_sustained = args.no_roofline = args.no_cpu_baseline = args.no_reference_gpu = True
+        args.no_workloads = args.no_scene = True
     warnings.simplefilter("ignore")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(_respawn_under_launcher(args))
@@ -426,6 +463,9 @@ def main():
         elapsed = t.item()
     assert args.no_check or (torch.isfinite(scores).all() and torch.isfinite(emb).all())
     tiles_per_s = world * B * args.steps / elapsed
+    if args.dump_outputs and rank == 0:
+        # before any --full leg: the scene block loads other weights into the same model
+        dump_outputs(args.dump_outputs, step.output_names, (scores, emb))
 
     # Sustained leg: the timed region above is a ~0.1 s burst from an idle (cool) chip; the matrix pipes of this part are power-limited
     # (1.55 GHz under random-data f16 MFMA), so the same step is run for >= 3 s and reported beside `value`, with

@@ -129,16 +129,49 @@ def _tied_cutoff_sources(pts, image_size, cfg):
     return out
 
 
-def test_oracle_infer_one_img_matches_reference_run():
+def _fused_255(image_hw, patch_infos, mask_scores_list):
+    """255 x the fused fp32 scores that oscene.fuse_masks truncates to the u8 masks (the same scatter-add order: the same floats)."""
+    acc, cnt = torch.zeros((2,) + tuple(image_hw)), torch.zeros(tuple(image_hw))
+    tiles = [s[j] for s in mask_scores_list for j in range(s.shape[0])]
+    for (_, (x0, y0), (x1, y1)), s in zip(patch_infos, tiles):
+        acc[:, y0:y1, x0:x1] += s.permute(2, 0, 1)
+        cnt[y0:y1, x0:x1] += 1.0
+    return torch.nan_to_num(acc / cnt * 255, nan=0.0).numpy()
+
+
+def _assert_mask_levels_match(name, got, want, fused255):
+    """u8 mask = trunc(255 x fp32 fused score).  The last bits of the oracle's fp32 scores follow the summation order of the CPU's
+    GEMM / convolution kernels (thread count, vector ISA, cache blocking): on one host, 255 x score moves by <= 1e-4 between thread
+    counts.  So a pixel whose 255 x score lies within 1e-3 of an integer may truncate to the neighbouring level on a CPU other than
+    the one the fixture was made on.  Everywhere else the levels are identical; at such pixels they differ by at most one level, and
+    such pixels are at most 1e-4 of the mask."""
+    diff = got != want
+    frac = fused255 - np.floor(fused255)
+    at_edge = np.minimum(frac, 1.0 - frac) < 1e-3
+    step = np.abs(got.astype(np.int16) - want.astype(np.int16))
+    print(f"{name} mask: {int(diff.sum())} of {diff.size} pixels one level off at a truncation edge")
+    assert not (diff & ~at_edge).any() and step.max() <= 1 and diff.sum() <= 1e-4 * diff.size, \
+        (name, int(diff.sum()), int((diff & ~at_edge).sum()), int(step.max()))
+
+
+def test_oracle_infer_one_img_matches_reference_run(monkeypatch):
     """oracle/scene.py (tile grid, batcher, fusion, NMS, pass-2 queries, vote) against inferencer.infer_one_img run verbatim:
-    identical u8 masks, identical nodes, identical edge set and edge list order with rtree returning ids ascending; for the two
-    other rtree orders the fixture was made with, identical nodes and an edge set that differs only at tied kNN cut-offs."""
+    identical u8 masks (up to fp32 summation order at truncation edges, _assert_mask_levels_match), identical nodes, identical
+    edge set and edge list order with rtree returning ids ascending; for the two other rtree orders the fixture was made with,
+    identical nodes and an edge set that differs only at tied kNN cut-offs."""
     mg, g, cfg, img = _scene_setup()
     oracle = SAMRoadOracle(AttrDict(cfg)).eval()
     oracle.load_state_dict(mg.scene_state_dict(oracle, mg.SCENE_WSEED), strict=True)
+    fused, fuse = {}, oscene.fuse_masks
+
+    def fuse_and_keep(image_hw, patch_infos, mask_scores_list):
+        fused["255"] = _fused_255(image_hw, patch_infos, mask_scores_list)
+        return fuse(image_hw, patch_infos, mask_scores_list)
+    monkeypatch.setattr(oscene, "fuse_masks", fuse_and_keep)
     nodes, edges, kp, road = oscene.infer_one_img(oracle, img, AttrDict(cfg))
-    np.testing.assert_array_equal(kp, g["kp_mask"])
-    np.testing.assert_array_equal(road, g["road_mask"])
+    np.testing.assert_array_equal(fused["255"].astype(np.uint8), np.stack([kp, road]))     # the floats behind the oracle's masks
+    _assert_mask_levels_match("keypoint", kp, g["kp_mask"], fused["255"][0])
+    _assert_mask_levels_match("road", road, g["road_mask"], fused["255"][1])
     np.testing.assert_array_equal(nodes, g["nodes_ascending"])
     assert nodes.shape[0] > 100 and edges.shape[0] > 500
     want = {tuple(e) for e in g["edges_ascending"].tolist()}

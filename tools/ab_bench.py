@@ -18,8 +18,10 @@ res = {t: [] for t in args.trees}
 for r in range(args.rounds):
     for t in args.trees:
         env = {k: v for k, v in os.environ.items() if k != "SRH_LIB_PATH"}
-        out = subprocess.run([sys.executable, "bench.py", "--workload", args.workload, "--steps", str(args.steps), "--warmup", "5",
-                              "--no-cpu-baseline", "--no-reference-gpu", "--no-sustained", "--no-scene", "--no-workloads"],
+        # the per-class times come from the roofline leg, which only a --full run has (trees from before --full run it by default)
+        full = ["--full"] if "--full" in open(os.path.join(t, "bench.py")).read() else []
+        out = subprocess.run([sys.executable, "bench.py", "--workload", args.workload, "--steps", str(args.steps), "--warmup", "5"] + full +
+                             ["--no-cpu-baseline", "--no-reference-gpu", "--no-sustained", "--no-scene", "--no-workloads"],
                              capture_output=True, text=True, env=env, cwd=t)
         line = [l for l in out.stdout.splitlines() if l.startswith("{")]
         if not line:
