@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define SRH_ABI_VERSION 8
+#define SRH_ABI_VERSION 9
 
 typedef enum {
     SRH_OK = 0,
@@ -37,6 +37,7 @@ typedef enum {
     SRH_ERR_MISSING_WEIGHT = -4,
     SRH_ERR_NO_DEVICE = -5,
     SRH_ERR_NONFINITE = -6     /* ABI 8: a LayerNorm pass of an EARLIER call on this context read an Inf / NaN (fp16 overflow upstream) */
+    /* ABI 9: an earlier srh_toponet_ragged call's pair outside its row's tile is reported the same lazy way, as SRH_ERR_BAD_ARG */
 } srh_status;
 
 typedef enum { SRH_F32 = 0, SRH_F16 = 1, SRH_U8 = 2, SRH_I32 = 3, SRH_I64 = 4 } srh_dtype;
@@ -126,7 +127,11 @@ int srh_toponet(srh_ctx* ctx, const srh_weights* w, const float* embeddings, con
  * ABI 8: tile_offsets (HOST pointer, int64 [n_tiles + 1], nullable) = the first row of every tile, from 0 to R.  With it the rows are
  * scored in chunks of whole tiles of at most 16 384 rows (same bits: rows are independent and a pair only names rows of its own
  * tile), so the context's workspace is bounded like the reference's INFER_BATCH_SIZE batches instead of growing with the scene;
- * without it the call is one launch and refuses more than 65 536 rows. */
+ * without it the call is one launch and refuses more than 65 536 rows.
+ * ABI 9: both indices of every pair must be rows in [0, R) whose point_tile equals the source row's (no python-style wrap of a
+ * negative index).  The pair gather checks this on the device; a pair that breaks it makes the call's scores invalid and is reported
+ * like the non-finite sentinel — SRH_ERR_BAD_ARG from srh_ctx_check or the next srh_encode_decode / srh_scene_pass1 on the context —
+ * instead of silently gathering another row (a chunk would otherwise wrap or clamp it into an unrelated row of its own). */
 int srh_toponet_ragged(srh_ctx* ctx, const srh_weights* w, const float* embeddings, int n_tiles, const float* points,
                        const int32_t* point_tile, const int32_t* pairs, const uint8_t* valid, int64_t R, int K,
                        const int64_t* tile_offsets, float* scores, void* stream);
@@ -179,6 +184,20 @@ int srh_op_attention(srh_ctx* ctx, const void* qkv_f16, const void* relpos_h_f16
 int srh_op_attention_hd(srh_ctx* ctx, const void* qkv_f16, const void* relpos_h_f16, const void* relpos_w_f16,
                         const void* bias_qkv_f16, int B, int S, int heads, int head_dim, int win,
                         void* out_f16, void* stream);
+
+/* The heads after the encoder (test-only; the launches and parameters of srh_encode_decode / srh_toponet):
+ *   srh_op_map_decoder: the fused map_decoder of `w` (naive decoder, S = patch_size / 16) on a neck output emb_f16 [B*S*S, 256] fp16
+ *     -> mask_logits / mask_scores [B,P,P,2] f32, both nullable;
+ *   srh_op_sample: BilinearSampler over emb_f32 [n_tiles,h,w,C] channels-last (C % 4 == 0) at points [B,N,2] (SRH_F32 / SRH_I64) in
+ *     pixels of a `patch`-px tile; point_tile i32 [B*N] (nullable: point i samples tile i / N, B <= n_tiles; else clamped into
+ *     [0, n_tiles)) -> out_f32 / out_f16 [B*N, C] (at least one);
+ *   srh_op_pair_gather: pair rows [B*Ns*K, ld] fp16 = src | tgt features of pf_f16 [B*N,128] | dx dy (0 with zero_offset) | 0, pairs
+ *     [B,Ns,K,2] (SRH_I32 / SRH_I64) minus index_base; a negative index wraps python-style only when index_base == 0. */
+int srh_op_map_decoder(srh_ctx* ctx, const srh_weights* w, const void* emb_f16, int B, float* mask_logits, float* mask_scores, void* stream);
+int srh_op_sample(srh_ctx* ctx, const float* emb_f32, int n_tiles, int h, int w, int C, const void* points, int points_dtype,
+                  const int32_t* point_tile, int B, int N, float patch, float* out_f32, void* out_f16, void* stream);
+int srh_op_pair_gather(srh_ctx* ctx, const void* pf_f16, const void* points, int points_dtype, const void* pairs, int pairs_dtype,
+                       int B, int N, int Ns, int K, int zero_offset, int64_t index_base, void* out_f16, int ld, void* stream);
 
 /* profiling --------------------------------------------------------------------------------------- */
 

@@ -98,6 +98,7 @@ struct srh_weights {
 };
 
 constexpr int NF_SLOTS = 128, NF_NECK = 64, NF_DECODER = 66;   // tags: 2 * block + (0 norm1 | 1 norm2), neck LN2d 64 / 65, map_decoder LN2d 66
+constexpr int NF_PAIRS = 67;                                    // ABI 9: srh_toponet_ragged's pair gather saw a pair outside its row's tile
 
 static int fail(srh_ctx* c, int code, const std::string& msg) {
     if (c) c->err = msg;
@@ -220,6 +221,9 @@ static int nonfinite_check(srh_ctx* c, const char* who) {
     for (int i = 0; i < NF_SLOTS; ++i)
         if (reinterpret_cast<volatile unsigned*>(c->nf_host)[i]) { if (first < 0) first = i; c->nf_host[i] = 0; }
     if (first < 0) return 0;
+    if (first == NF_PAIRS)
+        return fail(c, SRH_ERR_BAD_ARG, std::string(who) + ": an earlier srh_toponet_ragged call on this context was given a pair that names a row "
+                                        "outside its own tile (or outside [0, R)); the scores of that call are invalid");
     std::string where;
     if (first < NF_NECK) where = "encoder block " + std::to_string(first / 2) + (first & 1 ? ", norm2 (the block's attention branch output or its residual stream)"
                                                                                          : ", norm1 (the previous block's MLP output, the patch embedding for block 0, or the residual stream)");
@@ -998,6 +1002,7 @@ static int toponet_impl(srh_ctx* c, const srh_weights* w, const float* embedding
     pg.pf = c->t_pf16.as<f16>(); pg.points = points; pg.points_i64 = points_dtype == SRH_I64;
     pg.pairs = pairs; pg.pairs_i64 = pairs_dtype == SRH_I64; pg.B = B; pg.N = N; pg.Ns = Ns; pg.Kp = K;
     pg.zero_offset = w->cfg.toponet_version == 1; pg.out = c->t_pair16.as<f16>(); pg.ld = 320; pg.index_base = pair_base;
+    if (point_tile) { pg.point_tile = point_tile; pg.bad = c->nf_dev + NF_PAIRS; }      // ragged rows: pairs stay inside their tile
     TRYK(c, "pair_gather", 0, (double)R * (512 + 640), s, launch_pair_gather(pg, s));
     {
         // pair_proj + encoder layers + output_proj in one register-resident kernel (topo_fused.hip)
@@ -1129,6 +1134,55 @@ extern "C" int srh_op_layernorm(srh_ctx* c, const float* x, const float* gamma, 
     ln.out_f32 = out_f32; ln.out_f16 = (f16*)out_f16;
     hipStream_t s = (hipStream_t)stream;
     TRYK(c, "layernorm", 0, 0, s, launch_layernorm(ln, s));
+    return 0;
+}
+
+// The heads after the encoder at op level: the same launchers, with the parameters the model path gives them (encode_batch,
+// toponet_impl), on caller-supplied inputs.
+extern "C" int srh_op_map_decoder(srh_ctx* c, const srh_weights* w, const void* emb_f16, int B, float* mask_logits, float* mask_scores,
+                                  void* stream) {
+    if (!c || !w || !emb_f16 || B <= 0) return fail(c, SRH_ERR_BAD_ARG, "srh_op_map_decoder: bad argument");
+    if (w->cfg.use_sam_decoder || !w->dec_frags) return fail(c, SRH_ERR_UNSUPPORTED, "srh_op_map_decoder: the weights have no naive map_decoder");
+    if (!mask_logits && !mask_scores) return 0;
+    hipSetDevice(c->device);
+    hipStream_t s = (hipStream_t)stream;
+    DecodeFusedParams dp;
+    dp.emb16 = (const f16*)emb_f16; dp.frags = w->dec_frags; dp.prm = w->dec_prm; dp.B = B; dp.S = w->S;
+    dp.logits = mask_logits; dp.scores = mask_scores; dp.nf = c->nf_dev; dp.nf_tag = NF_DECODER;
+    TRYK(c, "map_decoder", 0, 0, s, launch_decode_fused(dp, s));
+    return 0;
+}
+
+extern "C" int srh_op_sample(srh_ctx* c, const float* emb_f32, int n_tiles, int h, int w, int C, const void* points, int points_dtype,
+                             const int32_t* point_tile, int B, int N, float patch, float* out_f32, void* out_f16, void* stream) {
+    if (!c || !emb_f32 || !points || (!out_f32 && !out_f16)) return fail(c, SRH_ERR_BAD_ARG, "srh_op_sample: null argument");
+    if (points_dtype != SRH_I64 && points_dtype != SRH_F32) return fail(c, SRH_ERR_BAD_ARG, "srh_op_sample: points dtype must be i64 or f32");
+    if (B < 0 || N < 0 || h <= 0 || w <= 0 || C <= 0 || C % 4 || n_tiles <= 0 || !(patch > 0.f))
+        return fail(c, SRH_ERR_BAD_ARG, "srh_op_sample: bad sizes (C must be a multiple of 4)");
+    if (!point_tile && B > n_tiles) return fail(c, SRH_ERR_BAD_ARG, "srh_op_sample: without point_tile, batch b samples tile b: B must be <= n_tiles");
+    hipSetDevice(c->device);
+    hipStream_t s = (hipStream_t)stream;
+    SampleParams sp;
+    sp.emb = emb_f32; sp.points = points; sp.points_i64 = points_dtype == SRH_I64; sp.B = B; sp.N = N;
+    sp.h = h; sp.w = w; sp.C = C; sp.patch = patch; sp.out_f32 = out_f32; sp.out_f16 = (f16*)out_f16;
+    sp.point_tile = point_tile; sp.n_tiles = n_tiles;
+    TRYK(c, "bilinear_sample", 0, 0, s, launch_sample(sp, s));
+    return 0;
+}
+
+extern "C" int srh_op_pair_gather(srh_ctx* c, const void* pf_f16, const void* points, int points_dtype, const void* pairs, int pairs_dtype,
+                                  int B, int N, int Ns, int K, int zero_offset, int64_t index_base, void* out_f16, int ld, void* stream) {
+    if (!c || !pf_f16 || !points || !pairs || !out_f16) return fail(c, SRH_ERR_BAD_ARG, "srh_op_pair_gather: null argument");
+    if (points_dtype != SRH_I64 && points_dtype != SRH_F32) return fail(c, SRH_ERR_BAD_ARG, "srh_op_pair_gather: points dtype must be i64 or f32");
+    if (pairs_dtype != SRH_I64 && pairs_dtype != SRH_I32) return fail(c, SRH_ERR_BAD_ARG, "srh_op_pair_gather: pairs dtype must be i64 or i32");
+    if (B < 0 || N <= 0 || Ns < 0 || K <= 0) return fail(c, SRH_ERR_BAD_ARG, "srh_op_pair_gather: bad sizes");
+    hipSetDevice(c->device);
+    hipStream_t s = (hipStream_t)stream;
+    PairGatherParams pg;
+    pg.pf = (const f16*)pf_f16; pg.points = points; pg.points_i64 = points_dtype == SRH_I64;
+    pg.pairs = pairs; pg.pairs_i64 = pairs_dtype == SRH_I64; pg.B = B; pg.N = N; pg.Ns = Ns; pg.Kp = K;
+    pg.zero_offset = zero_offset != 0; pg.out = (f16*)out_f16; pg.ld = ld; pg.index_base = (long)index_base;
+    TRYK(c, "pair_gather", 0, 0, s, launch_pair_gather(pg, s));
     return 0;
 }
 

@@ -72,9 +72,18 @@ __global__ __launch_bounds__(256) void pair_gather_kernel(PairGatherParams p) {
         tgt = reinterpret_cast<const int*>(p.pairs)[row * 2 + 1];
     }
     src -= p.index_base; tgt -= p.index_base;
-    // python-style negative index wrap, then clamp (out-of-range is an error in the reference)
-    if (src < 0) src += p.N;
-    if (tgt < 0) tgt += p.N;
+    if (p.bad) {
+        // ragged rows: both indices must be rows of this launch on the same tile (a chunk of srh_toponet_ragged holds whole tiles, so
+        // a pair into another tile would gather a different row than the unchunked call); flag it, the clamp below keeps reads in bounds
+        const bool ok = src >= 0 && src < p.N && tgt >= 0 && tgt < p.N && (!p.point_tile || p.point_tile[src] == p.point_tile[tgt]);
+        if (!ok && sub == 0) *p.bad = 1u;
+    } else if (p.index_base == 0) {
+        // python-style negative index wrap (model.py:104-108 indexes with the pairs as given); never on a chunk of a longer row list,
+        // where a negative index is a row of an earlier chunk, not one counted from the end
+        if (src < 0) src += p.N;
+        if (tgt < 0) tgt += p.N;
+    }
+    // clamp (out-of-range is an error in the reference)
     src = min(max(src, 0L), (long)p.N - 1);
     tgt = min(max(tgt, 0L), (long)p.N - 1);
     f16* out = p.out + row * p.ld;

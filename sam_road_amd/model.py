@@ -458,7 +458,8 @@ class SAMRoad(nn.Module):
         the flat list), valid u8 [R,K]  ->  scores f32 [R,K] (srh_toponet_ragged; rows as built by srh_pass2_pack_ragged).
         tile_offsets (host int64 [n + 1], rows of tile t = offsets[t] .. offsets[t+1], from 0 to R): the library then scores the scene in
         chunks of whole tiles (<= 16 k rows each, same bits) so that its workspace does not grow with the scene; without them at most
-        65 536 rows per call."""
+        65 536 rows per call.  Both rows of every pair must be rows of the same tile (ABI 9): a pair that is not makes check_finite()
+        (or the next infer_* / scene_pass1 call) raise SrhError instead of the scores silently depending on the chunking."""
         dev = image_embeddings.device
         ctx, wh = self._weights(dev)
         emb = image_embeddings.permute(0, 2, 3, 1)
@@ -488,7 +489,7 @@ class SAMRoad(nn.Module):
         encoder: srh_ctx_check, SRH_ERR_NONFINITE) — the masks / embeddings of that call are invalid.  synchronize=True waits for the
         current stream first; False only looks at what has already completed (the scene loop polls right after a scene's masks reached
         the host).  The same condition is raised lazily by the next infer_* / scene_pass1 call.  The reference's own guards
-        (inferencer.py:206,219) only see TopoNet's scores."""
+        (inferencer.py:206,219) only see TopoNet's scores.  An infer_toponet_ragged pair outside its own tile is reported here too."""
         dev = torch.device(device) if device is not None else next(self.parameters()).device
         idx = dev.index if dev.index is not None else torch.cuda.current_device()
         ctx = _lib.Context.get(idx)

@@ -38,6 +38,18 @@ ATTN_OP_MEAN = 1.5e-3
 GEMM_F16_OUT = 1.5e-3        # half an fp16 ulp of the largest magnitude is 4.9e-4 at |ref| in [4, 8); measured <= 5e-4 in round 4's probe
 GEMM_MLP_PAIR = 2.5e-3       # fc1 -> fc2 against torch on torch's fp16 hidden activation (a one-ulp difference in a few hidden values)
 
+# ---- heads after the encoder at op level (tests/test_gpu_heads.py, against float64 references) ----------------------------------------
+# map_decoder on weights that reach pre-activations of +-8 and logits of +-15 (tests/heads_ref.py DECODER_STDS), fp16 inputs and weights.
+# A priori: the kernel rounds the activations to fp16 at three layer boundaries (the MFMA B operands of layers 3, 5 and 7) and uses
+# gelu_fast (|error| <= 1.6e-6, negligible); the same three roundings simulated in float64 on 4 tiles of 256 px give logits 6.6e-3
+# and scores 1.3e-3 max-abs (the sigmoid's slope is 1/4 where the logits are small).
+DEC_OP_LOGIT = 2e-2          # measured 5.2e-3 .. 7.8e-3 (S = 16 .. 64)
+DEC_OP_SCORE = 3e-3          # measured 1.01e-3 .. 1.06e-3
+# bilinear sampler, f32 in and out, max-abs error / max|emb|.  A priori: f32 rounding only — mostly of the unnormalised coordinate
+# ((g + 1) * w rounds at |value| <= 2 w: <= w 2^-23 in each of ix, iy), so at most ~2 w 2^-23 ~ 8e-6 of max|emb| at w = 32; the
+# typical rounding is far below that worst case, and integer points are exact up to the taps' products.
+SAMPLE_OP_F32 = 2e-6         # measured 2.6e-7 .. 7.1e-7 (f32 points), 5.3e-8 .. 8.8e-8 (i64 points)
+
 _REC = {}
 
 
