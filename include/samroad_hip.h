@@ -50,7 +50,7 @@ typedef struct {
     int32_t embed_dim;          /* 768 / 1024 / 1280 */
     int32_t depth;              /* 12 / 24 / 32 */
     int32_t num_heads;          /* 12 / 16 / 16 */
-    int32_t patch_size;         /* config.PATCH_SIZE: tile side in pixels (256 / 512) */
+    int32_t patch_size;         /* config.PATCH_SIZE: tile side in pixels, a multiple of 16 from 128 to 1024 */
     int32_t n_global;           /* number of entries used in global_attn_indexes */
     int32_t global_attn_indexes[8];
     int32_t window_size;        /* 14 */

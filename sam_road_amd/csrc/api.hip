@@ -555,9 +555,10 @@ static int pack_impl(srh_ctx* c, const srh_model_cfg* cfg, const srh_named_tenso
     if (D <= 0 || heads <= 0 || D % heads) return fail(c, SRH_ERR_BAD_ARG, "bad embed_dim / num_heads");
     const int hd = D / heads;
     if (hd != 64 && hd != 80) return fail(c, SRH_ERR_UNSUPPORTED, "head_dim must be 64 (MFMA attention kernels) or 80 (ViT-H: generic kernel)");
-    if (cfg->patch_size % 16) return fail(c, SRH_ERR_BAD_ARG, "PATCH_SIZE must be a multiple of 16");
+    // 8 <= S <= 64: the global attention kernels' LDS plan ends at the 64 x 64 window (attention.hip)
+    if (cfg->patch_size % 16) return fail(c, SRH_ERR_BAD_ARG, "PATCH_SIZE must be a multiple of 16 from 128 to 1024");
     const int S = cfg->patch_size / 16;
-    if (S != 16 && S != 32 && S != 64) return fail(c, SRH_ERR_UNSUPPORTED, "PATCH_SIZE must be 256, 512 or 1024");
+    if (S < 8 || S > 64) return fail(c, SRH_ERR_UNSUPPORTED, "PATCH_SIZE must be a multiple of 16 from 128 to 1024");
     if (cfg->window_size != 14) return fail(c, SRH_ERR_UNSUPPORTED, "window_size must be 14");
     if (D % 128 || (D != 768 && D != 1024 && D != 1280)) return fail(c, SRH_ERR_UNSUPPORTED, "embed_dim must be 768, 1024 or 1280");
     hipSetDevice(c->device);

@@ -171,12 +171,20 @@ __device__ __forceinline__ void load_query(QState& st, const AttnParams& p, size
 // then  rel[q, k] = P[q, qc - k + WIN - 1] / scale  is scattered into the wave's LDS table buf[q][k] (row stride STRIDE
 // floats).  The w table goes first: its 16 per-lane values (tile-invariant) are read back into st.relw, then the same
 // buffer is overwritten with the h table, which the key loop reads one or two scalars per tile.
-template <int WIN, int STRIDE>
+// RT (any S, attn_global_kernel's runtime-S form): WIN is the padded width class WP >= S, the window is S x S.  Table rows j map to
+// k = qc - j + S - 1; k outside [0, S) goes to the dump slot WP.  Slots S .. WP - 1 (columns / rows past the window) are set to -inf
+// first and never written after, so they read back as rel_w = -inf for the pad key columns and rel_h = -inf for the pad key rows:
+// every pad key slot's score is -inf, P = 0.
+template <int WIN, int STRIDE, bool RT = false>
 __device__ __forceinline__ void fused_relpos(QState& st, const AttnParams& p, int qy, int qx, float* buf, const char* tbl_w, const char* tbl_h, int lane) {
     constexpr int NTJ = (2 * WIN - 1 + 31) / 32;
     static_assert(STRIDE > WIN, "slot WIN of a row is the dump slot");
     const int half = lane >> 5, row = lane & 31;
     const float inv_scale = 1.0f / p.scale;
+    const int S = RT ? p.S : WIN;
+    if constexpr (RT) {
+        for (int c = S + half; c < WIN; c += 2) buf[row * STRIDE + c] = -INFINITY;
+    }
 #pragma unroll
     for (int pass = 0; pass < 2; ++pass) {            // 0: w table -> st.relw, 1: h table -> buf
         const int qc = pass == 0 ? qx : qy;
@@ -195,12 +203,13 @@ __device__ __forceinline__ void fused_relpos(QState& st, const AttnParams& p, in
             for (int ks = 0; ks < 4; ++ks) acc = mfma32(a[ks], st.q[ks], acc);
             // P^T[j, q] -> rel[q][k = qc - j + WIN - 1]: one subtract, one unsigned min and an unconditional write per element (k < 0
             // and k >= WIN — also the rows j > 2 WIN - 2 — land in the dump slot WIN) instead of two compares and an exec-masked write
-            const unsigned kb = (unsigned)(qc + WIN - 1 - jt * 32 - 4 * half);
+            const unsigned kb = (unsigned)(qc + S - 1 - jt * 32 - 4 * half);
             float* rowp = buf + row * STRIDE;
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const unsigned k = kb - (unsigned)((r & 3) + 8 * (r >> 2));
-                rowp[min(k, (unsigned)WIN)] = acc[r] * inv_scale;
+                if constexpr (RT) rowp[k < (unsigned)S ? k : (unsigned)WIN] = acc[r] * inv_scale;
+                else rowp[min(k, (unsigned)WIN)] = acc[r] * inv_scale;
             }
         }
         __builtin_amdgcn_wave_barrier();
@@ -610,16 +619,33 @@ __global__ __launch_bounds__(256, 2) void attn_window_kernel(AttnParams p) {
 // Against the register-staged ring of round 3 (global -> VGPR -> ds_write): bit-identical, 85.9 -> 79.2 us alone, 0.405 -> 0.366
 // ms per step in the model (profiles/r04_attention_dma_tr.txt).
 // ---------------------------------------------------------------------------------------------
-template <int WIN, int OCC>
+// Runtime S (RT = true, any 8 <= S <= 64 but 16 / 32 / 64, which keep the compile-time instantiations): WIN is then the padded width
+// class WP = 16 / 32 / 64 of Geom<WP> — the key slots are an S x WP image (row y, column x < WP) cut into the class's 32-row tiles, the
+// tile count rounded up to a multiple of 4 (the loop's two stages of two tiles) with whole pad rows.  Global attention has no pad keys:
+// a key slot with x >= S or y >= S loads a real token (clamped into the window: finite K / V) and gets rel_w = -inf (columns) or
+// rel_h = -inf (rows) from fused_relpos, so its score is -inf and P = 0.  The query count S * S need not be a multiple of 128: the
+// last block's tail lanes compute the clamped query S * S - 1 and do not store.
+template <int WP>
+__device__ __forceinline__ int gkey_off(int t, int r, int S, int ldb) {      // byte offset (from the image's token 0) of key slot r of tile t
+    int y, x;
+    if (WP == 16) { y = 2 * t + (r >> 4); x = r & 15; }
+    else if (WP == 32) { y = t; x = r; }
+    else { y = t >> 1; x = 32 * (t & 1) + r; }
+    return (min(y, S - 1) * S + min(x, S - 1)) * ldb;
+}
+
+template <int WIN, int OCC, bool RT = false>
 __global__ __launch_bounds__(256, OCC) void attn_global_kernel(AttnParams p) {
-    constexpr int NT = Geom<WIN>::NT, WP = Geom<WIN>::WP, RPT = Geom<WIN>::RPT;
+    constexpr int WP = Geom<WIN>::WP, RPT = Geom<WIN>::RPT;
     constexpr int STAGE = 2 * 4096 + 2 * 4096;   // 2 K tiles + 2 V tiles
     __shared__ __attribute__((aligned(16))) char ring0[STAGE];
     __shared__ __attribute__((aligned(16))) char ring1[STAGE];
     __shared__ __attribute__((aligned(16))) float rh_lds[4 * 32 * (WP + 1)];
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int S = p.S, D = p.heads * HD;
-    const int nqb = (S * S) / 128;
+    // key tiles: RT rounds up to a multiple of 4 (pad rows)
+    const int NT = RT ? ((WP == 16 ? (S + 1) / 2 : WP == 32 ? S : 2 * S) + 3) / 4 * 4 : Geom<WIN>::NT;
+    const int nqb = RT ? (S * S + 127) / 128 : (S * S) / 128;
     int qb, bh;
     {
         const int nbh = p.B * p.heads;
@@ -633,17 +659,28 @@ __global__ __launch_bounds__(256, OCC) void attn_global_kernel(AttnParams p) {
     const __amdgpu_buffer_rsrc_t rsq = __builtin_amdgcn_make_buffer_rsrc((void*)(p.qkv + tok0 * p.ld), 0, 0x7fffffff, 0x00020000);
     const int ldb = p.ld * 2;
     const int r = wave * 8 + (lane >> 3), cpos = lane & 7;
-    const int ko = r * ldb + (D + head * HD) * 2 + ((cpos ^ ((r >> 1) & 7)) * 16);               // read_kfrag's swizzle, source side
-    const int vo = r * ldb + (2 * D + head * HD) * 2 + ((cpos ^ (((r >> 1) & 1) * 4)) * 16);     // the ds_read_b64_tr_b16 swizzle (vtr_bases)
-#define SRH_DMA_STAGE(sidx, ring) { const int so_ = (sidx) * 64 * ldb; char* d_ = (ring) + wave * 1024; \
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rsq, (lds_ptr)(d_), 16, ko, so_, 0, 0); \
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rsq, (lds_ptr)(d_ + 4096), 16, ko, so_ + 32 * ldb, 0, 0); \
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rsq, (lds_ptr)(d_ + 8192), 16, vo, so_, 0, 0); \
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rsq, (lds_ptr)(d_ + 12288), 16, vo, so_ + 32 * ldb, 0, 0); }
+    const int kcol = (D + head * HD) * 2 + ((cpos ^ ((r >> 1) & 7)) * 16);               // read_kfrag's swizzle, source side
+    const int vcol = (2 * D + head * HD) * 2 + ((cpos ^ (((r >> 1) & 1) * 4)) * 16);     // the ds_read_b64_tr_b16 swizzle (vtr_bases)
+    const int ko = r * ldb + kcol, vo = r * ldb + vcol;
+    // S == WIN: key slot = token, a stage is 64 consecutive tokens (scalar offset); RT: the stage's two tiles' slots -> clamped tokens
+#define SRH_DMA_STAGE(sidx, ring) { char* d_ = (ring) + wave * 1024; \
+        if constexpr (RT) { \
+            const int oa_ = gkey_off<WP>(2 * (sidx), r, S, ldb), ob_ = gkey_off<WP>(2 * (sidx) + 1, r, S, ldb); \
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsq, (lds_ptr)(d_), 16, oa_ + kcol, 0, 0, 0); \
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsq, (lds_ptr)(d_ + 4096), 16, ob_ + kcol, 0, 0, 0); \
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsq, (lds_ptr)(d_ + 8192), 16, oa_ + vcol, 0, 0, 0); \
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsq, (lds_ptr)(d_ + 12288), 16, ob_ + vcol, 0, 0, 0); \
+        } else { \
+            const int so_ = (sidx) * 64 * ldb; \
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsq, (lds_ptr)(d_), 16, ko, so_, 0, 0); \
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsq, (lds_ptr)(d_ + 4096), 16, ko, so_ + 32 * ldb, 0, 0); \
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsq, (lds_ptr)(d_ + 8192), 16, vo, so_, 0, 0); \
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsq, (lds_ptr)(d_ + 12288), 16, vo, so_ + 32 * ldb, 0, 0); } }
     // the two rel-pos tables in the K-tile format (NTJ tiles of 4 KiB each): wave w moves rows 8 w .. 8 w + 7 of a tile.  Up to the 32 x 32
     // window both fit ring1 (K / V stage 1 overwrites it behind stage 0's barrier, which every wave passes after its rel-pos) and stage 0
     // of the K / V stream flies under the prologue; the 64 x 64 window's tables (127 rows each) fill BOTH ring stages — w in ring1, h in
-    // ring0 — and the K / V stream starts behind the rel-pos (one exposed stage of 64)
+    // ring0 — and the K / V stream starts behind the rel-pos (one exposed stage of 64).  RT sizes NTJ for the class's widest window
+    // (rows past 2 S - 2 are copies of the last row: dump slot)
     constexpr int NTJ = (2 * WIN - 1 + 31) / 32;
     constexpr bool TBL2 = 2 * NTJ * 4096 > STAGE;
     static_assert(NTJ * 4096 <= STAGE, "one table per ring stage at most");
@@ -651,7 +688,7 @@ __global__ __launch_bounds__(256, OCC) void attn_global_kernel(AttnParams p) {
         typedef const __attribute__((address_space(1))) void* glb_ptr;
 #pragma unroll
         for (int tt = 0; tt < 2 * NTJ; ++tt) {
-            const int j = min((tt % NTJ) * 32 + r, 2 * WIN - 2);
+            const int j = min((tt % NTJ) * 32 + r, 2 * (RT ? S : WIN) - 2);
             const f16* src = (tt < NTJ ? p.table_w : p.table_h) + (size_t)j * HD + (cpos ^ ((r >> 1) & 7)) * 8;
             char* dst = TBL2 ? (tt < NTJ ? ring1 : ring0) + (tt % NTJ) * 4096 : ring1 + tt * 4096;
             __builtin_amdgcn_global_load_lds((glb_ptr)src, (lds_ptr)(dst + wave * 1024), 16, 0, 0);
@@ -659,7 +696,9 @@ __global__ __launch_bounds__(256, OCC) void attn_global_kernel(AttnParams p) {
     }
     if constexpr (!TBL2) SRH_DMA_STAGE(0, ring0)                   // in flight under the query loads and the rel-pos prologue
 
-    const int qi = qb * 128 + wave * 32 + (lane & 31);
+    const int qi_raw = qb * 128 + wave * 32 + (lane & 31);
+    const bool qvalid = !RT || qi_raw < S * S;
+    const int qi = RT ? min(qi_raw, S * S - 1) : qi_raw;
     const size_t tok = tok0 + qi;
     QState st;
     load_query<WIN>(st, p, tok, head, lane);
@@ -668,7 +707,7 @@ __global__ __launch_bounds__(256, OCC) void attn_global_kernel(AttnParams p) {
     else __builtin_amdgcn_s_waitcnt(0x0F74);                       // vmcnt(4): the table pieces have landed (stage 0's four may stay in flight) ...
     __builtin_amdgcn_s_barrier();                                  // ... every wave's
     asm volatile("" ::: "memory");
-    fused_relpos<WIN, WP + 1>(st, p, qi / S, qi % S, rh, ring1, TBL2 ? ring0 : ring1 + NTJ * 4096, lane);
+    fused_relpos<WIN, WP + 1, RT>(st, p, qi / S, qi % S, rh, ring1, TBL2 ? ring0 : ring1 + NTJ * 4096, lane);
     if constexpr (TBL2) {
         __builtin_amdgcn_s_barrier();                              // every wave is done with the h table in ring0
         asm volatile("" ::: "memory");
@@ -678,8 +717,8 @@ __global__ __launch_bounds__(256, OCC) void attn_global_kernel(AttnParams p) {
     vtr_bases(lane, vb0, vb1);
 
     const float c_exp = p.scale * 1.4426950408889634f;
-    constexpr int NSTAGE = NT / 2;
-    static_assert(NSTAGE % 2 == 0, "the key loop is unrolled by two stages");
+    const int NSTAGE = NT / 2;
+    static_assert(RT || Geom<WIN>::NT % 4 == 0, "the key loop is unrolled by two stages");
     // rel_h entries (one per window row) between the two tiles of a stage / per stage: the 64 x 64 window's stage is ONE row
     constexpr int RSTEP = WIN == 64 ? 0 : RPT, RSTAGE = WIN == 64 ? 1 : 2 * RPT;
     const float* rhp = rh + (lane & 31) * (WP + 1);
@@ -705,7 +744,7 @@ __global__ __launch_bounds__(256, OCC) void attn_global_kernel(AttnParams p) {
         rhp += 2 * RSTAGE;
     }
     __builtin_amdgcn_s_waitcnt(0x0F70);                        // the tail's re-load of the last stage must not outlive the workgroup's LDS
-    store_query(st, p, tok, head, lane, true);
+    store_query(st, p, tok, head, lane, qvalid);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -834,7 +873,10 @@ int launch_attention(const AttnParams& p_in, hipStream_t s) {
 #else
     p.ablate = 0;
 #endif
-    const bool mfma_path = p.hd == HD && (p.win == 14 || (p.win == p.S && (p.S == 16 || p.S == 32 || p.S == 64)));
+    // global windows: S = 16 / 32 / 64 their own instantiations; any other 8 <= S <= 64 the runtime-S form of the padded width class
+    const bool global_fixed = p.win == p.S && (p.S == 16 || p.S == 32 || p.S == 64);
+    const bool global_any = p.win == p.S && !global_fixed && p.S >= 8 && p.S <= 64;
+    const bool mfma_path = p.hd == HD && (p.win == 14 || global_fixed || global_any);
     if (!mfma_path && attention_hdx_supported(p)) return launch_attention_hdx(p, s);
     if (!mfma_path) {      // other head dims / windows (ViT-H at 512 / 1024 px)
         if ((p.hd != 64 && p.hd != 80) || !p.table_h || !p.table_w || p.win > 64) return -2;
@@ -852,12 +894,16 @@ int launch_attention(const AttnParams& p_in, hipStream_t s) {
         else hipLaunchKernelGGL(attn_generic_kernel<10>, grid, dim3(256), lds, s, p);
         return hipGetLastError() == hipSuccess ? 0 : -3;
     }
-    if (p.win == p.S) {
+    if (global_fixed) {
         const int grid = p.B * p.heads * (p.S * p.S / 128);
         if (p.S == 32) hipLaunchKernelGGL((attn_global_kernel<32, 3>), dim3(grid), dim3(256), 0, s, p);
         else if (p.S == 16) hipLaunchKernelGGL((attn_global_kernel<16, 2>), dim3(grid), dim3(256), 0, s, p);
-        else if (p.S == 64) hipLaunchKernelGGL((attn_global_kernel<64, 2>), dim3(grid), dim3(256), 0, s, p);   // 65 KiB of static LDS: two workgroups per CU
-        else return -2;
+        else hipLaunchKernelGGL((attn_global_kernel<64, 2>), dim3(grid), dim3(256), 0, s, p);   // 65 KiB of static LDS: two workgroups per CU
+    } else if (global_any) {
+        const int grid = p.B * p.heads * ((p.S * p.S + 127) / 128);
+        if (p.S < 16) hipLaunchKernelGGL((attn_global_kernel<16, 2, true>), dim3(grid), dim3(256), 0, s, p);
+        else if (p.S < 32) hipLaunchKernelGGL((attn_global_kernel<32, 3, true>), dim3(grid), dim3(256), 0, s, p);
+        else hipLaunchKernelGGL((attn_global_kernel<64, 2, true>), dim3(grid), dim3(256), 0, s, p);
     } else if (p.win == 14) {
         static OncePerDevice window_opt_in;
         if (!window_opt_in.run([] { return hipFuncSetAttribute(reinterpret_cast<const void*>(attn_window_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, WIN_LDS) == hipSuccess; }))

@@ -83,15 +83,21 @@ __global__ __launch_bounds__(DF_WAVES * 64) void decode_fused_kernel(DecodeFused
 #define DF_FR(base, fi) (*reinterpret_cast<const f16x8*>((base) + (fi) * 1024 + lane * 16))
     const int S = p.S, P = S * 16;
     constexpr int JT = 16 * NCG;                                     // tokens per wave job
-    const int ngroups = (p.B * S * S) / JT;                          // (S * S is a multiple of 256)
+    // T = B S S need not be a multiple of JT (odd S, or S = 2 mod 4 at B = 1): the last job's lanes past T load token T - 1 and store
+    // nothing (nor raise the non-finite sentinel); full jobs are unchanged
+    const int T = p.B * S * S;
+    const int ngroups = (T + JT - 1) / JT;
     const int wg_stride = (gridDim.x >> 2) * DF_WAVES;
     const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
     for (int tg = (blockIdx.x >> 2) * DF_WAVES + wave; tg < ngroups; tg += wg_stride) {
         // ---- layer 0 slice: U^T[co, token] for this sub1, K = 256 straight from memory
         f16x8 xin[NCG][8];
+        bool tvalid[NCG];
 #pragma unroll
         for (int cg = 0; cg < NCG; ++cg) {
-            const f16* xr = p.emb16 + ((size_t)tg * JT + cg * 16 + n) * 256 + 8 * g;
+            const int tk = tg * JT + cg * 16 + n;
+            tvalid[cg] = tk < T;
+            const f16* xr = p.emb16 + (size_t)min(tk, T - 1) * 256 + 8 * g;
 #pragma unroll
             for (int kb = 0; kb < 8; ++kb) xin[cg][kb] = *reinterpret_cast<const f16x8*>(xr + 32 * kb);
         }
@@ -127,7 +133,7 @@ __global__ __launch_bounds__(DF_WAVES * 64) void decode_fused_kernel(DecodeFused
 #pragma unroll
                 for (int r = 0; r < 4; ++r) { a0[rt][cg][r] -= mean; q = fmaf(a0[rt][cg][r], a0[rt][cg][r], q); }
             const float var = df_sum4(q) * (1.0f / 128.0f);
-            if (p.nf && !(var < INFINITY) && g == 0) p.nf[p.nf_tag] = 1u;
+            if (p.nf && !(var < INFINITY) && g == 0 && tvalid[cg]) p.nf[p.nf_tag] = 1u;
             const float rstd = rsqrtf(var + 1e-6f);
 #pragma unroll
             for (int rt = 0; rt < 8; ++rt) {
@@ -143,7 +149,7 @@ __global__ __launch_bounds__(DF_WAVES * 64) void decode_fused_kernel(DecodeFused
         int ob[NCG], oy[NCG], ox[NCG];
 #pragma unroll
         for (int cg = 0; cg < NCG; ++cg) {
-            int tk = tg * JT + cg * 16 + n;
+            int tk = min(tg * JT + cg * 16 + n, T - 1);
             const int px = tk % S; tk /= S;
             const int py = tk % S; ob[cg] = tk / S;
             oy[cg] = py * 2 + (sub1 >> 1); ox[cg] = px * 2 + (sub1 & 1);
@@ -209,7 +215,7 @@ __global__ __launch_bounds__(DF_WAVES * 64) void decode_fused_kernel(DecodeFused
                     const f16x8 ub = df_pack8(a5[2 * s3][cg], a5[2 * s3 + 1][cg]);
                     f32x4 o = mfma16(a7h, ub, zero);
                     o = mfma16(a7l, ub, o);
-                    if (g < 2) {
+                    if (g < 2 && tvalid[cg]) {
                         const int y = (((oy[cg] * 2 + (s2 >> 1)) * 2 + (s3 >> 1)) * 2) + g;
                         const int xx = ((ox[cg] * 2 + (s2 & 1)) * 2 + (s3 & 1)) * 2;
                         const size_t off = (((size_t)ob[cg] * P + y) * P + xx) * 2;
@@ -231,12 +237,11 @@ __global__ __launch_bounds__(DF_WAVES * 64) void decode_fused_kernel(DecodeFused
 int launch_decode_fused(const DecodeFusedParams& p, hipStream_t s) {
     const long T = (long)p.B * p.S * p.S;
     if (T <= 0) return 0;
-    if (T % 32 || (p.S != 16 && p.S != 32 && p.S != 64)) return -2;
     constexpr int NCG = 1, NW = 16;
     static OncePerDevice opt_in;
     if (!opt_in.run([] { return hipFuncSetAttribute(reinterpret_cast<const void*>(decode_fused_kernel<NCG, NW>), hipFuncAttributeMaxDynamicSharedMemorySize, DF_LDS) == hipSuccess; }))
         return -3;
-    const long ngroups = T / (16 * NCG);
+    const long ngroups = (T + 16 * NCG - 1) / (16 * NCG);                 // the last job may be partial
     const long per_sub = (ngroups + NW - 1) / NW;                         // workgroups per sub1 when every wave gets one job
     const unsigned grid = 4u * (unsigned)(per_sub < 64 ? per_sub : 64);   // one workgroup per CU at most (150 KiB of LDS each)
     hipLaunchKernelGGL((decode_fused_kernel<NCG, NW>), dim3(grid), dim3(NW * 64), DF_LDS, s, p);
