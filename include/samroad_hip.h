@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define SRH_ABI_VERSION 9
+#define SRH_ABI_VERSION 10
 
 typedef enum {
     SRH_OK = 0,
@@ -112,7 +112,8 @@ int srh_encode_decode(srh_ctx* ctx, const srh_weights* w, const void* rgb, int r
 
 /* SAMRoad.infer_toponet (model.py:498-508) = BilinearSampler (:29-58) + TopoNet (:61-148).
  * embeddings [B,h,w,256] f32 channels-last; points [B,N,2] (x,y) SRH_I64 or SRH_F32;
- * pairs [B,Ns,K,2] SRH_I64 or SRH_I32; valid [B,Ns,K] u8 (bool); K must be 16.
+ * pairs [B,Ns,K,2] SRH_I64 or SRH_I32; valid [B,Ns,K] u8 (bool).
+ * ABI 10: K = MAX_NEIGHBOR_QUERIES may be 1 to 64 (it had to be 16); any other K is SRH_ERR_UNSUPPORTED.
  *   -> logits (nullable) / scores (nullable) [B,Ns,K] f32. */
 int srh_toponet(srh_ctx* ctx, const srh_weights* w, const float* embeddings, const void* points,
                 int points_dtype, const void* pairs, int pairs_dtype, const uint8_t* valid, int B, int N,
@@ -125,9 +126,11 @@ int srh_toponet(srh_ctx* ctx, const srh_weights* w, const float* embeddings, con
  * `embeddings` (clamped into [0, n_tiles)); pairs i32 [R,K,2] = (row, target row) into the flat list; valid u8 [R,K]; scores f32
  * [R,K] out.  srh_pass2_pack_ragged builds these.
  * ABI 8: tile_offsets (HOST pointer, int64 [n_tiles + 1], nullable) = the first row of every tile, from 0 to R.  With it the rows are
- * scored in chunks of whole tiles of at most 16 384 rows (same bits: rows are independent and a pair only names rows of its own
- * tile), so the context's workspace is bounded like the reference's INFER_BATCH_SIZE batches instead of growing with the scene;
- * without it the call is one launch and refuses more than 65 536 rows.
+ * scored in chunks of whole tiles of at most 16 384 x 16 pairs (rows x K; same bits: rows are independent and a pair only names rows
+ * of its own tile), so the context's workspace is bounded like the reference's INFER_BATCH_SIZE batches instead of growing with the
+ * scene; without it the call is one launch and refuses more than 65 536 x 16 pairs.
+ * ABI 10: K may be 1 to 64 (it had to be 16); any other K is SRH_ERR_UNSUPPORTED.  The bounds above count pairs, so they are the
+ * 16 384 / 65 536 rows of ABI 8 at K = 16.
  * ABI 9: both indices of every pair must be rows in [0, R) whose point_tile equals the source row's (no python-style wrap of a
  * negative index).  The pair gather checks this on the device; a pair that breaks it makes the call's scores invalid and is reported
  * like the non-finite sentinel — SRH_ERR_BAD_ARG from srh_ctx_check or the next srh_encode_decode / srh_scene_pass1 on the context —

@@ -977,7 +977,7 @@ static int toponet_impl(srh_ctx* c, const srh_weights* w, const float* embedding
                         int Ns, int K, float* logits, float* scores, const int* point_tile, int n_tiles, long pair_base, void* stream) {
     if (!c || !w || !embeddings || !points || !pairs || !valid) return fail(c, SRH_ERR_BAD_ARG, "srh_toponet: null argument");
     if (B <= 0 || N < 0 || Ns < 0) return fail(c, SRH_ERR_BAD_ARG, "srh_toponet: bad sizes");
-    if (K != 16) return fail(c, SRH_ERR_UNSUPPORTED, "n_pairs must be 16 (MAX_NEIGHBOR_QUERIES)");
+    if (K < 1 || K > 64) return fail(c, SRH_ERR_UNSUPPORTED, "n_pairs (MAX_NEIGHBOR_QUERIES) must be 1 to 64");
     if (points_dtype != SRH_I64 && points_dtype != SRH_F32) return fail(c, SRH_ERR_BAD_ARG, "points dtype must be i64 or f32");
     if (pairs_dtype != SRH_I64 && pairs_dtype != SRH_I32) return fail(c, SRH_ERR_BAD_ARG, "pairs dtype must be i64 or i32");
     if (N == 0 || Ns == 0) return 0;
@@ -1009,8 +1009,8 @@ static int toponet_impl(srh_ctx* c, const srh_weights* w, const float* embedding
         // pair_proj + encoder layers + output_proj in one register-resident kernel (topo_fused.hip)
         TopoFusedParams tf;
         tf.pair = c->t_pair16.as<f16>(); tf.ld_pair = 320; tf.valid = valid; tf.stream = w->tp_stream; tf.params = w->tp_params;
-        tf.nlayers = w->tp_layers; tf.nseq = B * Ns; tf.logits = logits; tf.scores = scores;
-        const double fl = (double)R * (2.0 * 320 * 128 + tf.nlayers * (2.0 * 128 * 768 + 4.0 * 16 * 128) + 256);
+        tf.nlayers = w->tp_layers; tf.nseq = B * Ns; tf.K = K; tf.logits = logits; tf.scores = scores;
+        const double fl = (double)R * (2.0 * 320 * 128 + tf.nlayers * (2.0 * 128 * 768 + 4.0 * K * 128) + 256);
         TRYK(c, "topo_fused", fl, 0, s, launch_topo_fused(tf, s));
         return 0;
     }
@@ -1030,15 +1030,18 @@ extern "C" int srh_toponet_ragged(srh_ctx* c, const srh_weights* w, const float*
                                   const int64_t* tile_offsets, float* scores, void* stream) {
     if (!point_tile || !scores) return fail(c, SRH_ERR_BAD_ARG, "srh_toponet_ragged: null argument");
     if (n_tiles <= 0) return fail(c, SRH_ERR_BAD_ARG, "srh_toponet_ragged: n_tiles must be the number of tiles in `embeddings`");
-    if (R < 0 || K != 16) return fail(c, R < 0 ? SRH_ERR_BAD_ARG : SRH_ERR_UNSUPPORTED, "srh_toponet_ragged: bad row count / n_pairs must be 16");
+    if (R < 0) return fail(c, SRH_ERR_BAD_ARG, "srh_toponet_ragged: bad row count");
+    if (K < 1 || K > 64) return fail(c, SRH_ERR_UNSUPPORTED, "srh_toponet_ragged: n_pairs (MAX_NEIGHBOR_QUERIES) must be 1 to 64");
     // Workspace bound (the reference's pass 2 is bounded by INFER_BATCH_SIZE, inferencer.py:179-207): with the tiles' row offsets the
-    // scene is scored in chunks of whole tiles of at most RAGGED_CHUNK_ROWS rows — rows are independent and a pair only names rows of
-    // its own tile, so the chunks' scores are those of the one launch, bit for bit — and the pair workspace stays below ~210 MB
-    // however large the scene (it grew with the scene before: 0.6 GB for a 48 k-row CityScale scene, ~10 GB for an 8192^2 one).
-    // Without offsets the caller's rows go through ONE launch and must fit the same bound.
-    constexpr int64_t RAGGED_CHUNK_ROWS = 16384;
+    // scene is scored in chunks of whole tiles of at most RAGGED_CHUNK_PAIRS pairs (16 384 rows at K = 16) — rows are independent and a
+    // pair only names rows of its own tile, so the chunks' scores are those of the one launch, bit for bit — and the pair workspace
+    // stays below ~210 MB whatever K and however large the scene (it grew with the scene before: 0.6 GB for a 48 k-row CityScale scene,
+    // ~10 GB for an 8192^2 one).  Without offsets the caller's rows go through ONE launch and must fit 4x that bound.
+    constexpr int64_t RAGGED_CHUNK_PAIRS = 16384 * 16;
+    const int64_t chunk_rows = RAGGED_CHUNK_PAIRS / K;
     if (!tile_offsets) {
-        if (R > 4 * RAGGED_CHUNK_ROWS) return fail(c, SRH_ERR_BAD_ARG, "srh_toponet_ragged: more than 65536 rows need tile_offsets (chunked at tile boundaries)");
+        if (R * K > 4 * RAGGED_CHUNK_PAIRS)
+            return fail(c, SRH_ERR_BAD_ARG, "srh_toponet_ragged: more than 1048576 pairs (rows x n_pairs) need tile_offsets (chunked at tile boundaries)");
         return toponet_impl(c, w, embeddings, points, SRH_F32, pairs, SRH_I32, valid, 1, (int)R, (int)R, K, nullptr, scores, point_tile, n_tiles, 0, stream);
     }
     if (tile_offsets[0] != 0 || tile_offsets[n_tiles] != R) return fail(c, SRH_ERR_BAD_ARG, "srh_toponet_ragged: tile_offsets must run from 0 to R");
@@ -1046,7 +1049,7 @@ extern "C" int srh_toponet_ragged(srh_ctx* c, const srh_weights* w, const float*
         if (tile_offsets[t + 1] < tile_offsets[t]) return fail(c, SRH_ERR_BAD_ARG, "srh_toponet_ragged: tile_offsets must ascend");
     for (int ta = 0; ta < n_tiles;) {
         int tb = ta + 1;                                                          // at least one tile (a tile above the bound is its own chunk)
-        while (tb < n_tiles && tile_offsets[tb + 1] - tile_offsets[ta] <= RAGGED_CHUNK_ROWS) ++tb;
+        while (tb < n_tiles && tile_offsets[tb + 1] - tile_offsets[ta] <= chunk_rows) ++tb;
         const int64_t r0 = tile_offsets[ta], n = tile_offsets[tb] - r0;
         if (n > 0x7fffffffLL / (2 * K)) return fail(c, SRH_ERR_BAD_ARG, "srh_toponet_ragged: a single tile has too many rows");
         if (n > 0)

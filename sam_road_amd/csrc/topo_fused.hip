@@ -70,13 +70,36 @@ __device__ __forceinline__ void tf_layernorm(f32x4 (&x)[8], const f32x4 (&y)[8],
     }
 }
 
-template <int NL>
+// Sequence length K = MAX_NEIGHBOR_QUERIES, 1 <= K <= 64.  The token is the MFMA N dimension, so a wave's 16-token tile is
+// filled by one of three mappings (template parameter G, the host picks it from K):
+//   G = 0   K = 16: one sequence per wave, the original instantiation.
+//   G = 1   K <= 15: 16 / S sequences packed into one tile, S = K rounded up to a power of two, sequence i on tokens i S ..
+//           i S + K - 1; a key counts only for the queries of its own sequence (block-diagonal mask), the all-invalid flip is per
+//           sequence.  Pad tokens (n % S >= K) load a real row, attend to themselves only, are never keys of a real query and are
+//           never stored.  The power-of-two slots keep a sequence's sums position-independent: its keys fill an aligned block of
+//           the softmax sum tree (lane-local r, then xor-16, xor-32) and of the MFMA k dimension, everything else adds exact zeros,
+//           so its scores do not depend on its slot or its tile mates.  With NL = 0 (no attention) the tile is simply 16
+//           consecutive pair rows.
+//   G = 2-4 17 <= K <= 64: G waves of the workgroup own one sequence, one tile each (TF_NW / G sequences per workgroup pass, the
+//           two spare waves at G = 3 compute a copy of group 0 and store nothing).  Per-token work stays wave-local; per head every
+//           wave publishes its K^T tile pair (and, once per layer, its V tiles) in an LDS exchange slot, and after one barrier
+//           computes S^T against the G key tiles, softmax over G x 16 keys (lane-local over the tiles, then the xor-16 / 32
+//           exchanges) and O^T = sum_j V_j^T P_j^T.  Tokens 16 j + n >= K are pad tokens as above, but attend the sequence's keys.
+constexpr int TF_XSLOT = 8192;                // G >= 2 exchange slot per wave: V (8 tiles x 512 B), K^T (4 heads x 1 KiB)
+constexpr int tf_nprm(int nl) { return 128 + 1280 * nl + 132; }
+constexpr int tf_lds(int nl, int G) { return TF_RING + tf_nprm(nl) * 4 + (G >= 2 ? TF_NW * TF_XSLOT + TF_NW * 4 : 0); }
+__host__ __device__ constexpr int tf_log2_ceil(int k) { int l = 0; while ((1 << l) < k) ++l; return l; }
+static_assert(tf_nprm(3) % 4 == 0 && tf_nprm(0) % 4 == 0, "exchange area alignment");
+
+template <int NL, int G>
 __global__ __launch_bounds__(TF_NW * 64) void topo_fused_kernel(TopoFusedParams p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char* const ring = smem;
     float* const prm = reinterpret_cast<float*>(smem + TF_RING);
+    char* const xch = smem + TF_RING + tf_nprm(NL) * 4;                  // G >= 2: TF_NW slots, then TF_NW tile valid masks
     constexpr int NCH = 5 + 12 * NL;
-    constexpr int NPRM = 128 + 1280 * NL + 132;
+    constexpr int NPRM = tf_nprm(NL);
+    constexpr int GT = G > 1 ? G : 1;                                     // key tiles per query
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int n = lane & 15, g = lane >> 4;
     for (int i = tid; i < NPRM; i += TF_NW * 64) prm[i] = p.params[i];
@@ -98,28 +121,80 @@ __global__ __launch_bounds__(TF_NW * 64) void topo_fused_kernel(TopoFusedParams 
         __builtin_amdgcn_s_barrier(); \
         if ((ci) + 3 < NCH) { TF_DMA((ci) + 3) } }
 #define TF_B4(off) (*reinterpret_cast<const f32x4*>(prm + (off)))
+    // G >= 2 exchange: this wave's LDS writes are done, then every wave's are visible (LDS-DMA of the ring may stay in flight)
+#define TF_XBAR() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); __builtin_amdgcn_s_barrier(); }
+#define TF_XV(w, c) (*reinterpret_cast<f16x4*>(xch + (w) * TF_XSLOT + (c) * 512 + lane * 8))
+#define TF_XK(w, h) (*reinterpret_cast<f16x8*>(xch + (w) * TF_XSLOT + 4096 + (h) * 1024 + lane * 16))
 
+    // work units per workgroup pass: sequences (G = 0, G >= 2, G = 1 with attention) or pair rows (G = 1 without attention)
+    const int K = p.K;
+    const int per = G == 0 ? TF_NW : G >= 2 ? TF_NW / GT : NL == 0 ? TF_NW * 16 : TF_NW * (16 >> tf_log2_ceil(K));
+    const int nunits = G == 1 && NL == 0 ? p.nseq * K : p.nseq;
     const float c_exp = 0.17677669529663687f * 1.4426950408889634f;      // 32^-0.5 * log2(e)
-    for (int sg = blockIdx.x; sg * TF_NW < p.nseq; sg += gridDim.x) {
-        const int seq_raw = sg * TF_NW + wave;
-        const bool live = seq_raw < p.nseq;
-        const int seq = live ? seq_raw : p.nseq - 1;
-        // the sequence's 16 pair rows as B operands (natural k order: pair_proj's fragments are packed to match)
-        const f16* row = p.pair + ((size_t)seq * 16 + n) * p.ld_pair + 8 * g;
+    for (int sg = blockIdx.x; sg * per < nunits; sg += gridDim.x) {
+        int seq = 0, rowi = 0;
+        bool live = false;
+        uint32_t vbits = 0;      // G = 0: valid bytes of keys 4 g .. 4 g + 3
+        uint32_t kbits = 0;      // G >= 1: bit 4 j + r set = key 16 j + 4 g + r counts for this lane's query
+        if constexpr (G == 0) {
+            const int seq_raw = sg * TF_NW + wave;
+            live = seq_raw < p.nseq;
+            seq = live ? seq_raw : p.nseq - 1;
+        } else if constexpr (NL == 0) {
+            const int t = (sg * TF_NW + wave) * 16 + n;
+            live = t < nunits;
+            rowi = live ? t : nunits - 1;
+        } else if constexpr (G == 1) {
+            // sequence s0 + i owns tokens i * S .. i * S + K - 1 (S = K rounded up to a power of two); a token with n % S >= K is a pad
+            const int lg = tf_log2_ceil(K), sub = n >> lg, slot = n & ((1 << lg) - 1), s0 = (sg * TF_NW + wave) * (16 >> lg);
+            live = slot < K && s0 + sub < p.nseq;
+            rowi = live ? (s0 + sub) * K + slot : p.nseq * K - 1;
+            uint32_t vm = (uint32_t)__ballot(live && p.valid[(size_t)rowi]) & 0xffffu;     // bit n: token n is a valid key
+            // model.py:129-130 per packed sequence: one without any valid key attends to all of its keys
+            const uint32_t all = (1u << K) - 1;
+            for (int i = 0; i < (16 >> lg); ++i)
+                if (!(vm & (all << (i << lg)))) vm |= all << (i << lg);
+            // block-diagonal mask; a pad token attends to itself only
+            const uint32_t am = slot < K ? vm & (all << (sub << lg)) : 1u << n;
+            kbits = (am >> (4 * g)) & 0xfu;
+        } else {
+            constexpr int NG = TF_NW / G;
+            const int gi = wave / G, j = wave - gi * G, seq_raw = sg * NG + gi;
+            seq = seq_raw < p.nseq ? seq_raw : p.nseq - 1;
+            const int t = 16 * j + n;
+            live = gi < NG && seq_raw < p.nseq && t < K;
+            rowi = seq * K + (t < K ? t : K - 1);
+            const uint32_t vm = (uint32_t)__ballot(t < K && p.valid[(size_t)rowi]) & 0xffffu;   // bit n: key 16 j + n is valid
+            uint32_t* const xvm = reinterpret_cast<uint32_t*>(xch + TF_NW * TF_XSLOT);
+            if (lane == 0) xvm[wave] = vm;
+            TF_XBAR()
+            const int gb = (gi < NG ? gi : 0) * G;                        // the spare waves read group 0
+            uint64_t sm = 0;
+#pragma unroll
+            for (int jj = 0; jj < G; ++jj) sm |= (uint64_t)xvm[gb + jj] << (16 * jj);
+            if (!sm) sm = K == 64 ? ~0ull : (1ull << K) - 1;            // model.py:129-130 across the group
+#pragma unroll
+            for (int jj = 0; jj < G; ++jj) kbits |= (uint32_t)((sm >> (16 * jj + 4 * g)) & 0xfu) << (4 * jj);
+        }
+        // the tile's 16 pair rows as B operands (natural k order: pair_proj's fragments are packed to match)
+        const f16* row = p.pair + (G == 0 ? (size_t)seq * 16 + n : (size_t)rowi) * p.ld_pair + 8 * g;
+        const int orow = live ? rowi : -1;                                 // G >= 1: the output this lane's token stores, if any
         f16x8 xin[10];
 #pragma unroll
         for (int kb = 0; kb < 10; ++kb) xin[kb] = *reinterpret_cast<const f16x8*>(row + 32 * kb);
-        uint32_t vbits = *reinterpret_cast<const uint32_t*>(p.valid + (size_t)seq * 16 + 4 * g);   // keys 4g .. 4g+3
+        if constexpr (G == 0) vbits = *reinterpret_cast<const uint32_t*>(p.valid + (size_t)seq * 16 + 4 * g);   // keys 4g .. 4g+3
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();          // params visible / the previous pass has released the ring
         TF_DMA(0) TF_DMA(1) TF_DMA(2)
         // model.py:129-130: a sequence without any valid key attends to every key
-        {
+        if constexpr (G == 0) {
             int any = vbits != 0;
             any |= __shfl_xor(any, 16, 64);
             any |= __shfl_xor(any, 32, 64);
             if (!any) vbits = 0x01010101u;
         }
+        // the G >= 2 sequence's first wave (exchange slots gb ..)
+        const int xb = G >= 2 ? ((wave / GT) < TF_NW / GT ? (wave / GT) : 0) * GT : 0;
 
         f32x4 xs[8];        // residual stream, C layout: token n, features 16 t + 4 g + r
         f16x8 xp[4];        // the same as MFMA operand (k block kb = row tiles 2 kb, 2 kb + 1)
@@ -164,6 +239,7 @@ __global__ __launch_bounds__(TF_NW * 64) void topo_fused_kernel(TopoFusedParams 
 #pragma unroll
                     for (int r = 0; r < 4; ++r) a[r] += bv;
                     vp[c] = tf_pack4(a);
+                    if constexpr (G >= 2) TF_XV(wave, c) = vp[c];       // read by the group after head 0's exchange barrier
                 }
             }
             // ---- per head: Q^T, K^T tile pairs -> S^T -> softmax over keys -> O^T = V^T P^T
@@ -182,23 +258,58 @@ __global__ __launch_bounds__(TF_NW * 64) void topo_fused_kernel(TopoFusedParams 
                     for (int r = 0; r < 4; ++r) qk[i][r] += b[r];
                 }
                 const f16x8 qp = tf_pack8(qk[0], qk[1]), kp = tf_pack8(qk[2], qk[3]);
-                f32x4 s = mfma16(kp, qp, f32x4{0.f, 0.f, 0.f, 0.f});       // s[r]: key 4 g + r, query n
-                float m = -INFINITY;
+                if constexpr (G == 0) {
+                    f32x4 s = mfma16(kp, qp, f32x4{0.f, 0.f, 0.f, 0.f});       // s[r]: key 4 g + r, query n
+                    float m = -INFINITY;
 #pragma unroll
-                for (int r = 0; r < 4; ++r) { if (!((vbits >> (8 * r)) & 0xffu)) s[r] = -INFINITY; m = fmaxf(m, s[r]); }
-                m = tf_max4(m);
-                const float mc = -m * c_exp;
-                f32x4 e;
-                float sum = 0.f;
+                    for (int r = 0; r < 4; ++r) { if (!((vbits >> (8 * r)) & 0xffu)) s[r] = -INFINITY; m = fmaxf(m, s[r]); }
+                    m = tf_max4(m);
+                    const float mc = -m * c_exp;
+                    f32x4 e;
+                    float sum = 0.f;
 #pragma unroll
-                for (int r = 0; r < 4; ++r) { e[r] = __builtin_amdgcn_exp2f(fmaf(s[r], c_exp, mc)); sum += e[r]; }
-                const float inv = 1.0f / tf_sum4(sum);
-                const f16x4 pp = tf_pack4(e);
-                f32x4 o0 = mfma16k16(vp[2 * h], pp, f32x4{0.f, 0.f, 0.f, 0.f});
-                f32x4 o1 = mfma16k16(vp[2 * h + 1], pp, f32x4{0.f, 0.f, 0.f, 0.f});
+                    for (int r = 0; r < 4; ++r) { e[r] = __builtin_amdgcn_exp2f(fmaf(s[r], c_exp, mc)); sum += e[r]; }
+                    const float inv = 1.0f / tf_sum4(sum);
+                    const f16x4 pp = tf_pack4(e);
+                    f32x4 o0 = mfma16k16(vp[2 * h], pp, f32x4{0.f, 0.f, 0.f, 0.f});
+                    f32x4 o1 = mfma16k16(vp[2 * h + 1], pp, f32x4{0.f, 0.f, 0.f, 0.f});
 #pragma unroll
-                for (int r = 0; r < 4; ++r) { o0[r] *= inv; o1[r] *= inv; }
-                op[h] = tf_pack8(o0, o1);
+                    for (int r = 0; r < 4; ++r) { o0[r] *= inv; o1[r] *= inv; }
+                    op[h] = tf_pack8(o0, o1);
+                } else {
+                    f32x4 s[GT];                                               // s[j][r]: key 16 j + 4 g + r, query n
+                    if constexpr (G >= 2) {
+                        TF_XK(wave, h) = kp;
+                        TF_XBAR()
+#pragma unroll
+                        for (int j = 0; j < GT; ++j) s[j] = mfma16(TF_XK(xb + j, h), qp, f32x4{0.f, 0.f, 0.f, 0.f});
+                    } else {
+                        s[0] = mfma16(kp, qp, f32x4{0.f, 0.f, 0.f, 0.f});
+                    }
+                    float m = -INFINITY;
+#pragma unroll
+                    for (int j = 0; j < GT; ++j)
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) { if (!((kbits >> (4 * j + r)) & 1u)) s[j][r] = -INFINITY; m = fmaxf(m, s[j][r]); }
+                    m = tf_max4(m);
+                    const float mc = -m * c_exp;
+                    float sum = 0.f;
+#pragma unroll
+                    for (int j = 0; j < GT; ++j)
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) { s[j][r] = __builtin_amdgcn_exp2f(fmaf(s[j][r], c_exp, mc)); sum += s[j][r]; }
+                    const float inv = 1.0f / tf_sum4(sum);
+                    f32x4 o0 = f32x4{0.f, 0.f, 0.f, 0.f}, o1 = o0;
+#pragma unroll
+                    for (int j = 0; j < GT; ++j) {
+                        const f16x4 pp = tf_pack4(s[j]);
+                        o0 = mfma16k16(G >= 2 ? TF_XV(xb + j, 2 * h) : vp[2 * h], pp, o0);
+                        o1 = mfma16k16(G >= 2 ? TF_XV(xb + j, 2 * h + 1) : vp[2 * h + 1], pp, o1);
+                    }
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) { o0[r] *= inv; o1[r] *= inv; }
+                    op[h] = tf_pack8(o0, o1);
+                }
             }
             // ---- out_proj + residual -> LayerNorm 1
             f32x4 y[8];
@@ -266,8 +377,8 @@ __global__ __launch_bounds__(TF_NW * 64) void topo_fused_kernel(TopoFusedParams 
             for (int r = 0; r < 4; ++r) d = fmaf(xs[t][r], wv[r], d);
         }
         d = tf_sum4(d) + prm[128 + 1280 * NL + 128];
-        if (live && g == 0) {
-            const size_t o = (size_t)seq * 16 + n;
+        if (G == 0 ? live && g == 0 : orow >= 0 && g == 0) {
+            const size_t o = G == 0 ? (size_t)seq * 16 + n : (size_t)orow;
             if (p.logits) p.logits[o] = d;
             if (p.scores) p.scores[o] = sigmoidf_(d);
         }
@@ -276,24 +387,43 @@ __global__ __launch_bounds__(TF_NW * 64) void topo_fused_kernel(TopoFusedParams 
 #undef TF_DMA
 #undef TF_STEP
 #undef TF_B4
+#undef TF_XBAR
+#undef TF_XV
+#undef TF_XK
+}
+
+template <int NL, int G>
+static int tf_launch(const TopoFusedParams& p, hipStream_t s) {
+    // work units and units per workgroup pass, as in the kernel
+    const long units = G == 1 && NL == 0 ? (long)p.nseq * p.K : p.nseq;
+    const int per = G == 0 ? TF_NW : G >= 2 ? TF_NW / G : NL == 0 ? TF_NW * 16 : TF_NW * (16 >> tf_log2_ceil(p.K));
+    const long groups = (units + per - 1) / per;
+    const int grid = groups < 256 ? (int)groups : 256;
+    hipLaunchKernelGGL((topo_fused_kernel<NL, G>), dim3(grid), dim3(TF_NW * 64), tf_lds(NL, G), s, p);
+    return SRH_CHECK_LAUNCH();
+}
+
+template <int NL, int G>
+static bool tf_opt_in() {
+    return hipFuncSetAttribute(reinterpret_cast<const void*>(topo_fused_kernel<NL, G>), hipFuncAttributeMaxDynamicSharedMemorySize, tf_lds(NL, G)) == hipSuccess;
 }
 
 int launch_topo_fused(const TopoFusedParams& p, hipStream_t s) {
     if (p.nseq <= 0) return 0;
     if (p.nlayers != 0 && p.nlayers != 3) return -2;
-    const int nprm = 128 + 1280 * p.nlayers + 132;
-    const int lds = TF_RING + nprm * 4;
+    if (p.K < 1 || p.K > 64) return -2;
     static OncePerDevice opt_in;
     if (!opt_in.run([] {
-            return hipFuncSetAttribute(reinterpret_cast<const void*>(topo_fused_kernel<3>), hipFuncAttributeMaxDynamicSharedMemorySize, TF_RING + (128 + 1280 * 3 + 132) * 4) == hipSuccess &&
-                   hipFuncSetAttribute(reinterpret_cast<const void*>(topo_fused_kernel<0>), hipFuncAttributeMaxDynamicSharedMemorySize, TF_RING + (128 + 132) * 4) == hipSuccess;
+            return tf_opt_in<3, 0>() && tf_opt_in<0, 0>() && tf_opt_in<3, 1>() && tf_opt_in<0, 1>() && tf_opt_in<3, 2>() && tf_opt_in<3, 3>() &&
+                   tf_opt_in<3, 4>();
         }))
         return -3;
-    const int groups = (p.nseq + TF_NW - 1) / TF_NW;
-    const int grid = groups < 256 ? groups : 256;
-    if (p.nlayers == 3) hipLaunchKernelGGL(topo_fused_kernel<3>, dim3(grid), dim3(TF_NW * 64), lds, s, p);
-    else hipLaunchKernelGGL(topo_fused_kernel<0>, dim3(grid), dim3(TF_NW * 64), lds, s, p);
-    return SRH_CHECK_LAUNCH();
+    if (p.K == 16) return p.nlayers == 3 ? tf_launch<3, 0>(p, s) : tf_launch<0, 0>(p, s);
+    if (p.nlayers == 0) return tf_launch<0, 1>(p, s);
+    if (p.K < 16) return tf_launch<3, 1>(p, s);
+    if (p.K <= 32) return tf_launch<3, 2>(p, s);
+    if (p.K <= 48) return tf_launch<3, 3>(p, s);
+    return tf_launch<3, 4>(p, s);
 }
 
 }  // namespace srh

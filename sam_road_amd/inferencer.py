@@ -552,8 +552,22 @@ def infer_one_img(net, img, config, device=None):
         return _infer_one_img(net, img, config, device)
 
 
+MAX_NEIGHBOR_QUERIES_RANGE = (1, 64)
+
+
+def neighbor_queries(config):
+    """config.MAX_NEIGHBOR_QUERIES (K: candidate edges per graph point, inferencer.py:160-166), checked against what the fused TopoNet
+    trunk supports.  Raises ValueError for anything but an int in 1..64 — before pass 1, not after a whole encoder pass."""
+    k = config.MAX_NEIGHBOR_QUERIES
+    lo, hi = MAX_NEIGHBOR_QUERIES_RANGE
+    if isinstance(k, (bool, np.bool_)) or not isinstance(k, (int, np.integer)) or not lo <= k <= hi:
+        raise ValueError(f"MAX_NEIGHBOR_QUERIES must be an int from {lo} to {hi}, got {k!r}")
+    return int(k)
+
+
 def _scene_plan(img, config):
     """Validated scene + its tile list (inferencer.py:63-76): (img u8 [S,S,3], infos, tile origins int32 [n,2] (x0, y0))."""
+    neighbor_queries(config)
     img = np.asarray(img)
     # the reference uses img.shape[0] for both axes (inferencer.py:63,67) and casts whatever it gets to f32; a non-square or
     # non-u8 scene would silently produce garbage here (row stride = S on the device), so it is refused instead
@@ -711,6 +725,7 @@ def infer_imgs(net, imgs, config, device=None, tile_sharded=None, pipelined=None
     key TILE_SHARD_PIPELINE, CLI `--shard tiles-pipelined`), which interleaves the band reduce of scene i+1 with the point broadcast
     and vote gather of scene i.  The pipelined loop has only ever run on gloo / CPU (no multi-GPU box was available to the builder:
     DESIGN.md §6), so it stays opt-in until an RCCL run exists; both give the same results (tests/test_distributed_cpu.py)."""
+    neighbor_queries(config)                          # fail before any scene touches the device
     if D.is_distributed() if tile_sharded is None else tile_sharded:
         if pipelined is None:
             pipelined = _cfg_switch(config.TILE_SHARD_PIPELINE, False)
@@ -723,7 +738,7 @@ def infer_imgs(net, imgs, config, device=None, tile_sharded=None, pipelined=None
     device = torch.device(device) if device is not None else next(net.parameters()).device
     lane = _Lane(device)
     pools = [_StagingPool(device), _StagingPool(device)]
-    bs, K = int(config.INFER_BATCH_SIZE), int(config.MAX_NEIGHBOR_QUERIES)
+    bs, K = int(config.INFER_BATCH_SIZE), neighbor_queries(config)
     import os
     import time
     prof = os.environ.get("SRH_PROFILE_HOST") == "1"      # tuning aid: host wall time of each step (no device synchronisation)
@@ -1040,6 +1055,7 @@ def main(argv=None):
                          "tiles-pipelined: the same with scene i+1's pass 1 queued before scene i's host stages (opt-in: exercised on gloo only)")
     args = ap.parse_args(argv)
     config = load_config(args.config)
+    neighbor_queries(config)                     # a K the TopoNet trunk cannot run fails here, not after the first scene's pass 1
     device = torch.device("cuda") if args.device == "cuda" else torch.device(args.device)
     torch.set_num_threads(max(1, min(torch.get_num_threads(), usable_cpus() // max(1, int(os.environ.get("WORLD_SIZE", "1"))))))   # this rank's share of the container's CPU quota (hostcpu.py)
     _numpy_hugepages(False)                      # for the whole run: image decoding and output encoding allocate beside the GPU too (_host_quiet)

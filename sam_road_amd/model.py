@@ -448,6 +448,7 @@ class SAMRoad(nn.Module):
 
     @torch.no_grad()
     def infer_toponet(self, image_embeddings, graph_points, pairs, valid):
+        """model.py:498-508: pairs [B,N,K,2], valid [B,N,K] for any K = MAX_NEIGHBOR_QUERIES from 1 to 64 (ABI 10) -> scores [B,N,K,1]."""
         return self._topo(image_embeddings, graph_points, pairs, valid, False)[1]
 
     @torch.no_grad()
@@ -457,8 +458,8 @@ class SAMRoad(nn.Module):
         buffer), points f32 [R,2] tile-local (x, y), point_tile i32 [R] (index into image_embeddings), pairs i32 [R,K,2] (rows of
         the flat list), valid u8 [R,K]  ->  scores f32 [R,K] (srh_toponet_ragged; rows as built by srh_pass2_pack_ragged).
         tile_offsets (host int64 [n + 1], rows of tile t = offsets[t] .. offsets[t+1], from 0 to R): the library then scores the scene in
-        chunks of whole tiles (<= 16 k rows each, same bits) so that its workspace does not grow with the scene; without them at most
-        65 536 rows per call.  Both rows of every pair must be rows of the same tile (ABI 9): a pair that is not makes check_finite()
+        chunks of whole tiles (<= 16 k x 16 pairs = rows x K each, same bits) so that its workspace does not grow with the scene; without
+        them at most 65 536 x 16 pairs per call.  K (MAX_NEIGHBOR_QUERIES) may be 1 to 64 (ABI 10).  Both rows of every pair must be rows of the same tile (ABI 9): a pair that is not makes check_finite()
         (or the next infer_* / scene_pass1 call) raise SrhError instead of the scores silently depending on the chunking."""
         dev = image_embeddings.device
         ctx, wh = self._weights(dev)
