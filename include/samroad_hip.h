@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define SRH_ABI_VERSION 10
+#define SRH_ABI_VERSION 11
 
 typedef enum {
     SRH_OK = 0,
@@ -153,6 +153,20 @@ int srh_scene_pass1(srh_ctx* ctx, const srh_weights* w, const uint8_t* scene, in
 int srh_scene_normalise(srh_ctx* ctx, const float* canvas_kp, const float* canvas_road, int S,
                         const int32_t* tile_xy, int n_tiles, int P, uint8_t* kp_u8, uint8_t* road_u8,
                         void* stream);
+
+/* ABI 11: rectangular scenes.  The same two calls for a scene u8 [H,W,3] (row pitch W pixels, no padding) with canvases f32 [H,W] and
+ * masks u8 [H,W]; H and W are independent, each >= PATCH_SIZE, and H * W <= 2^31 - 1 pixels (SRH_ERR_BAD_ARG otherwise).  Tiles stay
+ * PATCH_SIZE squares, and every tile is computed by the kernels that compute it for a square scene: srh_scene_pass1(S) and
+ * srh_scene_normalise(S) ARE the H = W = S case of this code.  tile_xy is a device array the host cannot read without a
+ * synchronisation, so it is a PRECONDITION (as it always was for the square calls) that every tile lies inside the scene:
+ * 0 <= x0 <= W - P and 0 <= y0 <= H - P.  The tile list may have any length (no n x n grid is assumed); pixels no tile covers
+ * keep their canvas value and come out of the normalise as 0. */
+int srh_scene_pass1_hw(srh_ctx* ctx, const srh_weights* w, const uint8_t* scene, int H, int W, const int32_t* tile_xy,
+                       int n_tiles, int B, float* canvas_kp, float* canvas_road, float* embeddings_all,
+                       void* stream);
+int srh_scene_normalise_hw(srh_ctx* ctx, const float* canvas_kp, const float* canvas_road, int H, int W,
+                           const int32_t* tile_xy, int n_tiles, int P, uint8_t* kp_u8, uint8_t* road_u8,
+                           void* stream);
 
 /* op level (used by the parity tests to localise a failure; same kernels as above) ----------------- */
 

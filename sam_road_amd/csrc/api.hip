@@ -1061,13 +1061,17 @@ extern "C" int srh_toponet_ragged(srh_ctx* c, const srh_weights* w, const float*
 }
 
 // ---- scene level ------------------------------------------------------------------------------------------
-extern "C" int srh_scene_pass1(srh_ctx* c, const srh_weights* w, const uint8_t* scene, int S, const int32_t* tile_xy,
-                               int n_tiles, int B, float* canvas_kp, float* canvas_road, float* embeddings_all,
-                               void* stream) {
+// A scene's pixel count must fit an int: the scene kernels index canvas pixels with one (byte offsets are 64-bit).
+static bool scene_dims_ok(int H, int W) { return H > 0 && W > 0 && (long long)H * W <= 2147483647LL; }
+
+static int scene_pass1_impl(srh_ctx* c, const char* who, const srh_weights* w, const uint8_t* scene, int H, int W,
+                            const int32_t* tile_xy, int n_tiles, int B, float* canvas_kp, float* canvas_road,
+                            float* embeddings_all, void* stream) {
     if (!c || !w || !scene || !tile_xy || !canvas_kp || !canvas_road || !embeddings_all)
-        return fail(c, SRH_ERR_BAD_ARG, "srh_scene_pass1: null argument");
-    if (n_tiles < 0 || B <= 0 || S < w->cfg.patch_size) return fail(c, SRH_ERR_BAD_ARG, "srh_scene_pass1: bad sizes");
-    TRY(nonfinite_check(c, "srh_scene_pass1"));
+        return fail(c, SRH_ERR_BAD_ARG, std::string(who) + ": null argument");
+    if (n_tiles < 0 || B <= 0 || H < w->cfg.patch_size || W < w->cfg.patch_size || !scene_dims_ok(H, W))
+        return fail(c, SRH_ERR_BAD_ARG, std::string(who) + ": bad sizes");
+    TRY(nonfinite_check(c, who));
     hipSetDevice(c->device);
     hipStream_t s = (hipStream_t)stream;
     const int P = w->cfg.patch_size;
@@ -1076,28 +1080,53 @@ extern "C" int srh_scene_pass1(srh_ctx* c, const srh_weights* w, const uint8_t* 
     for (int off = 0; off < n_tiles; off += B) {
         const int nb = std::min(B, n_tiles - off);
         PatchParams pp;
-        pp.src = scene; pp.src_is_u8 = 1; pp.scene_S = S; pp.tile_xy = tile_xy + 2 * off;
+        pp.src = scene; pp.src_is_u8 = 1; pp.scene_W = W; pp.tile_xy = tile_xy + 2 * off;
         TRY(encode_batch(c, w, pp, nb, nullptr, c->scores_ws.as<float>(), embeddings_all + emb_per_tile * off, s));
         TRYK(c, "scene_add", 0, (double)nb * P * P * 8 * 3, s,
-             launch_scene_add(c->scores_ws.as<float>(), nb, P, tile_xy + 2 * off, canvas_kp, canvas_road, S, s));
+             launch_scene_add(c->scores_ws.as<float>(), nb, P, tile_xy + 2 * off, canvas_kp, canvas_road, H, W, s));
     }
     return 0;
+}
+
+extern "C" int srh_scene_pass1_hw(srh_ctx* c, const srh_weights* w, const uint8_t* scene, int H, int W, const int32_t* tile_xy,
+                                  int n_tiles, int B, float* canvas_kp, float* canvas_road, float* embeddings_all,
+                                  void* stream) {
+    return scene_pass1_impl(c, "srh_scene_pass1_hw", w, scene, H, W, tile_xy, n_tiles, B, canvas_kp, canvas_road, embeddings_all, stream);
+}
+
+extern "C" int srh_scene_pass1(srh_ctx* c, const srh_weights* w, const uint8_t* scene, int S, const int32_t* tile_xy,
+                               int n_tiles, int B, float* canvas_kp, float* canvas_road, float* embeddings_all,
+                               void* stream) {
+    return scene_pass1_impl(c, "srh_scene_pass1", w, scene, S, S, tile_xy, n_tiles, B, canvas_kp, canvas_road, embeddings_all, stream);
+}
+
+static int scene_normalise_impl(srh_ctx* c, const char* who, const float* canvas_kp, const float* canvas_road, int H, int W,
+                                const int32_t* tile_xy, int n_tiles, int P, uint8_t* kp_u8, uint8_t* road_u8, void* stream) {
+    if (!c || !canvas_kp || !canvas_road || !tile_xy || !kp_u8 || !road_u8)
+        return fail(c, SRH_ERR_BAD_ARG, std::string(who) + ": null argument");
+    if (!scene_dims_ok(H, W) || n_tiles < 0 || P <= 0) return fail(c, SRH_ERR_BAD_ARG, std::string(who) + ": bad sizes");
+    hipSetDevice(c->device);
+    hipStream_t s = (hipStream_t)stream;
+    const size_t npx = (size_t)H * W;
+    if (c->counter.ensure(npx * 4)) return fail(c, SRH_ERR_HIP, "counter allocation failed");
+    TRYK(c, "scene_count", 0, (double)npx * 4, s, launch_scene_count(c->counter.as<float>(), H, W, tile_xy, n_tiles, P, s));
+    SceneNormParams np;
+    np.canvas_kp = canvas_kp; np.canvas_road = canvas_road; np.counter = c->counter.as<float>();
+    np.kp_u8 = kp_u8; np.road_u8 = road_u8; np.n = (int)npx;
+    TRYK(c, "scene_normalise", 0, (double)npx * 14, s, launch_scene_normalise(np, s));
+    return 0;
+}
+
+extern "C" int srh_scene_normalise_hw(srh_ctx* c, const float* canvas_kp, const float* canvas_road, int H, int W,
+                                      const int32_t* tile_xy, int n_tiles, int P, uint8_t* kp_u8, uint8_t* road_u8,
+                                      void* stream) {
+    return scene_normalise_impl(c, "srh_scene_normalise_hw", canvas_kp, canvas_road, H, W, tile_xy, n_tiles, P, kp_u8, road_u8, stream);
 }
 
 extern "C" int srh_scene_normalise(srh_ctx* c, const float* canvas_kp, const float* canvas_road, int S,
                                    const int32_t* tile_xy, int n_tiles, int P, uint8_t* kp_u8, uint8_t* road_u8,
                                    void* stream) {
-    if (!c || !canvas_kp || !canvas_road || !tile_xy || !kp_u8 || !road_u8)
-        return fail(c, SRH_ERR_BAD_ARG, "srh_scene_normalise: null argument");
-    hipSetDevice(c->device);
-    hipStream_t s = (hipStream_t)stream;
-    if (c->counter.ensure((size_t)S * S * 4)) return fail(c, SRH_ERR_HIP, "counter allocation failed");
-    TRYK(c, "scene_count", 0, (double)S * S * 4, s, launch_scene_count(c->counter.as<float>(), S, tile_xy, n_tiles, P, s));
-    SceneNormParams np;
-    np.canvas_kp = canvas_kp; np.canvas_road = canvas_road; np.counter = c->counter.as<float>();
-    np.kp_u8 = kp_u8; np.road_u8 = road_u8; np.n = S * S;
-    TRYK(c, "scene_normalise", 0, (double)S * S * 14, s, launch_scene_normalise(np, s));
-    return 0;
+    return scene_normalise_impl(c, "srh_scene_normalise", canvas_kp, canvas_road, S, S, tile_xy, n_tiles, P, kp_u8, road_u8, stream);
 }
 
 // ---- op level ------------------------------------------------------------------------------------------------

@@ -252,10 +252,10 @@ int launch_decode_fused(const DecodeFusedParams& p, hipStream_t s) {
 // One thread per canvas pixel walks the batch's tiles IN ORDER, so the f32 summation order is the
 // reference's sequential `canvas[y0:y1, x0:x1] += patch` order (deterministic; no atomics).
 __global__ __launch_bounds__(256) void scene_add_kernel(const float* scores, int B, int P, const int* tile_xy,
-                                                        float* kp, float* road, int S) {
+                                                        float* kp, float* road, int H, int W) {
     const long gid = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (gid >= (long)S * S) return;
-    const int x = gid % S, y = gid / S;
+    if (gid >= (long)H * W) return;
+    const int x = gid % W, y = gid / W;                    // canvas [H, W]: row pitch W
     float a = kp[gid], r = road[gid];
     bool touched = false;
     for (int t = 0; t < B; ++t) {
@@ -269,10 +269,10 @@ __global__ __launch_bounds__(256) void scene_add_kernel(const float* scores, int
     if (touched) { kp[gid] = a; road[gid] = r; }
 }
 
-__global__ __launch_bounds__(256) void scene_count_kernel(float* counter, int S, const int* tile_xy, int n, int P) {
+__global__ __launch_bounds__(256) void scene_count_kernel(float* counter, int H, int W, const int* tile_xy, int n, int P) {
     const long gid = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (gid >= (long)S * S) return;
-    const int x = gid % S, y = gid / S;
+    if (gid >= (long)H * W) return;
+    const int x = gid % W, y = gid / W;
     float c = 0.f;
     for (int t = 0; t < n; ++t) {
         const int lx = x - tile_xy[2 * t], ly = y - tile_xy[2 * t + 1];
@@ -291,14 +291,14 @@ __global__ __launch_bounds__(256) void scene_norm_kernel(SceneNormParams p) {
     p.road_u8[gid] = (c > 0.f) ? (uint8_t)r : (uint8_t)0;
 }
 
-int launch_scene_add(const float* scores, int B, int P, const int* tile_xy, float* kp, float* road, int S, hipStream_t s) {
-    const long n = (long)S * S;
-    hipLaunchKernelGGL(scene_add_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, scores, B, P, tile_xy, kp, road, S);
+int launch_scene_add(const float* scores, int B, int P, const int* tile_xy, float* kp, float* road, int H, int W, hipStream_t s) {
+    const long n = (long)H * W;
+    hipLaunchKernelGGL(scene_add_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, scores, B, P, tile_xy, kp, road, H, W);
     return hipGetLastError() == hipSuccess ? 0 : -3;
 }
-int launch_scene_count(float* counter, int S, const int* tile_xy, int n_tiles, int P, hipStream_t s) {
-    const long n = (long)S * S;
-    hipLaunchKernelGGL(scene_count_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, counter, S, tile_xy, n_tiles, P);
+int launch_scene_count(float* counter, int H, int W, const int* tile_xy, int n_tiles, int P, hipStream_t s) {
+    const long n = (long)H * W;
+    hipLaunchKernelGGL(scene_count_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, counter, H, W, tile_xy, n_tiles, P);
     return hipGetLastError() == hipSuccess ? 0 : -3;
 }
 int launch_scene_normalise(const SceneNormParams& p, hipStream_t s) {

@@ -24,9 +24,9 @@ __global__ __launch_bounds__(256) void patch_im2col_kernel(PatchParams p) {
     const int y = (int)((gid / Q) % p.P);
     const int b = (int)(gid / ((long)Q * p.P));
     long src_off;
-    if (p.scene_S > 0) {
+    if (p.scene_W > 0) {
         const int x0 = p.tile_xy[2 * b], y0 = p.tile_xy[2 * b + 1];
-        src_off = ((long)(y0 + y) * p.scene_S + x0) * 3 + 4 * q;
+        src_off = ((long)(y0 + y) * p.scene_W + x0) * 3 + 4 * q;    // row pitch = scene width; 64-bit from the first product on
     } else {
         src_off = ((long)b * p.P + y) * p.P * 3 + 4 * q;
     }

@@ -57,7 +57,8 @@ def broadcast_bytes(buf, src=0, device=None):
 
 def tile_bands(tile_xy, patch, world):
     """Column band [x_lo, x_hi) of the scene that each rank's tile chunk (tiling.shard_tiles) touches; (0, 0) for a rank without
-    tiles.  tile_xy: int array [n,2] of tile origins (x0, y0) in the reference's x-outer order."""
+    tiles.  tile_xy: int array [n,2] of tile origins (x0, y0) in the reference's x-outer order (n_x columns of n_y tiles each, n_x
+    and n_y independent: a contiguous chunk of that list is a run of whole or partial columns, i.e. a vertical band)."""
     from .tiling import shard_tiles
     bands = []
     for r in range(world):
@@ -71,9 +72,9 @@ def tile_bands(tile_xy, patch, world):
 
 
 def reduce_canvases(kp, road, dst=0, bands=None):
-    """In-place SUM of the two f32 scene canvases [S,S] onto `dst`.  With `bands` (tile_bands: every rank touched only the
-    columns [x_lo, x_hi) of its own tile chunk) each rank ships just that band — 2 x S x (x_hi - x_lo) floats instead of
-    2 x S x S: about 600 of 2048 columns per rank for the CityScale tiling on 8 GPUs — by point-to-point sends to `dst`, which
+    """In-place SUM of the two f32 scene canvases [H,W] onto `dst`.  With `bands` (tile_bands: every rank touched only the
+    columns [x_lo, x_hi) of its own tile chunk, over the full height) each rank ships just that band — 2 x H x (x_hi - x_lo)
+    floats instead of 2 x H x W: about 600 of 2048 columns per rank for the CityScale tiling on 8 GPUs — by point-to-point sends to `dst`, which
     adds the bands in rank order.  Without bands: one dense reduce.  Either way a pixel's addends are grouped per rank, so the
     last f32 bit may differ from the single-GPU order (the u8 truncation that follows is compared with +-1 level)."""
     if not is_distributed():
@@ -123,9 +124,9 @@ def reduce_canvases(kp, road, dst=0, bands=None):
 _CHECK_BANDS = [False]       # tests switch this on: every sender checks that its canvas is zero outside its band
 
 
-def canvas_bytes(bands, S, dst=0):
-    """Bytes the banded reduce moves to `dst` for one scene (two f32 canvases, S rows)."""
-    return sum(2 * 4 * S * max(0, x1 - x0) for r, (x0, x1) in enumerate(bands) if r != dst)
+def canvas_bytes(bands, H, dst=0):
+    """Bytes the banded reduce moves to `dst` for one scene (two f32 canvases of H rows; bands are column ranges)."""
+    return sum(2 * 4 * H * max(0, x1 - x0) for r, (x0, x1) in enumerate(bands) if r != dst)
 
 
 def broadcast_points(points, src=0, device=None):

@@ -13,6 +13,8 @@ With torch.distributed initialised (one process per GPU) the tile list is split 
 chunks per rank; canvases are summed on rank 0, points broadcast, edge votes gathered
 (sam_road_amd/distributed.py).  Only rank 0 returns the graph; other ranks return None.
 """
+import warnings
+
 import numpy as np
 import scipy.spatial
 import torch
@@ -20,7 +22,7 @@ import torch
 from . import distributed as D
 from .graph_points import extract_graph_points
 from .hostcpu import fill_threads, usable_cpus, worker_threads
-from .tiling import get_patch_info_one_img, shard_tiles
+from .tiling import get_patch_info_hw, get_patch_info_one_img, patches_per_axis, shard_tiles
 
 
 def build_patch_queries(graph_points, x0, y0, x1, y1, config):
@@ -566,27 +568,39 @@ def neighbor_queries(config):
 
 
 def _scene_plan(img, config):
-    """Validated scene + its tile list (inferencer.py:63-76): (img u8 [S,S,3], infos, tile origins int32 [n,2] (x0, y0))."""
+    """Validated scene + its tile list (inferencer.py:63-76): (img u8 [H,W,3], infos, tile origins int32 [n,2] (x0, y0)).
+    H and W are independent; the reference's tile rule is applied per axis (tiling.get_patch_info_hw), and
+    INFER_PATCHES_PER_EDGE may be an int or [n_y, n_x].  Everything that can be refused is refused here, before the device is
+    touched."""
     neighbor_queries(config)
     img = np.asarray(img)
-    # the reference uses img.shape[0] for both axes (inferencer.py:63,67) and casts whatever it gets to f32; a non-square or
-    # non-u8 scene would silently produce garbage here (row stride = S on the device), so it is refused instead
-    if img.ndim != 3 or img.shape[2] != 3 or img.shape[0] != img.shape[1] or img.dtype != np.uint8:
-        raise ValueError(f"infer_one_img expects a square HxWx3 uint8 scene, got {img.dtype} {tuple(img.shape)}")
-    image_size = img.shape[0]
-    if image_size < int(config.PATCH_SIZE) + 2 * int(config.SAMPLE_MARGIN or 0):
-        raise ValueError(f"scene {image_size} px is smaller than PATCH_SIZE + 2 * SAMPLE_MARGIN")
-    infos = get_patch_info_one_img(0, image_size, config.SAMPLE_MARGIN, config.PATCH_SIZE,
-                                   config.INFER_PATCHES_PER_EDGE)
+    # the reference uses img.shape[0] for both axes (inferencer.py:63,67) and casts whatever it gets to f32: it would mis-stride a
+    # non-square scene and silently convert a non-u8 one.  Here H and W are separate all the way down; non-u8 is refused
+    if img.ndim != 3 or img.shape[2] != 3 or img.dtype != np.uint8:
+        raise ValueError(f"infer_one_img expects an HxWx3 uint8 scene, got {img.dtype} {tuple(img.shape)}")
+    H, W = int(img.shape[0]), int(img.shape[1])
+    P, m = int(config.PATCH_SIZE), int(config.SAMPLE_MARGIN or 0)
+    for axis, size in (("height", H), ("width", W)):
+        if size < P + 2 * m:
+            raise ValueError(f"scene {axis} {size} px is smaller than PATCH_SIZE + 2 * SAMPLE_MARGIN = {P + 2 * m}")
+    if H * W > 2 ** 31 - 1:
+        raise ValueError(f"scene {H} x {W} has more than 2^31 - 1 pixels")
+    n_y, n_x = patches_per_axis(config.INFER_PATCHES_PER_EDGE)
+    for axis, size, n in (("height", H, n_y), ("width", W, n_x)):
+        span = size - P - 2 * m                        # first to last tile origin
+        if span > (n - 1) * P:                         # stride > PATCH_SIZE (one tile: any span at all)
+            need = -(-span // P) + 1
+            warnings.warn(f"INFER_PATCHES_PER_EDGE = {n} along the {axis} ({size} px) leaves pixels between the {P}-px tiles that no "
+                          f"tile covers (they come out as 0); {need} tiles close the gap", stacklevel=2)
+    infos = get_patch_info_hw(0, H, W, config.SAMPLE_MARGIN, config.PATCH_SIZE, (n_y, n_x))
     all_xy = np.array([[p[1][0], p[1][1]] for p in infos], dtype=np.int32)
-    assert all_xy.min() >= 0 and all_xy.max() + int(config.PATCH_SIZE) <= image_size
+    assert all_xy.min() >= 0 and all_xy[:, 0].max() + P <= W and all_xy[:, 1].max() + P <= H
     return img, infos, all_xy
 
 
 def _infer_one_img(net, img, config, device=None):
     device = torch.device(device) if device is not None else next(net.parameters()).device
     img, infos, all_xy = _scene_plan(img, config)
-    image_size = img.shape[0]
     bs = int(config.INFER_BATCH_SIZE)
     world = torch.distributed.get_world_size() if D.is_distributed() else 1
     rank = torch.distributed.get_rank() if D.is_distributed() else 0
@@ -900,7 +914,8 @@ def _infer_imgs_tile_sharded(net, imgs, config, device=None, stats=None):
         if bands is not None:
             # this rank's own share: the band it ships to rank 0 (rank 0: what it receives), so that per-rank statistics are per rank
             x0, x1 = bands[rank]
-            stats["canvas_bytes"] += D.canvas_bytes(bands, job.img.shape[0]) if rank == 0 else 2 * 4 * job.img.shape[0] * max(0, x1 - x0)
+            rows = job.img.shape[0]                    # a band is a strip of columns of the full scene HEIGHT
+            stats["canvas_bytes"] += D.canvas_bytes(bands, rows) if rank == 0 else 2 * 4 * rows * max(0, x1 - x0)
         job.masks = job.e1 = None
         if rank == 0:
             kp_u8, road_u8 = net.scene_normalise(kp_c, road_c, job.xy_dev)

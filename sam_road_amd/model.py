@@ -500,41 +500,45 @@ class SAMRoad(nn.Module):
     # ---- scene level (pass 1 of infer_one_img: tile batcher + model + mask fusion) -------------------------
     @torch.no_grad()
     def scene_pass1(self, scene_u8, tile_xy, batch_size, canvas_kp=None, canvas_road=None):
-        """scene_u8 [S,S,3] uint8 on the GPU, tile_xy int32 [n,2] (x0,y0) on the GPU.  Runs the tiles in
-        batches through the encoder + decoder and accumulates the two mask canvases in the reference's
-        sequential order (inferencer.py:87-104).  Returns (canvas_kp, canvas_road, embeddings[n,256,h,w])."""
+        """scene_u8 [H,W,3] uint8 on the GPU (H and W independent, each >= PATCH_SIZE), tile_xy int32 [n,2] (x0,y0) on the
+        GPU, every tile inside the scene.  Runs the tiles in batches through the encoder + decoder and accumulates the two
+        mask canvases [H,W] in the reference's sequential order (inferencer.py:87-104).  Returns (canvas_kp, canvas_road,
+        embeddings[n,256,h,w])."""
         dev = scene_u8.device
         ctx, wh = self._weights(dev)
         assert scene_u8.dtype == torch.uint8 and scene_u8.dim() == 3 and scene_u8.shape[2] == 3
         scene_u8 = scene_u8.contiguous()
         tile_xy = tile_xy.to(device=dev, dtype=torch.int32).contiguous()
-        S, n, h = scene_u8.shape[0], tile_xy.shape[0], self.image_size // 16
-        if scene_u8.shape[1] != S:
-            raise ValueError(f"scene must be square, got {tuple(scene_u8.shape)}")
+        H, W = int(scene_u8.shape[0]), int(scene_u8.shape[1])
+        n, h = tile_xy.shape[0], self.image_size // 16
+        if H < self.image_size or W < self.image_size:
+            raise ValueError(f"scene {H} x {W} is smaller than a {self.image_size}-px tile")
         if canvas_kp is None:
-            canvas_kp = torch.zeros((S, S), dtype=torch.float32, device=dev)
-            canvas_road = torch.zeros((S, S), dtype=torch.float32, device=dev)
+            canvas_kp = torch.zeros((H, W), dtype=torch.float32, device=dev)
+            canvas_road = torch.zeros((H, W), dtype=torch.float32, device=dev)
+        elif tuple(canvas_kp.shape) != (H, W) or tuple(canvas_road.shape) != (H, W):
+            raise ValueError(f"canvases must be [{H}, {W}] like the scene, got {tuple(canvas_kp.shape)} / {tuple(canvas_road.shape)}")
         emb = torch.empty((n, h, h, 256), dtype=torch.float32, device=dev)
         if n == 0:                                   # a rank without tiles (world_size > tile count): nothing to add
             return canvas_kp, canvas_road, emb.permute(0, 3, 1, 2)
         with torch.cuda.device(dev):
-            ctx.check(ctx.lib.srh_scene_pass1(ctx.handle, wh, scene_u8.data_ptr(), S, tile_xy.data_ptr(), n,
-                                              int(batch_size), canvas_kp.data_ptr(), canvas_road.data_ptr(),
-                                              emb.data_ptr(), self._stream(dev)), "srh_scene_pass1")
+            ctx.check(ctx.lib.srh_scene_pass1_hw(ctx.handle, wh, scene_u8.data_ptr(), H, W, tile_xy.data_ptr(), n,
+                                                 int(batch_size), canvas_kp.data_ptr(), canvas_road.data_ptr(),
+                                                 emb.data_ptr(), self._stream(dev)), "srh_scene_pass1_hw")
         return canvas_kp, canvas_road, emb.permute(0, 3, 1, 2)
 
     @torch.no_grad()
     def scene_normalise(self, canvas_kp, canvas_road, tile_xy):
-        """(canvas / coverage count) * 255 -> uint8 masks (inferencer.py:106-110); tile_xy = ALL tiles."""
+        """(canvas / coverage count) * 255 -> uint8 masks [H,W] (inferencer.py:106-110); tile_xy = ALL tiles."""
         dev = canvas_kp.device
         ctx, _ = self._weights(dev)
-        S = canvas_kp.shape[0]
+        H, W = int(canvas_kp.shape[0]), int(canvas_kp.shape[1])
         tile_xy = tile_xy.to(device=dev, dtype=torch.int32).contiguous()
-        kp = torch.empty((S, S), dtype=torch.uint8, device=dev)
-        road = torch.empty((S, S), dtype=torch.uint8, device=dev)
+        kp = torch.empty((H, W), dtype=torch.uint8, device=dev)
+        road = torch.empty((H, W), dtype=torch.uint8, device=dev)
         with torch.cuda.device(dev):
-            ctx.check(ctx.lib.srh_scene_normalise(ctx.handle, canvas_kp.data_ptr(), canvas_road.data_ptr(), S,
-                                                  tile_xy.data_ptr(), tile_xy.shape[0], self.image_size,
-                                                  kp.data_ptr(), road.data_ptr(), self._stream(dev)),
-                      "srh_scene_normalise")
+            ctx.check(ctx.lib.srh_scene_normalise_hw(ctx.handle, canvas_kp.data_ptr(), canvas_road.data_ptr(), H, W,
+                                                     tile_xy.data_ptr(), tile_xy.shape[0], self.image_size,
+                                                     kp.data_ptr(), road.data_ptr(), self._stream(dev)),
+                      "srh_scene_normalise_hw")
         return kp, road

@@ -7,6 +7,8 @@ scenes through infer_imgs (the CLI's loop: scene i's host stages overlap scene i
 The final map_decoder bias is lowered so that the random network yields sparse masks (a few thousand graph points, as a trained one does).
 
     python tools/scene_bench.py [--bias -2.2] [--wscale 16] [--batch 64] [--iters 3]
+    python tools/scene_bench.py --scene 2048 4096 --tiles 16 32     # a rectangular scene H W (or 2048x4096) with [n_y, n_x] tiles;
+                                                                    # --scene 4096 --tiles 32 = the square a user had to pad it to
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 tools/scene_bench.py    # N GPUs:
         tiles sharded over the ranks (RCCL: packed-weight broadcast, banded canvas reduce, point broadcast, vote gather);
         rank 0 prints ms/scene (max over ranks) and the per-rank stage times
@@ -23,16 +25,32 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 
+def parse_scene(words):
+    """['2048'] -> (2048, 2048); ['2048', '4096'] or ['2048x4096'] -> (2048, 4096): height first, as in img.shape."""
+    parts = [p for w in words for p in str(w).lower().split("x")]
+    if len(parts) not in (1, 2) or not all(p.isdigit() and int(p) > 0 for p in parts):
+        raise SystemExit(f"--scene takes S, H W or HxW, got {words}")
+    return int(parts[0]), int(parts[-1])
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--bias", type=float, default=-2.2)
     ap.add_argument("--batch", type=int, default=64)
     ap.add_argument("--iters", type=int, default=3)
     ap.add_argument("--wscale", type=float, default=16.0)   # spread of the final layer: with 16 the random net yields ~4k graph points
+    ap.add_argument("--scene", nargs="+", default=["2048"], metavar="PX", help="scene size: S (square), H W or HxW; multiples of 8")
+    ap.add_argument("--tiles", nargs="+", type=int, default=[16], metavar="N", help="INFER_PATCHES_PER_EDGE: N or N_Y N_X")
+    ap.add_argument("--no-pipelined", action="store_true", help="skip the infer_imgs runs (12- and 48-scene streams)")
     args = ap.parse_args()
+    H, W = parse_scene(args.scene)
+    if len(args.tiles) not in (1, 2) or H % 8 or W % 8:
+        ap.error("--tiles takes one or two counts; the synthetic scene is made of 8-px blocks")
+    per_edge = args.tiles[0] if len(args.tiles) == 1 else list(args.tiles)
     from sam_road_amd import Config, SAMRoad
     from sam_road_amd.inferencer import infer_one_img
-    from sam_road_amd.tiling import get_patch_info_one_img, shard_tiles
+    from sam_road_amd.inferencer import _scene_plan
+    from sam_road_amd.tiling import shard_tiles
     rank, local_rank, world = (int(os.environ.get(k, d)) for k, d in (("RANK", "0"), ("LOCAL_RANK", "0"), ("WORLD_SIZE", "1")))
     if world > 1:
         import torch.distributed as dist
@@ -44,7 +62,7 @@ def main():
     from sam_road_amd.hostcpu import usable_cpus
     torch.set_num_threads(max(1, min(torch.get_num_threads(), usable_cpus() // world)))      # as the CLI does: respect the container's CPU quota
     cfg = Config(SAM_VERSION="vit_b", PATCH_SIZE=512, TOPONET_VERSION="normal", SAM_CKPT_PATH="", DATASET="cityscale",
-                 INFER_BATCH_SIZE=args.batch, SAMPLE_MARGIN=64, INFER_PATCHES_PER_EDGE=16, ITSC_THRESHOLD=0.248,
+                 INFER_BATCH_SIZE=args.batch, SAMPLE_MARGIN=64, INFER_PATCHES_PER_EDGE=per_edge, ITSC_THRESHOLD=0.248,
                  ROAD_THRESHOLD=0.364, TOPO_THRESHOLD=0.499, ITSC_NMS_RADIUS=8, ROAD_NMS_RADIUS=16, NEIGHBOR_RADIUS=64,
                  MAX_NEIGHBOR_QUERIES=16)
     net = SAMRoad(cfg)
@@ -65,11 +83,11 @@ def main():
     torch.cuda.synchronize()
     t_w = time.perf_counter() - t_w
     rng = np.random.default_rng(0)
-    coarse = rng.integers(0, 256, size=(2048 // 8, 2048 // 8, 3)).astype(np.float32)
+    coarse = rng.integers(0, 256, size=(H // 8, W // 8, 3)).astype(np.float32)
     img = np.kron(coarse, np.ones((8, 8, 1), np.float32)).astype(np.uint8)
 
-    infos = get_patch_info_one_img(0, 2048, cfg.SAMPLE_MARGIN, cfg.PATCH_SIZE, cfg.INFER_PATCHES_PER_EDGE)
-    xy = torch.as_tensor(np.array([[p[1][0], p[1][1]] for p in infos], dtype=np.int32)).to(dev)
+    img, infos, all_xy = _scene_plan(img, cfg)         # the product's own validation and tile list
+    xy = torch.as_tensor(all_xy).to(dev)
     scene = torch.as_tensor(img).to(dev)
     lo, hi = shard_tiles(len(infos), world, rank)
 
@@ -110,7 +128,7 @@ def main():
     # the median of the runs is reported next to every run)
     piped, piped_runs, same, piped48 = None, None, None, None
     inf.extract_graph_points, inf.edge_votes = plain            # the timing wrappers synchronise the device
-    if world == 1:
+    if world == 1 and not args.no_pipelined:
         n, piped_runs, same = 12, [], True
         list(inf.infer_imgs(net, (img for _ in range(3)), cfg))
         for _ in range(max(args.iters, 3)):                     # several runs: the rate varies in phases of a second or two
@@ -144,10 +162,10 @@ def main():
             dist.destroy_process_group()
         return
     nodes, edges, kp, road = res
-    print(json.dumps({"scene": "synthetic 2048x2048 u8, 256 tiles of 512^2 (16x16, margin 64)", "n_gpus": world,
+    print(json.dumps({"scene": f"synthetic {H}x{W} u8, {len(infos)} tiles of 512^2 ({per_edge} per edge, margin 64)", "n_gpus": world,
                       "ms_weight_share": round(1e3 * t_w, 2) if world > 1 else None, "per_rank": per_rank,
                       "infer_batch_size": args.batch, "ms_per_scene_pass1": round(1e3 * p1, 2),
-                      "tiles_per_s_pass1": round(256 / p1, 1), "ms_per_scene_full": round(1e3 * full, 2),
+                      "tiles_per_s_pass1": round(len(infos) / p1, 1), "ms_per_scene_full": round(1e3 * full, 2),
                       "ms_per_scene_pipelined": None if piped is None else round(1e3 * piped, 2), "pipelined_runs_of_12_scenes": piped_runs,
                       "ms_per_scene_pipelined_run_of_48": None if piped48 is None else round(1e3 * piped48, 2),
                       "pipelined_equals_serial": same,
