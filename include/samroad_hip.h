@@ -168,6 +168,26 @@ int srh_scene_normalise_hw(srh_ctx* ctx, const float* canvas_kp, const float* ca
                            const int32_t* tile_xy, int n_tiles, int P, uint8_t* kp_u8, uint8_t* road_u8,
                            void* stream);
 
+/* Scenes with a per-pixel validity mask (nodata).  Three additive entries; the ABI number stays 11 because nothing existing changes.
+ * valid = device u8 [H,W], row pitch W, non-zero = valid pixel.  A scene without a mask calls none of them.
+ *
+ * srh_scene_tile_valid: counts[t] = number of valid pixels inside the PxP tile at tile_xy[t] = (x0, y0) (device int32 [n_tiles]; exact,
+ *   one workgroup per tile, no atomics).  P must be a multiple of 16, at least 32 (every PATCH_SIZE is); H, W >= P and H * W <= 2^31 - 1, else
+ *   SRH_ERR_BAD_ARG.  Every tile must lie inside the scene, as for srh_scene_pass1_hw; a tile that does not is not read and counts -1.
+ *   The call touches no workspace of the context, so it may be issued on another stream than the context's compute stream.
+ * srh_scene_fill_invalid: scene[y][x] = (fill_r, fill_g, fill_b) wherever valid[y][x] == 0, in place on the device u8 [H,W,3] scene;
+ *   valid pixels keep their values (a group of four pixels that holds an invalid one is stored back whole, so the scene must not be read
+ *   by other work while the call runs).  fill_* outside 0..255 and H * W > 2^31 - 1 are SRH_ERR_BAD_ARG; no tile size enters this call.
+ * srh_scene_normalise_valid_hw: srh_scene_normalise_hw whose masks are also 0 on every invalid pixel; for valid pixels the same
+ *   arithmetic, so an all-valid mask gives the bytes of srh_scene_normalise_hw. */
+int srh_scene_tile_valid(srh_ctx* ctx, const uint8_t* valid, int H, int W, const int32_t* tile_xy, int n_tiles, int P,
+                         int32_t* counts, void* stream);
+int srh_scene_fill_invalid(srh_ctx* ctx, uint8_t* scene, const uint8_t* valid, int H, int W, int fill_r, int fill_g,
+                           int fill_b, void* stream);
+int srh_scene_normalise_valid_hw(srh_ctx* ctx, const float* canvas_kp, const float* canvas_road, int H, int W,
+                                 const int32_t* tile_xy, int n_tiles, int P, const uint8_t* valid, uint8_t* kp_u8,
+                                 uint8_t* road_u8, void* stream);
+
 /* op level (used by the parity tests to localise a failure; same kernels as above) ----------------- */
 
 /* out = act(A[M,K] W[N,K]^T + bias) (+resid); A,W fp16; N%128==0, K%64==0. act: 0/1 GELU/2 ReLU. */

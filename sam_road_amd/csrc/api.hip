@@ -1100,9 +1100,11 @@ extern "C" int srh_scene_pass1(srh_ctx* c, const srh_weights* w, const uint8_t* 
     return scene_pass1_impl(c, "srh_scene_pass1", w, scene, S, S, tile_xy, n_tiles, B, canvas_kp, canvas_road, embeddings_all, stream);
 }
 
+// valid (has_valid): the masks are also 0 on nodata — only the LAST launch differs; without it the two launches of every earlier ABI
 static int scene_normalise_impl(srh_ctx* c, const char* who, const float* canvas_kp, const float* canvas_road, int H, int W,
-                                const int32_t* tile_xy, int n_tiles, int P, uint8_t* kp_u8, uint8_t* road_u8, void* stream) {
-    if (!c || !canvas_kp || !canvas_road || !tile_xy || !kp_u8 || !road_u8)
+                                const int32_t* tile_xy, int n_tiles, int P, uint8_t* kp_u8, uint8_t* road_u8, void* stream,
+                                bool has_valid = false, const uint8_t* valid = nullptr) {
+    if (!c || !canvas_kp || !canvas_road || !tile_xy || !kp_u8 || !road_u8 || (has_valid && !valid))
         return fail(c, SRH_ERR_BAD_ARG, std::string(who) + ": null argument");
     if (!scene_dims_ok(H, W) || n_tiles < 0 || P <= 0) return fail(c, SRH_ERR_BAD_ARG, std::string(who) + ": bad sizes");
     hipSetDevice(c->device);
@@ -1113,7 +1115,8 @@ static int scene_normalise_impl(srh_ctx* c, const char* who, const float* canvas
     SceneNormParams np;
     np.canvas_kp = canvas_kp; np.canvas_road = canvas_road; np.counter = c->counter.as<float>();
     np.kp_u8 = kp_u8; np.road_u8 = road_u8; np.n = (int)npx;
-    TRYK(c, "scene_normalise", 0, (double)npx * 14, s, launch_scene_normalise(np, s));
+    if (has_valid) TRYK(c, "scene_norm_valid", 0, (double)npx * 15, s, launch_scene_normalise_valid(np, valid, s));
+    else TRYK(c, "scene_normalise", 0, (double)npx * 14, s, launch_scene_normalise(np, s));
     return 0;
 }
 
@@ -1127,6 +1130,36 @@ extern "C" int srh_scene_normalise(srh_ctx* c, const float* canvas_kp, const flo
                                    const int32_t* tile_xy, int n_tiles, int P, uint8_t* kp_u8, uint8_t* road_u8,
                                    void* stream) {
     return scene_normalise_impl(c, "srh_scene_normalise", canvas_kp, canvas_road, S, S, tile_xy, n_tiles, P, kp_u8, road_u8, stream);
+}
+
+// ---- scene level, validity mask (kernels in scene_valid.hip) -------------------------------------------------------------------
+extern "C" int srh_scene_tile_valid(srh_ctx* c, const uint8_t* valid, int H, int W, const int32_t* tile_xy, int n_tiles, int P,
+                                    int32_t* counts, void* stream) {
+    if (!c || !valid || !tile_xy || !counts) return fail(c, SRH_ERR_BAD_ARG, "srh_scene_tile_valid: null argument");
+    if (n_tiles < 0 || P < 32 || (P & 15) || H < P || W < P || !scene_dims_ok(H, W))
+        return fail(c, SRH_ERR_BAD_ARG, "srh_scene_tile_valid: bad sizes");
+    if (n_tiles == 0) return 0;
+    hipSetDevice(c->device);
+    hipStream_t s = (hipStream_t)stream;
+    TRYK(c, "tile_valid_count", 0, (double)n_tiles * P * P, s, launch_tile_valid_count(valid, H, W, tile_xy, n_tiles, P, counts, s));
+    return 0;
+}
+
+extern "C" int srh_scene_fill_invalid(srh_ctx* c, uint8_t* scene, const uint8_t* valid, int H, int W, int fill_r, int fill_g,
+                                      int fill_b, void* stream) {
+    if (!c || !scene || !valid) return fail(c, SRH_ERR_BAD_ARG, "srh_scene_fill_invalid: null argument");
+    if (!scene_dims_ok(H, W) || ((fill_r | fill_g | fill_b) & ~255)) return fail(c, SRH_ERR_BAD_ARG, "srh_scene_fill_invalid: bad sizes or fill colour");
+    hipSetDevice(c->device);
+    hipStream_t s = (hipStream_t)stream;
+    TRYK(c, "scene_fill_invalid", 0, (double)H * W, s, launch_scene_fill_invalid(scene, valid, H, W, fill_r, fill_g, fill_b, s));
+    return 0;
+}
+
+extern "C" int srh_scene_normalise_valid_hw(srh_ctx* c, const float* canvas_kp, const float* canvas_road, int H, int W,
+                                            const int32_t* tile_xy, int n_tiles, int P, const uint8_t* valid, uint8_t* kp_u8,
+                                            uint8_t* road_u8, void* stream) {
+    return scene_normalise_impl(c, "srh_scene_normalise_valid_hw", canvas_kp, canvas_road, H, W, tile_xy, n_tiles, P, kp_u8, road_u8, stream,
+                                true, valid);
 }
 
 // ---- op level ------------------------------------------------------------------------------------------------

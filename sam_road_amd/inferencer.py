@@ -547,11 +547,14 @@ def _host_quiet():
     return cm()
 
 
-def infer_one_img(net, img, config, device=None):
+def infer_one_img(net, img, config, device=None, valid=None):
     """reference inferencer.py:61-234: (pred_nodes (row, col), pred_edges, keypoint_mask u8, road_mask u8) of one scene (with the
-    garbage collector and numpy's huge-page madvise paused for the duration of the call, see _host_quiet)."""
+    garbage collector and numpy's huge-page madvise paused for the duration of the call, see _host_quiet).
+    valid (extension; bool or uint8 [H,W], non-zero = valid pixel; None = every pixel): only tiles that hold enough valid pixels are
+    run (config.MIN_VALID_FRACTION), nodata pixels are replaced by config.NODATA_FILL on the device copy of the scene, and both masks
+    are 0 on nodata, so no graph point lies there.  An all-true mask gives the result of valid=None bit for bit."""
     with _host_quiet():
-        return _infer_one_img(net, img, config, device)
+        return _infer_one_img(net, img, config, device, valid)
 
 
 MAX_NEIGHBOR_QUERIES_RANGE = (1, 64)
@@ -578,7 +581,13 @@ def _scene_plan(img, config):
     # non-square scene and silently convert a non-u8 one.  Here H and W are separate all the way down; non-u8 is refused
     if img.ndim != 3 or img.shape[2] != 3 or img.dtype != np.uint8:
         raise ValueError(f"infer_one_img expects an HxWx3 uint8 scene, got {img.dtype} {tuple(img.shape)}")
-    H, W = int(img.shape[0]), int(img.shape[1])
+    infos, all_xy = _tile_plan(int(img.shape[0]), int(img.shape[1]), config)
+    return img, infos, all_xy
+
+
+def _tile_plan(H, W, config, stacklevel=3):
+    """The candidate tiles of an H x W scene: (infos, tile origins int32 [n,2] (x0, y0)), or ValueError.  A stride warning is attributed to
+    the caller of this function's caller (stacklevel): whoever called _scene_plan or scene_tiles."""
     P, m = int(config.PATCH_SIZE), int(config.SAMPLE_MARGIN or 0)
     for axis, size in (("height", H), ("width", W)):
         if size < P + 2 * m:
@@ -591,20 +600,90 @@ def _scene_plan(img, config):
         if span > (n - 1) * P:                         # stride > PATCH_SIZE (one tile: any span at all)
             need = -(-span // P) + 1
             warnings.warn(f"INFER_PATCHES_PER_EDGE = {n} along the {axis} ({size} px) leaves pixels between the {P}-px tiles that no "
-                          f"tile covers (they come out as 0); {need} tiles close the gap", stacklevel=2)
+                          f"tile covers (they come out as 0); {need} tiles close the gap", stacklevel=stacklevel)
     infos = get_patch_info_hw(0, H, W, config.SAMPLE_MARGIN, config.PATCH_SIZE, (n_y, n_x))
     all_xy = np.array([[p[1][0], p[1][1]] for p in infos], dtype=np.int32)
     assert all_xy.min() >= 0 and all_xy[:, 0].max() + P <= W and all_xy[:, 1].max() + P <= H
-    return img, infos, all_xy
+    return infos, all_xy
 
 
-def _infer_one_img(net, img, config, device=None):
+# ---- scenes with a per-pixel validity mask (nodata) ---------------------------------------------------------------------------------
+NODATA_FILL_DEFAULT = (124, 116, 104)     # the pixel mean (123.675, 116.28, 103.53) rounded: ~0 after normalisation
+
+
+def _absent(v):
+    """A config key that is not there: None, or the empty node a Config returns for a missing key."""
+    return v is None or (isinstance(v, dict) and not v)
+
+
+def _is_int(v):
+    return isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_))
+
+
+def _valid_plan(valid, shape_hw, config):
+    """Validated mask arguments, before the device is touched: (valid u8 [H,W] C-contiguous (a bool mask reinterpreted, not copied),
+    MIN_VALID_FRACTION as a float in [0, 1] (missing key: 0), NODATA_FILL as three ints 0..255 (missing key: the rounded pixel
+    mean)).  ValueError for a mask of another shape or dtype and for keys outside their range."""
+    valid = np.asarray(valid)
+    if valid.dtype not in (np.dtype(bool), np.dtype(np.uint8)):
+        raise ValueError(f"valid must be a bool or uint8 mask, got dtype {valid.dtype}")
+    if tuple(valid.shape) != tuple(shape_hw):
+        raise ValueError(f"valid must have the scene's shape {tuple(shape_hw)}, got {tuple(valid.shape)}")
+    frac = 0.0 if _absent(config.MIN_VALID_FRACTION) else config.MIN_VALID_FRACTION
+    if not (_is_int(frac) or isinstance(frac, (float, np.floating))) or not 0.0 <= float(frac) <= 1.0:        # NaN fails the range
+        raise ValueError(f"MIN_VALID_FRACTION must be a number in [0, 1], got {frac!r}")
+    fill = NODATA_FILL_DEFAULT if _absent(config.NODATA_FILL) else config.NODATA_FILL
+    if not isinstance(fill, (list, tuple, np.ndarray)) or len(fill) != 3 or not all(_is_int(v) and 0 <= v <= 255 for v in fill):
+        raise ValueError(f"NODATA_FILL must be three ints in 0..255, got {fill!r}")
+    return np.ascontiguousarray(valid).view(np.uint8), float(frac), tuple(int(v) for v in fill)
+
+
+def select_tiles(counts, patch_size, min_valid_fraction):
+    """Indices (ascending: the kept tiles keep their relative order) of the tiles to run, from their valid-pixel counts: a tile is
+    kept iff count > 0 and count >= MIN_VALID_FRACTION * PATCH_SIZE^2."""
+    counts = np.asarray(counts, dtype=np.int64)
+    if (counts < 0).any():
+        raise ValueError("a tile lies outside the scene")
+    return np.flatnonzero((counts > 0) & (counts >= float(min_valid_fraction) * int(patch_size) * int(patch_size)))
+
+
+def _tile_counts(net, valid_d, xy_dev):
+    """Valid pixels per candidate tile on the host (int32 [n]): the model's count kernel + n int32 back + one wait."""
+    return net.scene_tile_valid(valid_d, xy_dev).cpu().numpy()
+
+
+def scene_tiles(shape, config, valid=None, net=None):
+    """The tiles infer_one_img runs for a scene of `shape` = (H, W[, 3]): the list of (0, (x0, y0), (x1, y1)) in the reference's
+    x-outer / y-inner order.  With `valid` (see infer_one_img) only the kept tiles, selected exactly as infer_one_img selects them: the
+    counts come from `net.scene_tile_valid` on the model's device, so `net` is required then (there is no host fallback)."""
+    neighbor_queries(config)
+    if len(shape) not in (2, 3) or (len(shape) == 3 and shape[2] != 3):
+        raise ValueError(f"shape must be (H, W) or (H, W, 3), got {tuple(shape)}")
+    H, W = int(shape[0]), int(shape[1])
+    infos, all_xy = _tile_plan(H, W, config)
+    if valid is None:
+        return infos
+    v8, frac, _ = _valid_plan(valid, (H, W), config)
+    if net is None:
+        raise ValueError("scene_tiles needs the model (net=) to count valid pixels on the device")
+    device = next(net.parameters()).device
+    counts = _tile_counts(net, torch.from_numpy(v8).to(device), torch.as_tensor(all_xy).to(device))
+    return [infos[i] for i in select_tiles(counts, config.PATCH_SIZE, frac)]
+
+
+def _empty_result(H, W):
+    """What a scene without a kept tile returns: no nodes, no edges, zero masks."""
+    return np.zeros((0, 2), dtype=np.int64), np.zeros((0, 2), dtype=np.int32), np.zeros((H, W), np.uint8), np.zeros((H, W), np.uint8)
+
+
+def _infer_one_img(net, img, config, device=None, valid=None):
     device = torch.device(device) if device is not None else next(net.parameters()).device
     img, infos, all_xy = _scene_plan(img, config)
+    if valid is not None:
+        valid, min_frac, fill = _valid_plan(valid, img.shape[:2], config)
     bs = int(config.INFER_BATCH_SIZE)
     world = torch.distributed.get_world_size() if D.is_distributed() else 1
     rank = torch.distributed.get_rank() if D.is_distributed() else 0
-    lo, hi = shard_tiles(len(infos), world, rank)
 
     import os
     import time
@@ -620,13 +699,30 @@ def _infer_one_img(net, img, config, device=None):
     scene = torch.as_tensor(np.ascontiguousarray(img), dtype=torch.uint8).to(device)
     xy_dev = torch.as_tensor(all_xy).to(device)
     lap("scene upload")
+    valid_d = None
+    if valid is not None:
+        # every rank holds the scene and the mask, computes the same integer counts and therefore the same kept list: from here
+        # on infos / all_xy / xy_dev ARE the kept tiles (a subsequence of an x-outer list is x-outer, so the banded reduce stays valid)
+        valid_d = torch.from_numpy(valid).to(device)
+        kept = select_tiles(_tile_counts(net, valid_d, xy_dev), config.PATCH_SIZE, min_frac)
+        lap("tile selection (count kernel + counts D2H)")
+        if len(kept) == 0:                             # nothing to run: the encoder is not launched
+            return _empty_result(*img.shape[:2]) if rank == 0 else None
+        infos, all_xy = [infos[i] for i in kept], np.ascontiguousarray(all_xy[kept])
+        xy_dev = torch.as_tensor(all_xy).to(device)
+        if scene.device.type != "cuda":                # a CPU tensor (the stand-in models of the gloo tests) shares the caller's memory
+            scene = scene.clone()
+        scene = net.scene_fill_invalid(scene, valid_d, fill)
+        lap("nodata fill")
+    lo, hi = shard_tiles(len(infos), world, rank)
     kp_c, road_c, emb = net.scene_pass1(scene, xy_dev[lo:hi], bs)      # an empty shard (world > n_tiles) returns zero canvases
     lap("pass 1 (GPU)")
     D.reduce_canvases(kp_c, road_c, dst=0, bands=D.tile_bands(all_xy, int(config.PATCH_SIZE), world) if world > 1 else None)
     graph_points = None
     kp_mask = road_mask = None
     if rank == 0:
-        kp_u8, road_u8 = net.scene_normalise(kp_c, road_c, xy_dev)
+        kp_u8, road_u8 = net.scene_normalise(kp_c, road_c, xy_dev) if valid_d is None else \
+            net.scene_normalise(kp_c, road_c, xy_dev, valid=valid_d)
         kp_mask, road_mask = kp_u8.cpu().numpy(), road_u8.cpu().numpy()
         _poll_finite(net, device)                      # the masks are on the host, so every LayerNorm pass of pass 1 has reported
         lap("normalise + mask D2H")
@@ -707,6 +803,22 @@ class _Lane:
         main.wait_stream(self.copy_stream)
         return dst
 
+    def on_copy_stream(self, pool, name, fn):
+        """fn() -> a small device tensor, launched on the copy stream (behind the uploads queued so far, which themselves wait for the
+        compute work queued when they were issued) and fetched: returns it as a numpy array after ONE host wait on that stream's event.
+        For work that touches nothing the compute stream owns."""
+        if not self.cuda:
+            return fn().numpy().copy()
+        with torch.cuda.stream(self.copy_stream):
+            t = fn()
+            h = pool.get("down_" + name, t.shape, t.dtype)
+            h.copy_(t, non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record(self.copy_stream)
+        t.record_stream(self.copy_stream)
+        ev.synchronize()
+        return h.numpy().copy()
+
     def download(self, pool, name, tensors):
         """Device tensors -> page-locked host tensors (asynchronous) + the event that says they have landed."""
         outs = []
@@ -725,7 +837,13 @@ class _SceneJob:
     pass
 
 
-def infer_imgs(net, imgs, config, device=None, tile_sharded=None, pipelined=None):
+def _valid_iter(valids):
+    """The masks parallel to a scene sequence, one next() per scene: `valids` (any iterable, entries may be None), or None for ever."""
+    import itertools
+    return itertools.repeat(None) if valids is None else itertools.chain(iter(valids), itertools.repeat(None))
+
+
+def infer_imgs(net, imgs, config, device=None, tile_sharded=None, pipelined=None, valids=None):
     """infer_one_img over a sequence of scenes, as a generator of the same tuples in the same order — software-pipelined on
     one GPU: while the device runs pass 1 of scene i+1, the host does scene i's mask -> points -> pass-2 queries; scene i's
     TopoNet batches are queued behind that pass 1 and its edge vote runs while scene i+2 is on the device.  One compute stream
@@ -738,16 +856,20 @@ def infer_imgs(net, imgs, config, device=None, tile_sharded=None, pipelined=None
     scene, its three exchange steps strictly in sequence — and the PIPELINED one (_infer_imgs_tile_sharded; `pipelined=True`, config
     key TILE_SHARD_PIPELINE, CLI `--shard tiles-pipelined`), which interleaves the band reduce of scene i+1 with the point broadcast
     and vote gather of scene i.  The pipelined loop has only ever run on gloo / CPU (no multi-GPU box was available to the builder:
-    DESIGN.md §6), so it stays opt-in until an RCCL run exists; both give the same results (tests/test_distributed_cpu.py)."""
+    DESIGN.md §6), so it stays opt-in until an RCCL run exists; both give the same results (tests/test_distributed_cpu.py).
+    valids: validity masks parallel to imgs (a list or any iterable, read in step with imgs; entries may be None), see infer_one_img.
+    A masked scene's tile selection — mask upload, count kernel, n int32 back, one host wait — is issued on the upload lane; like every
+    upload there it starts after the work the compute stream holds at that moment (the previous scene's pass 2)."""
     neighbor_queries(config)                          # fail before any scene touches the device
+    valids = _valid_iter(valids)
     if D.is_distributed() if tile_sharded is None else tile_sharded:
         if pipelined is None:
             pipelined = _cfg_switch(config.TILE_SHARD_PIPELINE, False)
         if pipelined:
-            yield from _infer_imgs_tile_sharded(net, imgs, config, device)
+            yield from _infer_imgs_tile_sharded(net, imgs, config, device, valids=valids)
         else:
             for img in imgs:
-                yield infer_one_img(net, img, config, device=device)
+                yield infer_one_img(net, img, config, device=device, valid=next(valids))
         return
     device = torch.device(device) if device is not None else next(net.parameters()).device
     lane = _Lane(device)
@@ -762,19 +884,39 @@ def infer_imgs(net, imgs, config, device=None, tile_sharded=None, pipelined=None
             t_sec.append(time.perf_counter())
             print(f"[infer_imgs] {name}: {(t_sec[-1] - t_sec[-2]) * 1e3:.1f} ms", flush=True)
 
-    def launch_pass1(img, pool):                       # G1: upload, pass 1, normalise, masks on their way to the host
+    def launch_pass1(img, pool, valid=None):           # G1: upload, pass 1, normalise, masks on their way to the host
         job = _SceneJob()
         img, job.infos, all_xy = _scene_plan(img, config)
-        job.pool, job.n_tiles = pool, len(job.infos)
+        if valid is not None:
+            valid, min_frac, fill = _valid_plan(valid, img.shape[:2], config)
+        job.pool = pool
         scene = lane.upload(pool, "scene", img)
         xy_dev = lane.upload(pool, "xy", all_xy)
         lap("stage + queue scene upload")
+        valid_d = None
+        if valid is not None:
+            # selection on the upload lane: mask upload, count kernel (it uses no workspace of the library context) and the n int32
+            # on their way back are queued on the copy stream.  Like every upload of this lane they start after what the compute
+            # stream holds at this moment (the previous scene's TopoNet work, about a millisecond), and the host waits for the counts
+            valid_d = lane.upload(pool, "valid_mask", valid)   # a key of its own: "valid" stages pass 2's pair flags (points_and_pass2)
+            counts = lane.on_copy_stream(pool, "counts", lambda: net.scene_tile_valid(valid_d, xy_dev))
+            kept = select_tiles(counts, config.PATCH_SIZE, min_frac)
+            lap("tile selection (upload lane)")
+            job.infos, all_xy = [job.infos[i] for i in kept], np.ascontiguousarray(all_xy[kept])
+            if len(kept) == 0:                         # nothing to run: zero masks, no nodes, the encoder is not launched
+                job.n_tiles, job.e1, job.emb = 0, None, None
+                job.masks = [torch.zeros(img.shape[:2], dtype=torch.uint8) for _ in range(2)]
+                return job
+            xy_dev = lane.upload(pool, "xy_kept", all_xy)
+            scene = net.scene_fill_invalid(scene, valid_d, fill)       # the device copy of this scene, not the caller's array
+        job.n_tiles = len(job.infos)
         if prof and lane.cuda:
             job.t = [torch.cuda.Event(enable_timing=True) for _ in range(5)]
             job.t[0].record()
         kp_c, road_c, job.emb = net.scene_pass1(scene, xy_dev, bs)
         lap("queue pass 1")
-        kp_u8, road_u8 = net.scene_normalise(kp_c, road_c, xy_dev)
+        kp_u8, road_u8 = net.scene_normalise(kp_c, road_c, xy_dev) if valid_d is None else \
+            net.scene_normalise(kp_c, road_c, xy_dev, valid=valid_d)
         if prof and lane.cuda:
             job.t[1].record()
         job.masks, job.e1 = lane.download(pool, "mask", [kp_u8, road_u8])
@@ -860,7 +1002,7 @@ def infer_imgs(net, imgs, config, device=None, tile_sharded=None, pipelined=None
     if img is None:
         return
     with _host_quiet():
-        cur = launch_pass1(img, pools[0])
+        cur = launch_pass1(img, pools[0], next(valids))
     prev, i = None, 0
     while cur is not None:
         with _host_quiet():
@@ -870,7 +1012,7 @@ def infer_imgs(net, imgs, config, device=None, tile_sharded=None, pipelined=None
                 _poll_finite(net, device)
             lap("wait for pass-1 masks")
             img = next(it, None)
-            nxt = launch_pass1(img, pools[(i + 1) % 2]) if img is not None else None
+            nxt = launch_pass1(img, pools[(i + 1) % 2], next(valids)) if img is not None else None
             res = finish(prev) if prev is not None else None
         if prev is not None:
             yield res
@@ -882,7 +1024,7 @@ def infer_imgs(net, imgs, config, device=None, tile_sharded=None, pipelined=None
     yield res
 
 
-def _infer_imgs_tile_sharded(net, imgs, config, device=None, stats=None):
+def _infer_imgs_tile_sharded(net, imgs, config, device=None, stats=None, valids=None):
     """Tile-sharded scenes (BASELINE configs[3]: ONE scene's tiles over the ranks of a node), software-pipelined like infer_imgs:
     every rank queues pass 1 of scene i+1 on its GPU BEFORE the host stages of scene i, so that rank 0's serial section (mask ->
     graph points, reference graph_extraction.py:130-139 / graph_utils.py:572-591, and the final vote merge) runs while all GPUs —
@@ -901,13 +1043,30 @@ def _infer_imgs_tile_sharded(net, imgs, config, device=None, stats=None):
     for k in ("pass1_queue_ms", "points_host_ms", "pass2_ms", "merge_host_ms", "canvas_bytes", "points_bytes", "votes_bytes", "scenes"):
         stats.setdefault(k, 0.0)
 
-    def stage1(img):
+    valids = _valid_iter(valids)
+
+    def stage1(img, valid=None):
         job = _SceneJob()
         t0 = time.perf_counter()
         job.img, job.infos, job.all_xy = _scene_plan(img, config)
-        job.lo, job.hi = shard_tiles(len(job.infos), world, rank)
+        if valid is not None:
+            valid, min_frac, fill = _valid_plan(valid, job.img.shape[:2], config)
         scene = torch.as_tensor(np.ascontiguousarray(job.img), dtype=torch.uint8).to(device, non_blocking=cuda)
         job.xy_dev = torch.as_tensor(job.all_xy).to(device)
+        job.empty, valid_d = False, None
+        if valid is not None:                          # the same integer counts, hence the same kept list, on every rank
+            valid_d = torch.from_numpy(valid).to(device)
+            kept = select_tiles(_tile_counts(net, valid_d, job.xy_dev), config.PATCH_SIZE, min_frac)
+            job.infos, job.all_xy = [job.infos[i] for i in kept], np.ascontiguousarray(job.all_xy[kept])
+            if len(kept) == 0:                         # no rank runs anything and no exchange step is entered
+                job.empty = True
+                stats["pass1_queue_ms"] += 1e3 * (time.perf_counter() - t0)
+                return job
+            job.xy_dev = torch.as_tensor(job.all_xy).to(device)
+            if not cuda:
+                scene = scene.clone()
+            scene = net.scene_fill_invalid(scene, valid_d, fill)
+        job.lo, job.hi = shard_tiles(len(job.infos), world, rank)
         kp_c, road_c, job.emb = net.scene_pass1(scene, job.xy_dev[job.lo:job.hi], bs)
         bands = D.tile_bands(job.all_xy, int(config.PATCH_SIZE), world) if world > 1 else None
         D.reduce_canvases(kp_c, road_c, dst=0, bands=bands)
@@ -918,7 +1077,8 @@ def _infer_imgs_tile_sharded(net, imgs, config, device=None, stats=None):
             stats["canvas_bytes"] += D.canvas_bytes(bands, rows) if rank == 0 else 2 * 4 * rows * max(0, x1 - x0)
         job.masks = job.e1 = None
         if rank == 0:
-            kp_u8, road_u8 = net.scene_normalise(kp_c, road_c, job.xy_dev)
+            kp_u8, road_u8 = net.scene_normalise(kp_c, road_c, job.xy_dev) if valid_d is None else \
+                net.scene_normalise(kp_c, road_c, job.xy_dev, valid=valid_d)
             if cuda:       # asynchronous download behind the scene's own kernels: the host does not wait here
                 job.masks = [torch.empty(t.shape, dtype=t.dtype, pin_memory=True) for t in (kp_u8, road_u8)]
                 for h, t in zip(job.masks, (kp_u8, road_u8)):
@@ -931,6 +1091,8 @@ def _infer_imgs_tile_sharded(net, imgs, config, device=None, stats=None):
         return job
 
     def stage2(job):
+        if job.empty:
+            return _empty_result(*job.img.shape[:2]) if rank == 0 else None
         t0 = time.perf_counter()
         graph_points = kp_mask = road_mask = None
         if rank == 0:
@@ -973,11 +1135,11 @@ def _infer_imgs_tile_sharded(net, imgs, config, device=None, stats=None):
     if img is None:
         return
     with _host_quiet():
-        cur = stage1(img)
+        cur = stage1(img, next(valids))
     while cur is not None:
         with _host_quiet():
             img = next(it, None)
-            nxt = stage1(img) if img is not None else None        # the next scene's pass 1 is on the device before this scene's host work
+            nxt = stage1(img, next(valids)) if img is not None else None        # the next scene's pass 1 is on the device before this scene's host work
             res = stage2(cur)
         stats["scenes"] += 1
         yield res
@@ -994,6 +1156,32 @@ def read_rgb_img(path):
     """dataset.py:16-19 (cv2.imread + BGR->RGB): [H,W,3] uint8 RGB.  PIL decodes the same 8-bit PNGs."""
     from PIL import Image
     return np.ascontiguousarray(np.array(Image.open(path).convert("RGB")))
+
+
+def has_alpha(path):
+    """Whether an image file has an alpha channel (reads the header only); False for .npy scenes."""
+    from PIL import Image
+    if str(path).endswith(".npy"):
+        return False
+    with Image.open(path) as im:
+        return im.mode in ("RGBA", "LA", "PA") or "transparency" in im.info       # a palette / grey PNG with a tRNS chunk as well
+
+
+def read_alpha_valid(path):
+    """The validity mask an image file carries itself: alpha > 0 of a file with an alpha channel or a transparency (tRNS) entry as
+    bool [H,W]; None for a file without one (read_rgb_img drops alpha)."""
+    from PIL import Image
+    if not has_alpha(path):
+        return None
+    return np.ascontiguousarray(np.array(Image.open(path).convert("RGBA").getchannel("A")) > 0)
+
+
+def read_valid_mask(path):
+    """A validity mask file: .npy (bool or uint8 [H,W]) as it is, or an image whose non-zero pixels are valid (read as 8-bit grey)."""
+    from PIL import Image
+    if str(path).endswith(".npy"):
+        return np.load(path)
+    return np.ascontiguousarray(np.array(Image.open(path).convert("L")) > 0)
 
 
 def cityscale_data_partition():
@@ -1050,7 +1238,9 @@ def main(argv=None):
     `viz/` renderings and the ground-truth pickle the reference loads but only uses in commented-out code (visualisation,
     SURVEY §2 #17).  Extras: `--images a.png b.npy ...` runs explicit scene files instead of the dataset split; under torchrun
     (one process per GPU) the scenes are dealt round-robin to the ranks (`--shard scenes`, default) or every scene's tiles are split
-    over the ranks (`--shard tiles`; `tiles-pipelined` for the software-pipelined loop), all ranks writing into the one output directory."""
+    over the ranks (`--shard tiles`; `tiles-pipelined` for the software-pipelined loop), all ranks writing into the one output directory.
+    `--valid-masks m0.png m1.npy ...` (parallel to `--images`; `-` = no mask for that scene) gives every scene a validity mask
+    (infer_one_img's `valid`); without it an RGBA `--images` file uses its alpha > 0.  Output formats do not change."""
     import argparse
     import os
     import pickle
@@ -1064,6 +1254,9 @@ def main(argv=None):
     ap.add_argument("--output_dir", default=None, help="Name of the output dir, if not specified will use timestamp")
     ap.add_argument("--device", default="cuda", help="device to use (an MI355X: there is no CPU path)")
     ap.add_argument("--images", nargs="*", default=None, help="(extension) explicit scene images instead of the dataset split")
+    ap.add_argument("--valid-masks", nargs="*", default=None, metavar="MASK",
+                    help="(extension) one validity mask per --images entry (.npy bool / uint8 [H,W], or an image: non-zero = valid; "
+                         "'-' = none): nodata tiles are skipped and nothing is predicted on nodata.  Default: alpha > 0 of an RGBA image")
     ap.add_argument("--shard", choices=("scenes", "tiles", "tiles-pipelined"), default="scenes",
                     help="(extension, multi-GPU runs under torchrun) scenes: every rank takes whole scenes, no data-path collective "
                          "(throughput); tiles: the tiles of every scene are split over the ranks, scene by scene (latency of one scene); "
@@ -1089,6 +1282,8 @@ def main(argv=None):
     by_scene = world > 1 and args.shard == "scenes"
     net = _build_net(config, args.checkpoint, device)
 
+    if args.valid_masks is not None and (args.images is None or len(args.valid_masks) != len(args.images)):
+        ap.error("--valid-masks takes exactly one entry per --images entry ('-' for a scene without a mask)")
     if args.images is not None:
         jobs = [(os.path.splitext(os.path.basename(p))[0], p) for p in args.images]
     elif config.DATASET == "cityscale":
@@ -1099,8 +1294,14 @@ def main(argv=None):
         jobs = [(i, "./spacenet/RGB_1.0_meter/{}__rgb.png".format(i)) for i in test_img_indices]
     else:
         raise ValueError(f"config.DATASET must be 'cityscale' or 'spacenet' (got {config.DATASET!r}), or pass --images")
+    job_masks = [None if m == "-" else m for m in args.valid_masks] if args.valid_masks is not None else [None] * len(jobs)
     if by_scene:
         jobs = jobs[rank::world]                 # independent scenes: round-robin over the ranks, nothing to exchange
+        job_masks = job_masks[rank::world]
+    use_alpha = args.valid_masks is None and any(has_alpha(p) for _, p in jobs)      # headers only; mask files take precedence
+    masked = args.valid_masks is not None or use_alpha
+    import collections
+    scene_valids = collections.deque()           # the masks of the scenes the loader has handed out, in the same order
 
     output_dir_prefix = "./save/infer_"
     if world > 1:                                # one directory for all ranks: rank 0 creates it (and its timestamp), the others wait
@@ -1118,14 +1319,24 @@ def main(argv=None):
     from concurrent.futures import ThreadPoolExecutor
 
     def scenes(depth=3):                         # decode ahead on worker threads: a 2048^2 RGB PNG takes ~100 ms to decode, more than
-        load = lambda path: np.load(path) if str(path).endswith(".npy") else read_rgb_img(path)   # the GPU needs for the scene
+        def load(path, mask_path):               # the GPU needs for the scene
+            img = np.load(path) if str(path).endswith(".npy") else read_rgb_img(path)
+            if mask_path is not None:
+                return img, read_valid_mask(mask_path)
+            return img, (read_alpha_valid(path) if use_alpha else None)
         with ThreadPoolExecutor(depth) as ex:
             futs = {}
             for j in range(len(jobs)):
                 for k in range(j, min(j + depth, len(jobs))):
                     if k not in futs:
-                        futs[k] = ex.submit(load, jobs[k][1])
-                yield futs.pop(j).result()
+                        futs[k] = ex.submit(load, jobs[k][1], job_masks[k])
+                img, valid = futs.pop(j).result()
+                scene_valids.append(valid)
+                yield img
+
+    def valids():                                # infer_imgs reads a scene, then its mask
+        while True:
+            yield scene_valids.popleft()
 
     mask_save_dir, graph_save_dir = os.path.join(output_dir, "mask"), os.path.join(output_dir, "graph")
 
@@ -1149,7 +1360,7 @@ def main(argv=None):
     # encoding and pickling (tens of ms per 2048^2 scene) run on two writer threads so that the loop goes straight back to the GPU.
     total_inference_seconds = 0.0
     results = infer_imgs(net, scenes(), config, device=device, tile_sharded=world > 1 and not by_scene,
-                         pipelined=True if args.shard == "tiles-pipelined" else None)
+                         pipelined=True if args.shard == "tiles-pipelined" else None, **(dict(valids=valids()) if masked else {}))
     with ThreadPoolExecutor(2) as writer:
         pending = []
         for img_id, path in jobs:

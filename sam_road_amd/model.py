@@ -528,17 +528,69 @@ class SAMRoad(nn.Module):
         return canvas_kp, canvas_road, emb.permute(0, 3, 1, 2)
 
     @torch.no_grad()
-    def scene_normalise(self, canvas_kp, canvas_road, tile_xy):
-        """(canvas / coverage count) * 255 -> uint8 masks [H,W] (inferencer.py:106-110); tile_xy = ALL tiles."""
+    def scene_normalise(self, canvas_kp, canvas_road, tile_xy, valid=None):
+        """(canvas / coverage count) * 255 -> uint8 masks [H,W] (inferencer.py:106-110); tile_xy = ALL tiles.  valid (u8 [H,W] on the
+        GPU, non-zero = valid pixel): the masks are also 0 on every invalid pixel (srh_scene_normalise_valid_hw); None: the call and
+        the kernels of a scene without a mask."""
         dev = canvas_kp.device
         ctx, _ = self._weights(dev)
         H, W = int(canvas_kp.shape[0]), int(canvas_kp.shape[1])
         tile_xy = tile_xy.to(device=dev, dtype=torch.int32).contiguous()
         kp = torch.empty((H, W), dtype=torch.uint8, device=dev)
         road = torch.empty((H, W), dtype=torch.uint8, device=dev)
+        if valid is not None:
+            valid = self._valid_u8(valid, H, W, dev)
+            with torch.cuda.device(dev):
+                ctx.check(ctx.lib.srh_scene_normalise_valid_hw(ctx.handle, canvas_kp.data_ptr(), canvas_road.data_ptr(), H, W,
+                                                               tile_xy.data_ptr(), tile_xy.shape[0], self.image_size, valid.data_ptr(),
+                                                               kp.data_ptr(), road.data_ptr(), self._stream(dev)),
+                          "srh_scene_normalise_valid_hw")
+            return kp, road
         with torch.cuda.device(dev):
             ctx.check(ctx.lib.srh_scene_normalise_hw(ctx.handle, canvas_kp.data_ptr(), canvas_road.data_ptr(), H, W,
                                                      tile_xy.data_ptr(), tile_xy.shape[0], self.image_size,
                                                      kp.data_ptr(), road.data_ptr(), self._stream(dev)),
                       "srh_scene_normalise_hw")
         return kp, road
+
+    # ---- scene level, validity mask (nodata): which tiles hold data, nodata neutralised before the crop ------------------------
+    @staticmethod
+    def _valid_u8(valid, H, W, dev):
+        if valid.device != dev or valid.dtype not in (torch.uint8, torch.bool) or tuple(valid.shape) != (H, W):
+            raise ValueError(f"valid must be a uint8 / bool [{H}, {W}] tensor on {dev}, got {valid.dtype} {tuple(valid.shape)} on {valid.device}")
+        valid = valid.contiguous()
+        return valid.view(torch.uint8) if valid.dtype == torch.bool else valid
+
+    @torch.no_grad()
+    def scene_tile_valid(self, valid_u8, tile_xy):
+        """Valid pixels per tile: valid_u8 [H,W] uint8 / bool on the GPU (non-zero = valid), tile_xy int32 [n,2] (x0,y0), every tile
+        inside the scene -> int32 [n] on the GPU (srh_scene_tile_valid: exact integer counts).  The call uses no workspace of the
+        library context, so it may run on a side stream beside a scene's pass 1."""
+        dev = valid_u8.device
+        ctx, _ = self._weights(dev)
+        H, W = int(valid_u8.shape[0]), int(valid_u8.shape[1])
+        valid_u8 = self._valid_u8(valid_u8, H, W, dev)
+        tile_xy = tile_xy.to(device=dev, dtype=torch.int32).contiguous()
+        counts = torch.empty((tile_xy.shape[0],), dtype=torch.int32, device=dev)
+        if tile_xy.shape[0] == 0:                    # nothing to count (an empty tensor has no address to hand over)
+            return counts
+        with torch.cuda.device(dev):
+            ctx.check(ctx.lib.srh_scene_tile_valid(ctx.handle, valid_u8.data_ptr(), H, W, tile_xy.data_ptr(), tile_xy.shape[0],
+                                                   self.image_size, counts.data_ptr(), self._stream(dev)), "srh_scene_tile_valid")
+        return counts
+
+    @torch.no_grad()
+    def scene_fill_invalid(self, scene_u8, valid_u8, fill):
+        """scene_u8 [H,W,3] uint8 on the GPU, IN PLACE: every pixel whose valid_u8 [H,W] is 0 becomes the colour `fill` (three ints
+        0..255).  Returns scene_u8 (srh_scene_fill_invalid)."""
+        dev = scene_u8.device
+        ctx, _ = self._weights(dev)
+        if scene_u8.dtype != torch.uint8 or scene_u8.dim() != 3 or scene_u8.shape[2] != 3 or not scene_u8.is_contiguous():
+            raise ValueError(f"scene must be a contiguous uint8 [H,W,3] tensor, got {scene_u8.dtype} {tuple(scene_u8.shape)}")
+        H, W = int(scene_u8.shape[0]), int(scene_u8.shape[1])
+        valid_u8 = self._valid_u8(valid_u8, H, W, dev)
+        r, g, b = (int(v) for v in fill)
+        with torch.cuda.device(dev):
+            ctx.check(ctx.lib.srh_scene_fill_invalid(ctx.handle, scene_u8.data_ptr(), valid_u8.data_ptr(), H, W, r, g, b,
+                                                     self._stream(dev)), "srh_scene_fill_invalid")
+        return scene_u8

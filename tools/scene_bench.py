@@ -9,6 +9,8 @@ The final map_decoder bias is lowered so that the random network yields sparse m
     python tools/scene_bench.py [--bias -2.2] [--wscale 16] [--batch 64] [--iters 3]
     python tools/scene_bench.py --scene 2048 4096 --tiles 16 32     # a rectangular scene H W (or 2048x4096) with [n_y, n_x] tiles;
                                                                     # --scene 4096 --tiles 32 = the square a user had to pad it to
+    python tools/scene_bench.py --scene 2048 4096 --tiles 16 32 --valid-frac 0.5    # a validity mask: a diagonal band covering that share
+                                                                    # of the scene; only tiles that hold valid pixels run (kept / all is printed)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 tools/scene_bench.py    # N GPUs:
         tiles sharded over the ranks (RCCL: packed-weight broadcast, banded canvas reduce, point broadcast, vote gather);
         rank 0 prints ms/scene (max over ranks) and the per-rank stage times
@@ -41,6 +43,8 @@ def main():
     ap.add_argument("--wscale", type=float, default=16.0)   # spread of the final layer: with 16 the random net yields ~4k graph points
     ap.add_argument("--scene", nargs="+", default=["2048"], metavar="PX", help="scene size: S (square), H W or HxW; multiples of 8")
     ap.add_argument("--tiles", nargs="+", type=int, default=[16], metavar="N", help="INFER_PATCHES_PER_EDGE: N or N_Y N_X")
+    ap.add_argument("--valid-frac", type=float, default=None, metavar="F",
+                    help="run the scene with a validity mask: a diagonal band that covers the share F (0 < F <= 1) of its pixels")
     ap.add_argument("--no-pipelined", action="store_true", help="skip the infer_imgs runs (12- and 48-scene streams)")
     args = ap.parse_args()
     H, W = parse_scene(args.scene)
@@ -87,11 +91,29 @@ def main():
     img = np.kron(coarse, np.ones((8, 8, 1), np.float32)).astype(np.uint8)
 
     img, infos, all_xy = _scene_plan(img, cfg)         # the product's own validation and tile list
+    n_all = len(infos)
+    valid = None
+    if args.valid_frac is not None:
+        if not 0.0 < args.valid_frac <= 1.0:
+            ap.error("--valid-frac takes a share in (0, 1]")
+        # |y / H - x / W| < w covers 1 - (1 - w)^2 of the rectangle
+        yy, xx = np.mgrid[0:H, 0:W]
+        valid = np.abs(yy / H - xx / W) < 1.0 - np.sqrt(1.0 - args.valid_frac)
+        from sam_road_amd.inferencer import scene_tiles
+        infos = scene_tiles(img.shape, cfg, valid=valid, net=net)
+        all_xy = np.array([[p[1][0], p[1][1]] for p in infos], dtype=np.int32).reshape(-1, 2)
     xy = torch.as_tensor(all_xy).to(dev)
     scene = torch.as_tensor(img).to(dev)
+    valid_d = None if valid is None else torch.as_tensor(valid).to(dev)
     lo, hi = shard_tiles(len(infos), world, rank)
 
     def pass1():              # this rank's share of the tiles (no collective: tile throughput)
+        if valid_d is not None:    # the masked pass 1 from the resident scene: count, fill (of a copy), kept tiles, masked normalise
+            net.scene_tile_valid(valid_d, torch.as_tensor(_scene_plan(img, cfg)[2]).to(dev)).cpu()
+            filled = net.scene_fill_invalid(scene.clone(), valid_d, (124, 116, 104))
+            kp, road, emb = net.scene_pass1(filled, xy[lo:hi], args.batch)
+            kpu, ru = net.scene_normalise(kp, road, xy, valid=valid_d)
+            return kpu.cpu(), ru.cpu()
         kp, road, emb = net.scene_pass1(scene, xy[lo:hi], args.batch)
         kpu, ru = net.scene_normalise(kp, road, xy)
         return kpu.cpu(), ru.cpu()
@@ -115,12 +137,12 @@ def main():
     plain = inf.extract_graph_points, inf.edge_votes
     inf.extract_graph_points = timed("extract_graph_points", inf.extract_graph_points)
     inf.edge_votes = timed("edge_votes", inf.edge_votes)
-    res = infer_one_img(net, img, cfg)
+    res = infer_one_img(net, img, cfg, valid=valid)
     for k in acc: acc[k] = 0.0
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(args.iters):
-        res = infer_one_img(net, img, cfg)
+        res = infer_one_img(net, img, cfg, valid=valid)
     torch.cuda.synchronize()
     full = (time.perf_counter() - t0) / args.iters
     # throughput of the CLI's scene loop: the same scenes through the software-pipelined generator (one GPU only; the timed
@@ -130,18 +152,18 @@ def main():
     inf.extract_graph_points, inf.edge_votes = plain            # the timing wrappers synchronise the device
     if world == 1 and not args.no_pipelined:
         n, piped_runs, same = 12, [], True
-        list(inf.infer_imgs(net, (img for _ in range(3)), cfg))
+        list(inf.infer_imgs(net, (img for _ in range(3)), cfg, valids=(valid for _ in range(3))))
         for _ in range(max(args.iters, 3)):                     # several runs: the rate varies in phases of a second or two
             torch.cuda.synchronize()
             t0 = time.perf_counter()
-            outs = list(inf.infer_imgs(net, (img for _ in range(n)), cfg))
+            outs = list(inf.infer_imgs(net, (img for _ in range(n)), cfg, valids=(valid for _ in range(n))))
             torch.cuda.synchronize()
             piped_runs.append(round(1e3 * (time.perf_counter() - t0) / n, 2))
             same = same and all(all(np.array_equal(a, b) for a, b in zip(o, res)) for o in outs)
         piped = float(np.median(piped_runs)) * 1e-3
         torch.cuda.synchronize()                                 # one long run: fill + drain (~one scene) amortised over 48 scenes
         t0 = time.perf_counter()
-        for o in inf.infer_imgs(net, (img for _ in range(48)), cfg):
+        for o in inf.infer_imgs(net, (img for _ in range(48)), cfg, valids=(valid for _ in range(48))):
             pass
         torch.cuda.synchronize()
         piped48 = (time.perf_counter() - t0) / 48
@@ -162,7 +184,8 @@ def main():
             dist.destroy_process_group()
         return
     nodes, edges, kp, road = res
-    print(json.dumps({"scene": f"synthetic {H}x{W} u8, {len(infos)} tiles of 512^2 ({per_edge} per edge, margin 64)", "n_gpus": world,
+    print(json.dumps({"scene": f"synthetic {H}x{W} u8, {n_all} tiles of 512^2 ({per_edge} per edge, margin 64)", "n_gpus": world,
+                      "valid_frac": None if valid is None else round(float(valid.mean()), 4), "tiles_kept": len(infos), "tiles_all": n_all,
                       "ms_weight_share": round(1e3 * t_w, 2) if world > 1 else None, "per_rank": per_rank,
                       "infer_batch_size": args.batch, "ms_per_scene_pass1": round(1e3 * p1, 2),
                       "tiles_per_s_pass1": round(len(infos) / p1, 1), "ms_per_scene_full": round(1e3 * full, 2),
