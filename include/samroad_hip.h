@@ -188,6 +188,29 @@ int srh_scene_normalise_valid_hw(srh_ctx* ctx, const float* canvas_kp, const flo
                                  const int32_t* tile_xy, int n_tiles, int P, const uint8_t* valid, uint8_t* kp_u8,
                                  uint8_t* road_u8, void* stream);
 
+/* Window-weighted fusion of overlapping tiles (config key FUSE_WINDOW; an extension, the reference fuses with a uniform mean).  Three
+ * additive entries; the ABI number stays 11 because nothing existing changes, and a scene without a window calls none of them.
+ * profile = device f32 [P], every value finite and in [2^-20, 2^20] (the caller checks it: the host cannot read the array here).  The
+ * weight of tile t at scene pixel (x, y) is w = profile[x - x0_t] * profile[y - y0_t], one f32 product.
+ *
+ * srh_scene_pass1_window_hw: srh_scene_pass1_hw whose canvases receive canvas = fma(w, score, canvas) per covering tile, in tile order
+ *   (deterministic, no atomics, independent of B).  Same encoder and decoder launches, same embeddings, same preconditions and
+ *   SRH_ERR_BAD_ARG cases as srh_scene_pass1_hw; the tile size is the model's PATCH_SIZE, so profile must hold that many values.
+ * srh_scene_normalise_window_hw: u8 = trunc((canvas / Wsum) * 255) with Wsum = the f32 sum of w over ALL n_tiles tiles in list order;
+ *   0 where no tile covers the pixel and, with valid != NULL (u8 [H,W], non-zero = valid), where the pixel is invalid.  An all-ones
+ *   profile gives the bytes of srh_scene_normalise_hw / srh_scene_normalise_valid_hw.  P must be a tile size (a multiple of 16 from 128
+ *   to 1024) and H * W <= 2^31 - 1, else SRH_ERR_BAD_ARG.
+ * srh_op_scene_fuse_window (test-only): the weighted add of pass 1 applied to caller-supplied scores f32 [n,P,P,2], all n tiles in
+ *   one launch; H, W >= P, every tile inside the scene. */
+int srh_scene_pass1_window_hw(srh_ctx* ctx, const srh_weights* w, const uint8_t* scene, int H, int W, const int32_t* tile_xy,
+                              int n_tiles, int B, const float* profile, float* canvas_kp, float* canvas_road,
+                              float* embeddings_all, void* stream);
+int srh_scene_normalise_window_hw(srh_ctx* ctx, const float* canvas_kp, const float* canvas_road, int H, int W,
+                                  const int32_t* tile_xy, int n_tiles, int P, const float* profile, const uint8_t* valid,
+                                  uint8_t* kp_u8, uint8_t* road_u8, void* stream);
+int srh_op_scene_fuse_window(srh_ctx* ctx, const float* scores, int n, int P, const int32_t* tile_xy, const float* profile,
+                             float* canvas_kp, float* canvas_road, int H, int W, void* stream);
+
 /* op level (used by the parity tests to localise a failure; same kernels as above) ----------------- */
 
 /* out = act(A[M,K] W[N,K]^T + bias) (+resid); A,W fp16; N%128==0, K%64==0. act: 0/1 GELU/2 ReLU. */

@@ -1066,8 +1066,8 @@ static bool scene_dims_ok(int H, int W) { return H > 0 && W > 0 && (long long)H 
 
 static int scene_pass1_impl(srh_ctx* c, const char* who, const srh_weights* w, const uint8_t* scene, int H, int W,
                             const int32_t* tile_xy, int n_tiles, int B, float* canvas_kp, float* canvas_road,
-                            float* embeddings_all, void* stream) {
-    if (!c || !w || !scene || !tile_xy || !canvas_kp || !canvas_road || !embeddings_all)
+                            float* embeddings_all, void* stream, bool has_window = false, const float* profile = nullptr) {
+    if (!c || !w || !scene || !tile_xy || !canvas_kp || !canvas_road || !embeddings_all || (has_window && !profile))
         return fail(c, SRH_ERR_BAD_ARG, std::string(who) + ": null argument");
     if (n_tiles < 0 || B <= 0 || H < w->cfg.patch_size || W < w->cfg.patch_size || !scene_dims_ok(H, W))
         return fail(c, SRH_ERR_BAD_ARG, std::string(who) + ": bad sizes");
@@ -1082,6 +1082,10 @@ static int scene_pass1_impl(srh_ctx* c, const char* who, const srh_weights* w, c
         PatchParams pp;
         pp.src = scene; pp.src_is_u8 = 1; pp.scene_W = W; pp.tile_xy = tile_xy + 2 * off;
         TRY(encode_batch(c, w, pp, nb, nullptr, c->scores_ws.as<float>(), embeddings_all + emb_per_tile * off, s));
+        if (has_window)      // FUSE_WINDOW (scene_window.hip): only this launch differs, the encoder and decoder are the same calls
+            TRYK(c, "scene_add_window", 0, (double)nb * P * P * 8 * 3, s,
+                 launch_scene_add_window(c->scores_ws.as<float>(), nb, P, tile_xy + 2 * off, profile, canvas_kp, canvas_road, H, W, s));
+        else
         TRYK(c, "scene_add", 0, (double)nb * P * P * 8 * 3, s,
              launch_scene_add(c->scores_ws.as<float>(), nb, P, tile_xy + 2 * off, canvas_kp, canvas_road, H, W, s));
     }
@@ -1160,6 +1164,45 @@ extern "C" int srh_scene_normalise_valid_hw(srh_ctx* c, const float* canvas_kp, 
                                             uint8_t* road_u8, void* stream) {
     return scene_normalise_impl(c, "srh_scene_normalise_valid_hw", canvas_kp, canvas_road, H, W, tile_xy, n_tiles, P, kp_u8, road_u8, stream,
                                 true, valid);
+}
+
+// ---- scene level, window-weighted fusion (kernels in scene_window.hip, behaviour in DESIGN.md §6e) -----------------------------
+static bool tile_size_ok(int P) { return P >= 128 && P <= 1024 && P % 16 == 0; }
+
+extern "C" int srh_scene_pass1_window_hw(srh_ctx* c, const srh_weights* w, const uint8_t* scene, int H, int W, const int32_t* tile_xy,
+                                         int n_tiles, int B, const float* profile, float* canvas_kp, float* canvas_road,
+                                         float* embeddings_all, void* stream) {
+    return scene_pass1_impl(c, "srh_scene_pass1_window_hw", w, scene, H, W, tile_xy, n_tiles, B, canvas_kp, canvas_road, embeddings_all, stream,
+                            true, profile);
+}
+
+extern "C" int srh_scene_normalise_window_hw(srh_ctx* c, const float* canvas_kp, const float* canvas_road, int H, int W,
+                                             const int32_t* tile_xy, int n_tiles, int P, const float* profile, const uint8_t* valid,
+                                             uint8_t* kp_u8, uint8_t* road_u8, void* stream) {
+    if (!c || !canvas_kp || !canvas_road || !tile_xy || !profile || !kp_u8 || !road_u8)
+        return fail(c, SRH_ERR_BAD_ARG, "srh_scene_normalise_window_hw: null argument");
+    if (!scene_dims_ok(H, W) || n_tiles < 0 || !tile_size_ok(P)) return fail(c, SRH_ERR_BAD_ARG, "srh_scene_normalise_window_hw: bad sizes");
+    hipSetDevice(c->device);
+    hipStream_t s = (hipStream_t)stream;
+    const double npx = (double)H * W;
+    // one kernel: the weight sum stays in a register (no counter canvas), so the context's counter workspace is not used
+    TRYK(c, "scene_norm_window", 0, npx * (valid ? 11 : 10), s,
+         launch_scene_normalise_window(canvas_kp, canvas_road, H, W, tile_xy, n_tiles, P, profile, valid, kp_u8, road_u8, s));
+    return 0;
+}
+
+// test-only: the weighted add of pass 1 on scores the caller supplies (f32 [n,P,P,2] on the device), all n tiles in one launch
+extern "C" int srh_op_scene_fuse_window(srh_ctx* c, const float* scores, int n, int P, const int32_t* tile_xy, const float* profile,
+                                        float* canvas_kp, float* canvas_road, int H, int W, void* stream) {
+    if (!c || !scores || !tile_xy || !profile || !canvas_kp || !canvas_road)
+        return fail(c, SRH_ERR_BAD_ARG, "srh_op_scene_fuse_window: null argument");
+    if (n < 0 || !tile_size_ok(P) || H < P || W < P || !scene_dims_ok(H, W)) return fail(c, SRH_ERR_BAD_ARG, "srh_op_scene_fuse_window: bad sizes");
+    if (n == 0) return 0;
+    hipSetDevice(c->device);
+    hipStream_t s = (hipStream_t)stream;
+    TRYK(c, "scene_add_window", 0, (double)n * P * P * 8 * 3, s,
+         launch_scene_add_window(scores, n, P, tile_xy, profile, canvas_kp, canvas_road, H, W, s));
+    return 0;
 }
 
 // ---- op level ------------------------------------------------------------------------------------------------

@@ -671,6 +671,60 @@ def scene_tiles(shape, config, valid=None, net=None):
     return [infos[i] for i in select_tiles(counts, config.PATCH_SIZE, frac)]
 
 
+# ---- window-weighted fusion of overlapping tiles (FUSE_WINDOW) ----------------------------------------------------------------------
+FUSE_WINDOW_RANGE = (2.0 ** -20, 2.0 ** 20)      # products of two values and sums over tiles stay normal f32 numbers
+FUSE_WINDOW_NAMES = ("uniform", "hann", "triangle")
+
+
+def fuse_window(config):
+    """config.FUSE_WINDOW (extension key) as the 1-D profile w1, float32 [PATCH_SIZE] (numpy), or None for the uniform
+    mean of the reference (key absent, None or 'uniform': nothing changes).  'hann': sin^2(pi (i + 0.5) / P); 'triangle':
+    min(i + 0.5, P - i - 0.5) * 2 / P; a sequence of exactly P numbers: taken as given.  Computed in float64, rounded once to f32.
+    A tile's weight at a pixel is w1[x - x0] * w1[y - y0].  ValueError — before the device is touched — for an unknown name, a wrong
+    length, and a value that is not finite or not inside [2^-20, 2^20] (so zero and negative values too)."""
+    v = config.FUSE_WINDOW
+    if _absent(v):
+        return None
+    P = int(config.PATCH_SIZE)
+    if isinstance(v, str):
+        name = v.strip().lower()
+        if name == "uniform":
+            return None
+        i = np.arange(P, dtype=np.float64)
+        if name == "hann":
+            w = np.sin(np.pi * (i + 0.5) / P) ** 2
+        elif name == "triangle":
+            w = np.minimum(i + 0.5, P - i - 0.5) * 2.0 / P
+        else:
+            raise ValueError(f"FUSE_WINDOW must be one of {FUSE_WINDOW_NAMES} or a sequence of PATCH_SIZE = {P} numbers, got {v!r}")
+    else:
+        if not isinstance(v, (list, tuple, np.ndarray)):
+            raise ValueError(f"FUSE_WINDOW must be one of {FUSE_WINDOW_NAMES} or a sequence of PATCH_SIZE = {P} numbers, got {v!r}")
+        try:
+            w = np.asarray(v)
+            numeric = w.dtype.kind in "iuf"
+            w = w.astype(np.float64) if numeric else None
+        except (TypeError, ValueError):
+            w = None
+        if w is None:
+            raise ValueError("FUSE_WINDOW: a profile must hold plain numbers")
+        if w.shape != (P,):
+            raise ValueError(f"FUSE_WINDOW: a profile must have exactly PATCH_SIZE = {P} values, got shape {tuple(w.shape)}")
+    lo, hi = FUSE_WINDOW_RANGE
+    with np.errstate(over="ignore"):
+        w32 = w.astype(np.float32)
+    if not (np.isfinite(w).all() and np.isfinite(w32).all() and (w32 >= lo).all() and (w32 <= hi).all()):
+        bad = int(np.flatnonzero(~(np.isfinite(w32) & (w32 >= lo) & (w32 <= hi)))[0])
+        raise ValueError(f"FUSE_WINDOW: every value must be finite and inside [2^-20, 2^20]; value {bad} is {w[bad]!r}")
+    return np.ascontiguousarray(w32)
+
+
+def _window_kw(window, device):
+    """The keyword a window adds to net.scene_pass1 / net.scene_normalise: none at all for the uniform case, so that those calls get
+    exactly the arguments they always got."""
+    return {} if window is None else dict(window=torch.from_numpy(window).to(device))
+
+
 def _empty_result(H, W):
     """What a scene without a kept tile returns: no nodes, no edges, zero masks."""
     return np.zeros((0, 2), dtype=np.int64), np.zeros((0, 2), dtype=np.int32), np.zeros((H, W), np.uint8), np.zeros((H, W), np.uint8)
@@ -681,6 +735,7 @@ def _infer_one_img(net, img, config, device=None, valid=None):
     img, infos, all_xy = _scene_plan(img, config)
     if valid is not None:
         valid, min_frac, fill = _valid_plan(valid, img.shape[:2], config)
+    window = fuse_window(config)
     bs = int(config.INFER_BATCH_SIZE)
     world = torch.distributed.get_world_size() if D.is_distributed() else 1
     rank = torch.distributed.get_rank() if D.is_distributed() else 0
@@ -715,14 +770,15 @@ def _infer_one_img(net, img, config, device=None, valid=None):
         scene = net.scene_fill_invalid(scene, valid_d, fill)
         lap("nodata fill")
     lo, hi = shard_tiles(len(infos), world, rank)
-    kp_c, road_c, emb = net.scene_pass1(scene, xy_dev[lo:hi], bs)      # an empty shard (world > n_tiles) returns zero canvases
+    wkw = _window_kw(window, device)                   # FUSE_WINDOW: the window applies to the kept list; uniform: no argument at all
+    kp_c, road_c, emb = net.scene_pass1(scene, xy_dev[lo:hi], bs, **wkw)      # an empty shard (world > n_tiles) returns zero canvases
     lap("pass 1 (GPU)")
     D.reduce_canvases(kp_c, road_c, dst=0, bands=D.tile_bands(all_xy, int(config.PATCH_SIZE), world) if world > 1 else None)
     graph_points = None
     kp_mask = road_mask = None
     if rank == 0:
-        kp_u8, road_u8 = net.scene_normalise(kp_c, road_c, xy_dev) if valid_d is None else \
-            net.scene_normalise(kp_c, road_c, xy_dev, valid=valid_d)
+        kp_u8, road_u8 = net.scene_normalise(kp_c, road_c, xy_dev, **wkw) if valid_d is None else \
+            net.scene_normalise(kp_c, road_c, xy_dev, valid=valid_d, **wkw)
         kp_mask, road_mask = kp_u8.cpu().numpy(), road_u8.cpu().numpy()
         _poll_finite(net, device)                      # the masks are on the host, so every LayerNorm pass of pass 1 has reported
         lap("normalise + mask D2H")
@@ -861,6 +917,7 @@ def infer_imgs(net, imgs, config, device=None, tile_sharded=None, pipelined=None
     A masked scene's tile selection — mask upload, count kernel, n int32 back, one host wait — is issued on the upload lane; like every
     upload there it starts after the work the compute stream holds at that moment (the previous scene's pass 2)."""
     neighbor_queries(config)                          # fail before any scene touches the device
+    fuse_window(config)
     valids = _valid_iter(valids)
     if D.is_distributed() if tile_sharded is None else tile_sharded:
         if pipelined is None:
@@ -875,6 +932,7 @@ def infer_imgs(net, imgs, config, device=None, tile_sharded=None, pipelined=None
     lane = _Lane(device)
     pools = [_StagingPool(device), _StagingPool(device)]
     bs, K = int(config.INFER_BATCH_SIZE), neighbor_queries(config)
+    wkw = _window_kw(fuse_window(config), device)      # FUSE_WINDOW: one upload for the whole sequence
     import os
     import time
     prof = os.environ.get("SRH_PROFILE_HOST") == "1"      # tuning aid: host wall time of each step (no device synchronisation)
@@ -913,10 +971,10 @@ def infer_imgs(net, imgs, config, device=None, tile_sharded=None, pipelined=None
         if prof and lane.cuda:
             job.t = [torch.cuda.Event(enable_timing=True) for _ in range(5)]
             job.t[0].record()
-        kp_c, road_c, job.emb = net.scene_pass1(scene, xy_dev, bs)
+        kp_c, road_c, job.emb = net.scene_pass1(scene, xy_dev, bs, **wkw)
         lap("queue pass 1")
-        kp_u8, road_u8 = net.scene_normalise(kp_c, road_c, xy_dev) if valid_d is None else \
-            net.scene_normalise(kp_c, road_c, xy_dev, valid=valid_d)
+        kp_u8, road_u8 = net.scene_normalise(kp_c, road_c, xy_dev, **wkw) if valid_d is None else \
+            net.scene_normalise(kp_c, road_c, xy_dev, valid=valid_d, **wkw)
         if prof and lane.cuda:
             job.t[1].record()
         job.masks, job.e1 = lane.download(pool, "mask", [kp_u8, road_u8])
@@ -1039,6 +1097,9 @@ def _infer_imgs_tile_sharded(net, imgs, config, device=None, stats=None, valids=
     rank = torch.distributed.get_rank() if D.is_distributed() else 0
     bs = int(config.INFER_BATCH_SIZE)
     cuda = device.type == "cuda"
+    # FUSE_WINDOW: every rank weights its own chunk; the bands of the reduce are unchanged, and rank 0 normalises with the full kept
+    # list — the weight sum follows from the list alone, so there is no collective for it
+    wkw = _window_kw(fuse_window(config), device)
     stats = stats if stats is not None else {}
     for k in ("pass1_queue_ms", "points_host_ms", "pass2_ms", "merge_host_ms", "canvas_bytes", "points_bytes", "votes_bytes", "scenes"):
         stats.setdefault(k, 0.0)
@@ -1067,7 +1128,7 @@ def _infer_imgs_tile_sharded(net, imgs, config, device=None, stats=None, valids=
                 scene = scene.clone()
             scene = net.scene_fill_invalid(scene, valid_d, fill)
         job.lo, job.hi = shard_tiles(len(job.infos), world, rank)
-        kp_c, road_c, job.emb = net.scene_pass1(scene, job.xy_dev[job.lo:job.hi], bs)
+        kp_c, road_c, job.emb = net.scene_pass1(scene, job.xy_dev[job.lo:job.hi], bs, **wkw)
         bands = D.tile_bands(job.all_xy, int(config.PATCH_SIZE), world) if world > 1 else None
         D.reduce_canvases(kp_c, road_c, dst=0, bands=bands)
         if bands is not None:
@@ -1077,8 +1138,8 @@ def _infer_imgs_tile_sharded(net, imgs, config, device=None, stats=None, valids=
             stats["canvas_bytes"] += D.canvas_bytes(bands, rows) if rank == 0 else 2 * 4 * rows * max(0, x1 - x0)
         job.masks = job.e1 = None
         if rank == 0:
-            kp_u8, road_u8 = net.scene_normalise(kp_c, road_c, job.xy_dev) if valid_d is None else \
-                net.scene_normalise(kp_c, road_c, job.xy_dev, valid=valid_d)
+            kp_u8, road_u8 = net.scene_normalise(kp_c, road_c, job.xy_dev, **wkw) if valid_d is None else \
+                net.scene_normalise(kp_c, road_c, job.xy_dev, valid=valid_d, **wkw)
             if cuda:       # asynchronous download behind the scene's own kernels: the host does not wait here
                 job.masks = [torch.empty(t.shape, dtype=t.dtype, pin_memory=True) for t in (kp_u8, road_u8)]
                 for h, t in zip(job.masks, (kp_u8, road_u8)):
@@ -1261,9 +1322,15 @@ def main(argv=None):
                     help="(extension, multi-GPU runs under torchrun) scenes: every rank takes whole scenes, no data-path collective "
                          "(throughput); tiles: the tiles of every scene are split over the ranks, scene by scene (latency of one scene); "
                          "tiles-pipelined: the same with scene i+1's pass 1 queued before scene i's host stages (opt-in: exercised on gloo only)")
+    ap.add_argument("--fuse-window", default=None, metavar="NAME", choices=FUSE_WINDOW_NAMES,
+                    help="(extension) how overlapping tiles are fused, overriding the config's FUSE_WINDOW: uniform (the reference's mean), "
+                         "hann or triangle (centre-weighted: tile borders count less)")
     args = ap.parse_args(argv)
     config = load_config(args.config)
+    if args.fuse_window is not None:
+        config.FUSE_WINDOW = args.fuse_window
     neighbor_queries(config)                     # a K the TopoNet trunk cannot run fails here, not after the first scene's pass 1
+    fuse_window(config)                          # and so does a FUSE_WINDOW that cannot be used
     device = torch.device("cuda") if args.device == "cuda" else torch.device(args.device)
     torch.set_num_threads(max(1, min(torch.get_num_threads(), usable_cpus() // max(1, int(os.environ.get("WORLD_SIZE", "1"))))))   # this rank's share of the container's CPU quota (hostcpu.py)
     _numpy_hugepages(False)                      # for the whole run: image decoding and output encoding allocate beside the GPU too (_host_quiet)

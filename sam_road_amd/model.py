@@ -499,11 +499,13 @@ class SAMRoad(nn.Module):
 
     # ---- scene level (pass 1 of infer_one_img: tile batcher + model + mask fusion) -------------------------
     @torch.no_grad()
-    def scene_pass1(self, scene_u8, tile_xy, batch_size, canvas_kp=None, canvas_road=None):
+    def scene_pass1(self, scene_u8, tile_xy, batch_size, canvas_kp=None, canvas_road=None, window=None):
         """scene_u8 [H,W,3] uint8 on the GPU (H and W independent, each >= PATCH_SIZE), tile_xy int32 [n,2] (x0,y0) on the
         GPU, every tile inside the scene.  Runs the tiles in batches through the encoder + decoder and accumulates the two
         mask canvases [H,W] in the reference's sequential order (inferencer.py:87-104).  Returns (canvas_kp, canvas_road,
-        embeddings[n,256,h,w])."""
+        embeddings[n,256,h,w]).  window (f32 [PATCH_SIZE] on the GPU, inferencer.fuse_window): every tile's scores enter the canvases
+        weighted by window[lx] * window[ly] (srh_scene_pass1_window_hw); None: the call and the kernels of a scene
+        without a window."""
         dev = scene_u8.device
         ctx, wh = self._weights(dev)
         assert scene_u8.dtype == torch.uint8 and scene_u8.dim() == 3 and scene_u8.shape[2] == 3
@@ -521,6 +523,14 @@ class SAMRoad(nn.Module):
         emb = torch.empty((n, h, h, 256), dtype=torch.float32, device=dev)
         if n == 0:                                   # a rank without tiles (world_size > tile count): nothing to add
             return canvas_kp, canvas_road, emb.permute(0, 3, 1, 2)
+        if window is not None:
+            window = self._window_f32(window, dev)
+            with torch.cuda.device(dev):
+                ctx.check(ctx.lib.srh_scene_pass1_window_hw(ctx.handle, wh, scene_u8.data_ptr(), H, W, tile_xy.data_ptr(), n,
+                                                            int(batch_size), window.data_ptr(), canvas_kp.data_ptr(),
+                                                            canvas_road.data_ptr(), emb.data_ptr(), self._stream(dev)),
+                          "srh_scene_pass1_window_hw")
+            return canvas_kp, canvas_road, emb.permute(0, 3, 1, 2)
         with torch.cuda.device(dev):
             ctx.check(ctx.lib.srh_scene_pass1_hw(ctx.handle, wh, scene_u8.data_ptr(), H, W, tile_xy.data_ptr(), n,
                                                  int(batch_size), canvas_kp.data_ptr(), canvas_road.data_ptr(),
@@ -528,16 +538,28 @@ class SAMRoad(nn.Module):
         return canvas_kp, canvas_road, emb.permute(0, 3, 1, 2)
 
     @torch.no_grad()
-    def scene_normalise(self, canvas_kp, canvas_road, tile_xy, valid=None):
+    def scene_normalise(self, canvas_kp, canvas_road, tile_xy, valid=None, window=None):
         """(canvas / coverage count) * 255 -> uint8 masks [H,W] (inferencer.py:106-110); tile_xy = ALL tiles.  valid (u8 [H,W] on the
         GPU, non-zero = valid pixel): the masks are also 0 on every invalid pixel (srh_scene_normalise_valid_hw); None: the call and
-        the kernels of a scene without a mask."""
+        the kernels of a scene without a mask.  window (f32 [PATCH_SIZE] on the GPU, the one pass 1 ran with): the divisor is the
+        sum of the tiles' weights instead of their count (srh_scene_normalise_window_hw, with or without valid); None: the calls above."""
         dev = canvas_kp.device
         ctx, _ = self._weights(dev)
         H, W = int(canvas_kp.shape[0]), int(canvas_kp.shape[1])
         tile_xy = tile_xy.to(device=dev, dtype=torch.int32).contiguous()
         kp = torch.empty((H, W), dtype=torch.uint8, device=dev)
         road = torch.empty((H, W), dtype=torch.uint8, device=dev)
+        if window is not None:
+            window = self._window_f32(window, dev)
+            if valid is not None:
+                valid = self._valid_u8(valid, H, W, dev)
+            with torch.cuda.device(dev):
+                ctx.check(ctx.lib.srh_scene_normalise_window_hw(ctx.handle, canvas_kp.data_ptr(), canvas_road.data_ptr(), H, W,
+                                                                tile_xy.data_ptr(), tile_xy.shape[0], self.image_size, window.data_ptr(),
+                                                                valid.data_ptr() if valid is not None else None,
+                                                                kp.data_ptr(), road.data_ptr(), self._stream(dev)),
+                          "srh_scene_normalise_window_hw")
+            return kp, road
         if valid is not None:
             valid = self._valid_u8(valid, H, W, dev)
             with torch.cuda.device(dev):
@@ -552,6 +574,31 @@ class SAMRoad(nn.Module):
                                                      kp.data_ptr(), road.data_ptr(), self._stream(dev)),
                       "srh_scene_normalise_hw")
         return kp, road
+
+    def _window_f32(self, window, dev):
+        if window.device != dev or window.dtype != torch.float32 or tuple(window.shape) != (self.image_size,):
+            raise ValueError(f"window must be a float32 [{self.image_size}] tensor on {dev}, got {window.dtype} {tuple(window.shape)} on {window.device}")
+        return window.contiguous()
+
+    @torch.no_grad()
+    def op_scene_fuse_window(self, scores, tile_xy, window, canvas_kp, canvas_road):
+        """Test-only (srh_op_scene_fuse_window): the weighted add of pass 1 on given scores f32 [n,P,P,2], IN PLACE on the f32 [H,W]
+        canvases; tile_xy int32 [n,2] (x0,y0), every tile inside the scene."""
+        dev = canvas_kp.device
+        ctx, _ = self._weights(dev)
+        P, n = self.image_size, int(tile_xy.shape[0])
+        H, W = int(canvas_kp.shape[0]), int(canvas_kp.shape[1])
+        window = self._window_f32(window, dev)
+        tile_xy = tile_xy.to(device=dev, dtype=torch.int32).contiguous()
+        ok = lambda t, shape: t.device == dev and t.dtype == torch.float32 and tuple(t.shape) == shape and t.is_contiguous()
+        if not (ok(scores, (n, P, P, 2)) and ok(canvas_kp, (H, W)) and ok(canvas_road, (H, W))):
+            raise ValueError(f"scores must be contiguous float32 [{n},{P},{P},2] and the canvases contiguous float32 [{H},{W}] on {dev}")
+        if n:
+            with torch.cuda.device(dev):
+                ctx.check(ctx.lib.srh_op_scene_fuse_window(ctx.handle, scores.data_ptr(), n, P, tile_xy.data_ptr(), window.data_ptr(),
+                                                           canvas_kp.data_ptr(), canvas_road.data_ptr(), H, W, self._stream(dev)),
+                          "srh_op_scene_fuse_window")
+        return canvas_kp, canvas_road
 
     # ---- scene level, validity mask (nodata): which tiles hold data, nodata neutralised before the crop ------------------------
     @staticmethod
