@@ -211,6 +211,29 @@ int srh_scene_normalise_window_hw(srh_ctx* ctx, const float* canvas_kp, const fl
 int srh_op_scene_fuse_window(srh_ctx* ctx, const float* scores, int n, int P, const int32_t* tile_xy, const float* profile,
                              float* canvas_kp, float* canvas_road, int H, int W, void* stream);
 
+/* Test-time augmentation over the 8 orientations of a tile (config key TTA; an extension).  Additive entries; the ABI
+ * number stays 11 because nothing existing changes, and a scene without TTA calls none of them.  An orientation code acts on a P x P
+ * tile T[row, col]:  0 id  1 flip_h T[:, ::-1]  2 flip_v T[::-1, :]  3 rot180  4 transpose  5 rot90 (np.rot90(T, 1))  6 rot270
+ * (np.rot90(T, 3))  7 anti_transpose T[::-1, ::-1] transposed.
+ *
+ * srh_scene_pass1_tta_hw: srh_scene_pass1_hw (profile == NULL) or srh_scene_pass1_window_hw (profile = device f32 [P]) run once per
+ *   orientation, in the order of orients (HOST array of k codes), each time over the WHOLE tile list: the crop of a tile is oriented,
+ *   encoded and decoded, its score tile is brought back with the inverse orientation and added by the same add kernel, so the
+ *   summation order is (orientation, tile) and independent of B.  embeddings_all receives the embeddings of orientation id, bit for bit
+ *   those of a call without TTA; the others go to a workspace of the context.  The canvases are to be normalised with the tile list
+ *   repeated k times.  The preconditions and SRH_ERR_BAD_ARG cases of srh_scene_pass1_hw, and SRH_ERR_BAD_ARG (nothing is launched)
+ *   unless 1 <= k <= 8, every code <= 7, no code twice and orients[0] == 0.  k == 1 makes exactly the launches of the entry it extends.
+ * srh_op_patch_im2col (test-only): the GEMM A matrix f16 [n (P/16)^2, 768] of pass 1's crop + normalise + im2col for n tiles of a u8
+ *   scene in one orientation; orient 0 is the launch of every scene without TTA.  P a tile size, H, W >= P, n <= 65535.
+ * srh_op_scores_unorient (test-only): scores f32 [n,P,P,2] of oriented tiles -> the scene frame, a permutation of bit patterns;
+ *   scores_out must not be scores_in.  orient 0 copies. */
+int srh_scene_pass1_tta_hw(srh_ctx* ctx, const srh_weights* w, const uint8_t* scene, int H, int W, const int32_t* tile_xy,
+                           int n_tiles, int B, const uint8_t* orients, int k, const float* profile, float* canvas_kp,
+                           float* canvas_road, float* embeddings_all, void* stream);
+int srh_op_patch_im2col(srh_ctx* ctx, const uint8_t* scene_u8, int H, int W, const int32_t* tile_xy, int n, int P, int orient,
+                        void* out_f16, void* stream);
+int srh_op_scores_unorient(srh_ctx* ctx, const float* scores_in, int n, int P, int orient, float* scores_out, void* stream);
+
 /* op level (used by the parity tests to localise a failure; same kernels as above) ----------------- */
 
 /* out = act(A[M,K] W[N,K]^T + bias) (+resid); A,W fp16; N%128==0, K%64==0. act: 0/1 GELU/2 ReLU. */

@@ -59,6 +59,9 @@ SYMBOLS = {
     "srh_scene_pass1_window_hw": (_I, [_P, _P, _P, _I, _I, _P, _I, _I, _P, _P, _P, _P, _P]),
     "srh_scene_normalise_window_hw": (_I, [_P, _P, _P, _I, _I, _P, _I, _I, _P, _P, _P, _P, _P]),
     "srh_op_scene_fuse_window": (_I, [_P, _P, _I, _I, _P, _P, _P, _P, _I, _I, _P]),
+    "srh_scene_pass1_tta_hw": (_I, [_P, _P, _P, _I, _I, _P, _I, _I, _P, _I, _P, _P, _P, _P, _P]),
+    "srh_op_patch_im2col": (_I, [_P, _P, _I, _I, _P, _I, _I, _I, _P, _P]),
+    "srh_op_scores_unorient": (_I, [_P, _P, _I, _I, _I, _P, _P]),
     "srh_op_gemm": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P]),
     "srh_op_gemm_ex": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _I, _P]),
     "srh_ctx_device_bytes": (C.c_size_t, [_P]),

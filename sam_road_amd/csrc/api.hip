@@ -45,6 +45,7 @@ struct srh_ctx {
     // encoder / decoder workspace
     DevBuf a0, x, xn16, delta16, delta16b, qkv16, attn16, hid16, n1, n1_16, n2, emb16;
     DevBuf scores_ws, emb_ws, counter, split_ws;
+    DevBuf tta_scores_ws;        // TTA: the scores of an oriented batch before they are brought back to the scene frame (emb_ws: its embeddings)
     ZTileTables ztab;            // gemm_z192's tile-order tables (one bounded slab, freed with the context)
     // non-finite sentinel: NF_SLOTS flags in host-mapped pinned memory (nf_host; nf_dev = the same bytes as the device sees them).
     // The LayerNorm passes set flag `tag` when a row's variance is not finite (NormParams::nf) — an fp16 overflow upstream.  Nothing is
@@ -188,7 +189,7 @@ extern "C" void srh_ctx_destroy(srh_ctx* c) {
     if (!c) return;
     hipSetDevice(c->device);
     DevBuf* bufs[] = {&c->a0, &c->x, &c->xn16, &c->delta16, &c->delta16b, &c->qkv16, &c->attn16, &c->hid16, &c->n1, &c->n1_16, &c->n2,
-                      &c->emb16, &c->scores_ws, &c->emb_ws, &c->counter, &c->split_ws,
+                      &c->emb16, &c->scores_ws, &c->emb_ws, &c->counter, &c->split_ws, &c->tta_scores_ws,
                       &c->sd_keys, &c->sd_keys16, &c->sd_k16, &c->sd_v16, &c->sd_a16, &c->sd_u0, &c->sd_u0_16, &c->sd_u1_16,
                       &c->sd_low, &c->sd_tok,
                       &c->t_feat16, &c->t_pf16, &c->t_pair16};
@@ -202,7 +203,7 @@ extern "C" void srh_ctx_destroy(srh_ctx* c) {
 extern "C" size_t srh_ctx_device_bytes(const srh_ctx* c) {
     if (!c) return 0;
     const DevBuf* bufs[] = {&c->a0, &c->x, &c->xn16, &c->delta16, &c->delta16b, &c->qkv16, &c->attn16, &c->hid16, &c->n1, &c->n1_16, &c->n2,
-                            &c->emb16, &c->scores_ws, &c->emb_ws, &c->counter, &c->split_ws,
+                            &c->emb16, &c->scores_ws, &c->emb_ws, &c->counter, &c->split_ws, &c->tta_scores_ws,
                             &c->sd_keys, &c->sd_keys16, &c->sd_k16, &c->sd_v16, &c->sd_a16, &c->sd_u0, &c->sd_u0_16, &c->sd_u1_16,
                             &c->sd_low, &c->sd_tok, &c->t_feat16, &c->t_pf16, &c->t_pair16};
     size_t n = c->ztab.device_bytes();
@@ -803,11 +804,14 @@ static int sam_decode(srh_ctx* c, const srh_weights* w, int B, const float* emb,
 }
 
 static int encode_batch(srh_ctx* c, const srh_weights* w, PatchParams pp, int B, float* logits, float* scores,
-                        float* emb, hipStream_t s) {
+                        float* emb, hipStream_t s, int orient = 0, int scene_H = 0) {
     const int S = w->S, D = w->D, heads = w->heads, hd = w->hd;
     const int T = B * S * S;
     TRY(ensure_encoder_ws(c, w, B));
     pp.B = B; pp.P = w->cfg.patch_size; pp.out = c->a0.as<f16>();
+    if (orient)          // TTA (scene_tta.hip): the crop is read through the orientation; everything after it is the same calls
+        TRYK(c, "patch_im2col_oriented", 0, (double)T * 768 * 3, s, launch_patch_im2col_oriented(pp, scene_H, orient, s));
+    else
     TRYK(c, "patch_im2col", 0, (double)T * 768 * (pp.src_is_u8 ? 3 : 6), s, launch_patch_im2col(pp, s));
     // Residual stream: x stays fp32.  Where the persistent z192 GEMM applies (gemm_z192.hip: fp16 output only), proj / fc2
     // write their branch output (bias included) as fp16 into delta16 and the NEXT LayerNorm pass folds "x += delta" into
@@ -1066,7 +1070,8 @@ static bool scene_dims_ok(int H, int W) { return H > 0 && W > 0 && (long long)H 
 
 static int scene_pass1_impl(srh_ctx* c, const char* who, const srh_weights* w, const uint8_t* scene, int H, int W,
                             const int32_t* tile_xy, int n_tiles, int B, float* canvas_kp, float* canvas_road,
-                            float* embeddings_all, void* stream, bool has_window = false, const float* profile = nullptr) {
+                            float* embeddings_all, void* stream, bool has_window = false, const float* profile = nullptr,
+                            const uint8_t* orients = nullptr, int k = 1) {
     if (!c || !w || !scene || !tile_xy || !canvas_kp || !canvas_road || !embeddings_all || (has_window && !profile))
         return fail(c, SRH_ERR_BAD_ARG, std::string(who) + ": null argument");
     if (n_tiles < 0 || B <= 0 || H < w->cfg.patch_size || W < w->cfg.patch_size || !scene_dims_ok(H, W))
@@ -1077,17 +1082,32 @@ static int scene_pass1_impl(srh_ctx* c, const char* who, const srh_weights* w, c
     const int P = w->cfg.patch_size;
     if (c->scores_ws.ensure((size_t)B * P * P * 2 * 4)) return fail(c, SRH_ERR_HIP, "scores workspace allocation failed");
     const size_t emb_per_tile = (size_t)w->S * w->S * 256;
-    for (int off = 0; off < n_tiles; off += B) {
-        const int nb = std::min(B, n_tiles - off);
-        PatchParams pp;
-        pp.src = scene; pp.src_is_u8 = 1; pp.scene_W = W; pp.tile_xy = tile_xy + 2 * off;
-        TRY(encode_batch(c, w, pp, nb, nullptr, c->scores_ws.as<float>(), embeddings_all + emb_per_tile * off, s));
-        if (has_window)      // FUSE_WINDOW (scene_window.hip): only this launch differs, the encoder and decoder are the same calls
-            TRYK(c, "scene_add_window", 0, (double)nb * P * P * 8 * 3, s,
-                 launch_scene_add_window(c->scores_ws.as<float>(), nb, P, tile_xy + 2 * off, profile, canvas_kp, canvas_road, H, W, s));
-        else
-        TRYK(c, "scene_add", 0, (double)nb * P * P * 8 * 3, s,
-             launch_scene_add(c->scores_ws.as<float>(), nb, P, tile_xy + 2 * off, canvas_kp, canvas_road, H, W, s));
+    if (k > 1 && n_tiles > 0) {       // TTA: an oriented batch's scores before the un-orient, and its embeddings, which nobody reads
+        const size_t nb_max = (size_t)std::min(B, n_tiles);
+        if (c->tta_scores_ws.ensure(nb_max * P * P * 2 * 4)) return fail(c, SRH_ERR_HIP, "TTA scores workspace allocation failed");
+        if (c->emb_ws.ensure(nb_max * emb_per_tile * 4)) return fail(c, SRH_ERR_HIP, "TTA embeddings workspace allocation failed");
+    }
+    for (int j = 0; j < k; ++j) {     // summation order (orientation, tile); k == 1: the loop of every earlier ABI
+        const int orient = orients ? orients[j] : 0;
+        for (int off = 0; off < n_tiles; off += B) {
+            const int nb = std::min(B, n_tiles - off);
+            PatchParams pp;
+            pp.src = scene; pp.src_is_u8 = 1; pp.scene_W = W; pp.tile_xy = tile_xy + 2 * off;
+            const float* scores = c->scores_ws.as<float>();
+            if (orient) {             // oriented crop -> the same encoder and decoder -> scores back to the scene frame (scene_tta.hip)
+                TRY(encode_batch(c, w, pp, nb, nullptr, c->tta_scores_ws.as<float>(), c->emb_ws.as<float>(), s, orient, H));
+                TRYK(c, "scores_unorient", 0, (double)nb * P * P * 8 * 2, s,
+                     launch_scores_unorient(c->tta_scores_ws.as<float>(), nb, P, orient, c->scores_ws.as<float>(), s));
+            } else {
+                TRY(encode_batch(c, w, pp, nb, nullptr, c->scores_ws.as<float>(), embeddings_all + emb_per_tile * off, s));
+            }
+            if (has_window)      // FUSE_WINDOW (scene_window.hip): only this launch differs, the encoder and decoder are the same calls
+                TRYK(c, "scene_add_window", 0, (double)nb * P * P * 8 * 3, s,
+                     launch_scene_add_window(scores, nb, P, tile_xy + 2 * off, profile, canvas_kp, canvas_road, H, W, s));
+            else
+                TRYK(c, "scene_add", 0, (double)nb * P * P * 8 * 3, s,
+                     launch_scene_add(scores, nb, P, tile_xy + 2 * off, canvas_kp, canvas_road, H, W, s));
+        }
     }
     return 0;
 }
@@ -1202,6 +1222,55 @@ extern "C" int srh_op_scene_fuse_window(srh_ctx* c, const float* scores, int n, 
     hipStream_t s = (hipStream_t)stream;
     TRYK(c, "scene_add_window", 0, (double)n * P * P * 8 * 3, s,
          launch_scene_add_window(scores, n, P, tile_xy, profile, canvas_kp, canvas_road, H, W, s));
+    return 0;
+}
+
+// ---- scene level, test-time augmentation over tile orientations (kernels in scene_tta.hip, behaviour in DESIGN.md §6f) ----------------
+extern "C" int srh_scene_pass1_tta_hw(srh_ctx* c, const srh_weights* w, const uint8_t* scene, int H, int W, const int32_t* tile_xy,
+                                      int n_tiles, int B, const uint8_t* orients, int k, const float* profile, float* canvas_kp,
+                                      float* canvas_road, float* embeddings_all, void* stream) {
+    if (!orients) return fail(c, SRH_ERR_BAD_ARG, "srh_scene_pass1_tta_hw: null argument");
+    if (k < 1 || k > 8) return fail(c, SRH_ERR_BAD_ARG, "srh_scene_pass1_tta_hw: 1 to 8 orientations");
+    unsigned seen = 0;
+    for (int j = 0; j < k; ++j) {
+        if (orients[j] > 7) return fail(c, SRH_ERR_BAD_ARG, "srh_scene_pass1_tta_hw: an orientation code is 0 to 7");
+        if (seen & (1u << orients[j])) return fail(c, SRH_ERR_BAD_ARG, "srh_scene_pass1_tta_hw: an orientation is listed twice");
+        seen |= 1u << orients[j];
+    }
+    if (orients[0] != 0) return fail(c, SRH_ERR_BAD_ARG, "srh_scene_pass1_tta_hw: the first orientation must be id (0): its embeddings feed pass 2");
+    return scene_pass1_impl(c, "srh_scene_pass1_tta_hw", w, scene, H, W, tile_xy, n_tiles, B, canvas_kp, canvas_road, embeddings_all, stream,
+                            profile != nullptr, profile, orients, k);
+}
+
+// test-only: the A matrix of pass 1's crop for n tiles of size P in one orientation (0: the launch of every scene without TTA)
+extern "C" int srh_op_patch_im2col(srh_ctx* c, const uint8_t* scene, int H, int W, const int32_t* tile_xy, int n, int P, int orient,
+                                   void* out_f16, void* stream) {
+    if (!c || !scene || !tile_xy || !out_f16) return fail(c, SRH_ERR_BAD_ARG, "srh_op_patch_im2col: null argument");
+    if (n < 0 || n > 65535 || !tile_size_ok(P) || H < P || W < P || !scene_dims_ok(H, W) || orient < 0 || orient > 7)
+        return fail(c, SRH_ERR_BAD_ARG, "srh_op_patch_im2col: bad sizes or orientation");
+    if (n == 0) return 0;
+    hipSetDevice(c->device);
+    hipStream_t s = (hipStream_t)stream;
+    PatchParams pp;
+    pp.src = scene; pp.src_is_u8 = 1; pp.scene_W = W; pp.tile_xy = tile_xy; pp.B = n; pp.P = P; pp.out = (f16*)out_f16;
+    const double bytes = (double)n * P * P * 3 * 3;
+    if (orient) TRYK(c, "patch_im2col_oriented", 0, bytes, s, launch_patch_im2col_oriented(pp, H, orient, s));
+    else TRYK(c, "patch_im2col", 0, bytes, s, launch_patch_im2col(pp, s));
+    return 0;
+}
+
+// test-only: scores f32 [n,P,P,2] of oriented tiles -> the scene frame (orient 0: a plain copy; pass 1 launches nothing for id)
+extern "C" int srh_op_scores_unorient(srh_ctx* c, const float* scores_in, int n, int P, int orient, float* scores_out, void* stream) {
+    if (!c || !scores_in || !scores_out || scores_in == scores_out) return fail(c, SRH_ERR_BAD_ARG, "srh_op_scores_unorient: null or aliased argument");
+    if (n < 0 || n > 65535 || !tile_size_ok(P) || orient < 0 || orient > 7) return fail(c, SRH_ERR_BAD_ARG, "srh_op_scores_unorient: bad sizes or orientation");
+    if (n == 0) return 0;
+    hipSetDevice(c->device);
+    hipStream_t s = (hipStream_t)stream;
+    if (orient == 0) {
+        const hipError_t e = hipMemcpyAsync(scores_out, scores_in, (size_t)n * P * P * 8, hipMemcpyDeviceToDevice, s);
+        return e == hipSuccess ? 0 : hip_fail(c, e, "srh_op_scores_unorient");
+    }
+    TRYK(c, "scores_unorient", 0, (double)n * P * P * 8 * 2, s, launch_scores_unorient(scores_in, n, P, orient, scores_out, s));
     return 0;
 }
 

@@ -655,20 +655,22 @@ def _tile_counts(net, valid_d, xy_dev):
 def scene_tiles(shape, config, valid=None, net=None):
     """The tiles infer_one_img runs for a scene of `shape` = (H, W[, 3]): the list of (0, (x0, y0), (x1, y1)) in the reference's
     x-outer / y-inner order.  With `valid` (see infer_one_img) only the kept tiles, selected exactly as infer_one_img selects them: the
-    counts come from `net.scene_tile_valid` on the model's device, so `net` is required then (there is no host fallback)."""
+    counts come from `net.scene_tile_valid` on the model's device, so `net` is required then (there is no host fallback).  The list is
+    a TilePlan: its `orientations` are the names of config.TTA (['id'] without the key) — every tile of the list runs once per name."""
     neighbor_queries(config)
     if len(shape) not in (2, 3) or (len(shape) == 3 and shape[2] != 3):
         raise ValueError(f"shape must be (H, W) or (H, W, 3), got {tuple(shape)}")
     H, W = int(shape[0]), int(shape[1])
+    orientations = tta_plan(config)[0]
     infos, all_xy = _tile_plan(H, W, config)
     if valid is None:
-        return infos
+        return TilePlan(infos, orientations)
     v8, frac, _ = _valid_plan(valid, (H, W), config)
     if net is None:
         raise ValueError("scene_tiles needs the model (net=) to count valid pixels on the device")
     device = next(net.parameters()).device
     counts = _tile_counts(net, torch.from_numpy(v8).to(device), torch.as_tensor(all_xy).to(device))
-    return [infos[i] for i in select_tiles(counts, config.PATCH_SIZE, frac)]
+    return TilePlan([infos[i] for i in select_tiles(counts, config.PATCH_SIZE, frac)], orientations)
 
 
 # ---- window-weighted fusion of overlapping tiles (FUSE_WINDOW) ----------------------------------------------------------------------
@@ -725,6 +727,86 @@ def _window_kw(window, device):
     return {} if window is None else dict(window=torch.from_numpy(window).to(device))
 
 
+# ---- test-time augmentation over the 8 orientations of a tile (TTA) ------------------------------------------------------------------
+TTA_NAMES = ("id", "flip_h", "flip_v", "rot180", "transpose", "rot90", "rot270", "anti_transpose")      # the index is the code
+_TTA_INVERSE = {"rot90": "rot270", "rot270": "rot90"}                                                   # every other one is its own inverse
+
+
+def orient_tile(arr, name):
+    """A square tile arr[row, col, ...] in orientation `name`, as a view: the table of DESIGN.md §6f, which IS the definition."""
+    T = np.asarray(arr)
+    if T.ndim < 2 or T.shape[0] != T.shape[1]:
+        raise ValueError(f"a tile must be square in its first two axes, got shape {tuple(T.shape)}")
+    if name == "id":
+        return T
+    if name == "flip_h":
+        return T[:, ::-1]
+    if name == "flip_v":
+        return T[::-1, :]
+    if name == "rot180":
+        return T[::-1, ::-1]
+    if name == "transpose":
+        return T.swapaxes(0, 1)
+    if name == "rot90":
+        return np.rot90(T, 1, axes=(0, 1))
+    if name == "rot270":
+        return np.rot90(T, 3, axes=(0, 1))
+    if name == "anti_transpose":
+        return T[::-1, ::-1].swapaxes(0, 1)
+    raise ValueError(f"an orientation must be one of {TTA_NAMES}, got {name!r}")
+
+
+def unorient_tile(arr, name):
+    """The inverse of orient_tile: unorient_tile(orient_tile(T, name), name) == T."""
+    return orient_tile(arr, _TTA_INVERSE.get(name, name))
+
+
+def tta_plan(config):
+    """config.TTA (extension key) as (names, codes): the orientations every tile is run in, in config order, and their
+    codes 0..7 (the index in TTA_NAMES).  Key absent or None: (['id'], [0]) — nothing changes.  A sequence of names, or one string of
+    names separated by commas (the CLI's form).  ValueError — before the device is touched — for an unknown name, a name listed twice, a
+    first entry that is not 'id' (its embeddings feed pass 2), an empty list and more than 8 entries."""
+    v = config.TTA
+    if _absent(v):
+        return ["id"], [0]
+    if isinstance(v, str):
+        v = [t for t in v.split(",")]
+    if not isinstance(v, (list, tuple)):
+        raise ValueError(f"TTA must be a sequence of orientation names out of {TTA_NAMES}, got {v!r}")
+    if not 1 <= len(v) <= 8:
+        raise ValueError(f"TTA must list 1 to 8 orientations, got {len(v)}")
+    names = []
+    for t in v:
+        name = t.strip().lower() if isinstance(t, str) else t
+        if not isinstance(name, str) or name not in TTA_NAMES:
+            raise ValueError(f"TTA: an orientation must be one of {TTA_NAMES}, got {t!r}")
+        if name in names:
+            raise ValueError(f"TTA: orientation {name!r} is listed twice")
+        names.append(name)
+    if names[0] != "id":
+        raise ValueError(f"TTA: the first orientation must be 'id' (its embeddings feed pass 2), got {names[0]!r}")
+    return names, [TTA_NAMES.index(n) for n in names]
+
+
+class TilePlan(list):
+    """What scene_tiles returns: the list of tiles, and in `orientations` the names every one of them is run in."""
+
+    def __init__(self, infos, orientations):
+        super().__init__(infos)
+        self.orientations = list(orientations)
+
+
+def _tta_kw(codes):
+    """The keyword TTA adds to net.scene_pass1: none at all for ['id'], so that the call gets exactly the arguments it always got."""
+    return {} if len(codes) == 1 else dict(tta=list(codes))
+
+
+def _tta_list(xy_dev, codes):
+    """The tile list scene_normalise gets: repeated once per orientation (the coverage count becomes k * count, the weight sum runs
+    over k * n terms in list order: DESIGN.md §6f); the list itself for ['id']."""
+    return xy_dev if len(codes) == 1 else xy_dev.repeat(len(codes), 1)
+
+
 def _empty_result(H, W):
     """What a scene without a kept tile returns: no nodes, no edges, zero masks."""
     return np.zeros((0, 2), dtype=np.int64), np.zeros((0, 2), dtype=np.int32), np.zeros((H, W), np.uint8), np.zeros((H, W), np.uint8)
@@ -736,6 +818,7 @@ def _infer_one_img(net, img, config, device=None, valid=None):
     if valid is not None:
         valid, min_frac, fill = _valid_plan(valid, img.shape[:2], config)
     window = fuse_window(config)
+    tta = tta_plan(config)[1]
     bs = int(config.INFER_BATCH_SIZE)
     world = torch.distributed.get_world_size() if D.is_distributed() else 1
     rank = torch.distributed.get_rank() if D.is_distributed() else 0
@@ -771,14 +854,16 @@ def _infer_one_img(net, img, config, device=None, valid=None):
         lap("nodata fill")
     lo, hi = shard_tiles(len(infos), world, rank)
     wkw = _window_kw(window, device)                   # FUSE_WINDOW: the window applies to the kept list; uniform: no argument at all
-    kp_c, road_c, emb = net.scene_pass1(scene, xy_dev[lo:hi], bs, **wkw)      # an empty shard (world > n_tiles) returns zero canvases
+    # TTA: every orientation runs the kept list (selection and fill happened once, above); ['id']: no argument at all
+    kp_c, road_c, emb = net.scene_pass1(scene, xy_dev[lo:hi], bs, **wkw, **_tta_kw(tta))      # an empty shard (world > n_tiles) returns zero canvases
     lap("pass 1 (GPU)")
     D.reduce_canvases(kp_c, road_c, dst=0, bands=D.tile_bands(all_xy, int(config.PATCH_SIZE), world) if world > 1 else None)
     graph_points = None
     kp_mask = road_mask = None
     if rank == 0:
-        kp_u8, road_u8 = net.scene_normalise(kp_c, road_c, xy_dev, **wkw) if valid_d is None else \
-            net.scene_normalise(kp_c, road_c, xy_dev, valid=valid_d, **wkw)
+        xy_norm = _tta_list(xy_dev, tta)
+        kp_u8, road_u8 = net.scene_normalise(kp_c, road_c, xy_norm, **wkw) if valid_d is None else \
+            net.scene_normalise(kp_c, road_c, xy_norm, valid=valid_d, **wkw)
         kp_mask, road_mask = kp_u8.cpu().numpy(), road_u8.cpu().numpy()
         _poll_finite(net, device)                      # the masks are on the host, so every LayerNorm pass of pass 1 has reported
         lap("normalise + mask D2H")
@@ -918,6 +1003,7 @@ def infer_imgs(net, imgs, config, device=None, tile_sharded=None, pipelined=None
     upload there it starts after the work the compute stream holds at that moment (the previous scene's pass 2)."""
     neighbor_queries(config)                          # fail before any scene touches the device
     fuse_window(config)
+    tta_plan(config)
     valids = _valid_iter(valids)
     if D.is_distributed() if tile_sharded is None else tile_sharded:
         if pipelined is None:
@@ -933,6 +1019,7 @@ def infer_imgs(net, imgs, config, device=None, tile_sharded=None, pipelined=None
     pools = [_StagingPool(device), _StagingPool(device)]
     bs, K = int(config.INFER_BATCH_SIZE), neighbor_queries(config)
     wkw = _window_kw(fuse_window(config), device)      # FUSE_WINDOW: one upload for the whole sequence
+    tta = tta_plan(config)[1]
     import os
     import time
     prof = os.environ.get("SRH_PROFILE_HOST") == "1"      # tuning aid: host wall time of each step (no device synchronisation)
@@ -971,10 +1058,11 @@ def infer_imgs(net, imgs, config, device=None, tile_sharded=None, pipelined=None
         if prof and lane.cuda:
             job.t = [torch.cuda.Event(enable_timing=True) for _ in range(5)]
             job.t[0].record()
-        kp_c, road_c, job.emb = net.scene_pass1(scene, xy_dev, bs, **wkw)
+        kp_c, road_c, job.emb = net.scene_pass1(scene, xy_dev, bs, **wkw, **_tta_kw(tta))
         lap("queue pass 1")
-        kp_u8, road_u8 = net.scene_normalise(kp_c, road_c, xy_dev, **wkw) if valid_d is None else \
-            net.scene_normalise(kp_c, road_c, xy_dev, valid=valid_d, **wkw)
+        xy_norm = _tta_list(xy_dev, tta)
+        kp_u8, road_u8 = net.scene_normalise(kp_c, road_c, xy_norm, **wkw) if valid_d is None else \
+            net.scene_normalise(kp_c, road_c, xy_norm, valid=valid_d, **wkw)
         if prof and lane.cuda:
             job.t[1].record()
         job.masks, job.e1 = lane.download(pool, "mask", [kp_u8, road_u8])
@@ -1100,6 +1188,7 @@ def _infer_imgs_tile_sharded(net, imgs, config, device=None, stats=None, valids=
     # FUSE_WINDOW: every rank weights its own chunk; the bands of the reduce are unchanged, and rank 0 normalises with the full kept
     # list — the weight sum follows from the list alone, so there is no collective for it
     wkw = _window_kw(fuse_window(config), device)
+    tta = tta_plan(config)[1]                          # TTA: every rank runs its chunk in every orientation; rank 0 normalises with the k-fold list
     stats = stats if stats is not None else {}
     for k in ("pass1_queue_ms", "points_host_ms", "pass2_ms", "merge_host_ms", "canvas_bytes", "points_bytes", "votes_bytes", "scenes"):
         stats.setdefault(k, 0.0)
@@ -1128,7 +1217,7 @@ def _infer_imgs_tile_sharded(net, imgs, config, device=None, stats=None, valids=
                 scene = scene.clone()
             scene = net.scene_fill_invalid(scene, valid_d, fill)
         job.lo, job.hi = shard_tiles(len(job.infos), world, rank)
-        kp_c, road_c, job.emb = net.scene_pass1(scene, job.xy_dev[job.lo:job.hi], bs, **wkw)
+        kp_c, road_c, job.emb = net.scene_pass1(scene, job.xy_dev[job.lo:job.hi], bs, **wkw, **_tta_kw(tta))
         bands = D.tile_bands(job.all_xy, int(config.PATCH_SIZE), world) if world > 1 else None
         D.reduce_canvases(kp_c, road_c, dst=0, bands=bands)
         if bands is not None:
@@ -1138,8 +1227,9 @@ def _infer_imgs_tile_sharded(net, imgs, config, device=None, stats=None, valids=
             stats["canvas_bytes"] += D.canvas_bytes(bands, rows) if rank == 0 else 2 * 4 * rows * max(0, x1 - x0)
         job.masks = job.e1 = None
         if rank == 0:
-            kp_u8, road_u8 = net.scene_normalise(kp_c, road_c, job.xy_dev, **wkw) if valid_d is None else \
-                net.scene_normalise(kp_c, road_c, job.xy_dev, valid=valid_d, **wkw)
+            xy_norm = _tta_list(job.xy_dev, tta)
+            kp_u8, road_u8 = net.scene_normalise(kp_c, road_c, xy_norm, **wkw) if valid_d is None else \
+                net.scene_normalise(kp_c, road_c, xy_norm, valid=valid_d, **wkw)
             if cuda:       # asynchronous download behind the scene's own kernels: the host does not wait here
                 job.masks = [torch.empty(t.shape, dtype=t.dtype, pin_memory=True) for t in (kp_u8, road_u8)]
                 for h, t in zip(job.masks, (kp_u8, road_u8)):
@@ -1325,12 +1415,19 @@ def main(argv=None):
     ap.add_argument("--fuse-window", default=None, metavar="NAME", choices=FUSE_WINDOW_NAMES,
                     help="(extension) how overlapping tiles are fused, overriding the config's FUSE_WINDOW: uniform (the reference's mean), "
                          "hann or triangle (centre-weighted: tile borders count less)")
+    ap.add_argument("--tta", default=None, metavar="NAMES",
+                    help="(extension) test-time augmentation, overriding the config's TTA: orientation names separated by commas, the first "
+                         "one id (id,flip_h,flip_v,rot180,transpose,rot90,rot270,anti_transpose); every tile is run once per name and "
+                         "the masks are averaged")
     args = ap.parse_args(argv)
     config = load_config(args.config)
     if args.fuse_window is not None:
         config.FUSE_WINDOW = args.fuse_window
+    if args.tta is not None:
+        config.TTA = [t.strip() for t in args.tta.split(",")]
     neighbor_queries(config)                     # a K the TopoNet trunk cannot run fails here, not after the first scene's pass 1
     fuse_window(config)                          # and so does a FUSE_WINDOW that cannot be used
+    tta_plan(config)                             # and a TTA list that cannot be run
     device = torch.device("cuda") if args.device == "cuda" else torch.device(args.device)
     torch.set_num_threads(max(1, min(torch.get_num_threads(), usable_cpus() // max(1, int(os.environ.get("WORLD_SIZE", "1"))))))   # this rank's share of the container's CPU quota (hostcpu.py)
     _numpy_hugepages(False)                      # for the whole run: image decoding and output encoding allocate beside the GPU too (_host_quiet)

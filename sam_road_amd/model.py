@@ -499,13 +499,16 @@ class SAMRoad(nn.Module):
 
     # ---- scene level (pass 1 of infer_one_img: tile batcher + model + mask fusion) -------------------------
     @torch.no_grad()
-    def scene_pass1(self, scene_u8, tile_xy, batch_size, canvas_kp=None, canvas_road=None, window=None):
+    def scene_pass1(self, scene_u8, tile_xy, batch_size, canvas_kp=None, canvas_road=None, window=None, tta=None):
         """scene_u8 [H,W,3] uint8 on the GPU (H and W independent, each >= PATCH_SIZE), tile_xy int32 [n,2] (x0,y0) on the
         GPU, every tile inside the scene.  Runs the tiles in batches through the encoder + decoder and accumulates the two
         mask canvases [H,W] in the reference's sequential order (inferencer.py:87-104).  Returns (canvas_kp, canvas_road,
         embeddings[n,256,h,w]).  window (f32 [PATCH_SIZE] on the GPU, inferencer.fuse_window): every tile's scores enter the canvases
         weighted by window[lx] * window[ly] (srh_scene_pass1_window_hw); None: the call and the kernels of a scene
-        without a window."""
+        without a window.  tta (orientation codes 0..7, the first one 0 = id, inferencer.tta_plan): the whole tile list is run once per
+        orientation and the canvases hold the sum over (orientation, tile) — to be normalised with the tile list repeated len(tta)
+        times; the embeddings are those of id (srh_scene_pass1_tta_hw, with or without window); None: the calls of a
+        scene without TTA."""
         dev = scene_u8.device
         ctx, wh = self._weights(dev)
         assert scene_u8.dtype == torch.uint8 and scene_u8.dim() == 3 and scene_u8.shape[2] == 3
@@ -522,6 +525,16 @@ class SAMRoad(nn.Module):
             raise ValueError(f"canvases must be [{H}, {W}] like the scene, got {tuple(canvas_kp.shape)} / {tuple(canvas_road.shape)}")
         emb = torch.empty((n, h, h, 256), dtype=torch.float32, device=dev)
         if n == 0:                                   # a rank without tiles (world_size > tile count): nothing to add
+            return canvas_kp, canvas_road, emb.permute(0, 3, 1, 2)
+        if tta is not None:
+            codes = self._tta_codes(tta)
+            if window is not None:
+                window = self._window_f32(window, dev)
+            with torch.cuda.device(dev):
+                ctx.check(ctx.lib.srh_scene_pass1_tta_hw(ctx.handle, wh, scene_u8.data_ptr(), H, W, tile_xy.data_ptr(), n, int(batch_size),
+                                                         codes, len(codes), window.data_ptr() if window is not None else None,
+                                                         canvas_kp.data_ptr(), canvas_road.data_ptr(), emb.data_ptr(), self._stream(dev)),
+                          "srh_scene_pass1_tta_hw")
             return canvas_kp, canvas_road, emb.permute(0, 3, 1, 2)
         if window is not None:
             window = self._window_f32(window, dev)
@@ -574,6 +587,48 @@ class SAMRoad(nn.Module):
                                                      kp.data_ptr(), road.data_ptr(), self._stream(dev)),
                       "srh_scene_normalise_hw")
         return kp, road
+
+    @staticmethod
+    def _tta_codes(tta):
+        """Orientation codes as the host byte array srh_scene_pass1_tta_hw reads (the library checks the rules of DESIGN.md §6f)."""
+        import ctypes
+        codes = [int(c) for c in tta]
+        if not codes or any(not 0 <= c <= 255 for c in codes):
+            raise ValueError(f"tta must be a non-empty sequence of orientation codes 0..7, got {list(tta)!r}")
+        return (ctypes.c_uint8 * len(codes))(*codes)
+
+    @torch.no_grad()
+    def op_patch_im2col(self, scene_u8, tile_xy, orient=0, patch_size=None):
+        """Test-only (srh_op_patch_im2col): the f16 GEMM A matrix [n (P/16)^2, 768] of pass 1's crop + normalise + im2col for the tiles
+        tile_xy int32 [n,2] (x0,y0) of a u8 [H,W,3] scene on the GPU, in orientation code `orient` (0: the launch of a scene without TTA)."""
+        dev = scene_u8.device
+        ctx, _ = self._weights(dev)
+        P = int(patch_size or self.image_size)
+        if scene_u8.dtype != torch.uint8 or scene_u8.dim() != 3 or scene_u8.shape[2] != 3 or not scene_u8.is_contiguous():
+            raise ValueError("scene must be a contiguous uint8 [H,W,3] tensor")
+        tile_xy = tile_xy.to(device=dev, dtype=torch.int32).contiguous()
+        n, H, W = int(tile_xy.shape[0]), int(scene_u8.shape[0]), int(scene_u8.shape[1])
+        if n and (int(tile_xy.min()) < 0 or int(tile_xy[:, 0].max()) + P > W or int(tile_xy[:, 1].max()) + P > H):
+            raise ValueError("a tile lies outside the scene")
+        out = torch.empty((n * (P // 16) ** 2, 768), dtype=torch.float16, device=dev)
+        with torch.cuda.device(dev):
+            ctx.check(ctx.lib.srh_op_patch_im2col(ctx.handle, scene_u8.data_ptr(), H, W, tile_xy.data_ptr(), n, P, int(orient),
+                                                  out.data_ptr(), self._stream(dev)), "srh_op_patch_im2col")
+        return out
+
+    @torch.no_grad()
+    def op_scores_unorient(self, scores, orient):
+        """Test-only (srh_op_scores_unorient): scores f32 [n,P,P,2] of tiles oriented by code `orient` -> the scene frame, as a new tensor
+        (a permutation of bit patterns)."""
+        dev = scores.device
+        ctx, _ = self._weights(dev)
+        if scores.dtype != torch.float32 or scores.dim() != 4 or scores.shape[1] != scores.shape[2] or scores.shape[3] != 2 or not scores.is_contiguous():
+            raise ValueError("scores must be a contiguous float32 [n,P,P,2] tensor")
+        out = torch.empty_like(scores)
+        with torch.cuda.device(dev):
+            ctx.check(ctx.lib.srh_op_scores_unorient(ctx.handle, scores.data_ptr(), int(scores.shape[0]), int(scores.shape[1]), int(orient),
+                                                     out.data_ptr(), self._stream(dev)), "srh_op_scores_unorient")
+        return out
 
     def _window_f32(self, window, dev):
         if window.device != dev or window.dtype != torch.float32 or tuple(window.shape) != (self.image_size,):

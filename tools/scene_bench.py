@@ -12,6 +12,7 @@ The final map_decoder bias is lowered so that the random network yields sparse m
     python tools/scene_bench.py --scene 2048 4096 --tiles 16 32 --valid-frac 0.5    # a validity mask: a diagonal band covering that share
                                                                     # of the scene; only tiles that hold valid pixels run (kept / all is printed)
     python tools/scene_bench.py --fuse-window hann                  # overlapping tiles fused with a window (FUSE_WINDOW) instead of the uniform mean
+    python tools/scene_bench.py --tta id,flip_h,rot90               # test-time augmentation (TTA): every tile runs once per orientation
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 tools/scene_bench.py    # N GPUs:
         tiles sharded over the ranks (RCCL: packed-weight broadcast, banded canvas reduce, point broadcast, vote gather);
         rank 0 prints ms/scene (max over ranks) and the per-rank stage times
@@ -48,6 +49,8 @@ def main():
                     help="run the scene with a validity mask: a diagonal band that covers the share F (0 < F <= 1) of its pixels")
     ap.add_argument("--fuse-window", default=None, metavar="NAME", choices=("uniform", "hann", "triangle"),
                     help="FUSE_WINDOW: how overlapping tiles are fused (default: the key is absent, the reference's uniform mean)")
+    ap.add_argument("--tta", default=None, metavar="NAMES",
+                    help="TTA: orientation names separated by commas, the first one id (default: the key is absent, one run per tile)")
     ap.add_argument("--no-pipelined", action="store_true", help="skip the infer_imgs runs (12- and 48-scene streams)")
     args = ap.parse_args()
     H, W = parse_scene(args.scene)
@@ -74,8 +77,11 @@ def main():
                  MAX_NEIGHBOR_QUERIES=16)
     if args.fuse_window is not None:
         cfg.FUSE_WINDOW = args.fuse_window
-    from sam_road_amd.inferencer import fuse_window
+    if args.tta is not None:
+        cfg.TTA = [t.strip() for t in args.tta.split(",")]
+    from sam_road_amd.inferencer import fuse_window, tta_plan
     window = fuse_window(cfg)
+    tta_names, tta = tta_plan(cfg)
     net = SAMRoad(cfg)
     g = torch.Generator().manual_seed(1234)
     sd = {}
@@ -114,16 +120,18 @@ def main():
     valid_d = None if valid is None else torch.as_tensor(valid).to(dev)
     lo, hi = shard_tiles(len(infos), world, rank)
     wkw = {} if window is None else dict(window=torch.from_numpy(window).to(dev))
+    tkw = {} if len(tta) == 1 else dict(tta=tta)                      # TTA: pass 1 runs the list once per orientation,
+    xy_norm = xy if len(tta) == 1 else xy.repeat(len(tta), 1)         # the normalise gets the k-fold list
 
     def pass1():              # this rank's share of the tiles (no collective: tile throughput)
         if valid_d is not None:    # the masked pass 1 from the resident scene: count, fill (of a copy), kept tiles, masked normalise
             net.scene_tile_valid(valid_d, torch.as_tensor(_scene_plan(img, cfg)[2]).to(dev)).cpu()
             filled = net.scene_fill_invalid(scene.clone(), valid_d, (124, 116, 104))
-            kp, road, emb = net.scene_pass1(filled, xy[lo:hi], args.batch, **wkw)
-            kpu, ru = net.scene_normalise(kp, road, xy, valid=valid_d, **wkw)
+            kp, road, emb = net.scene_pass1(filled, xy[lo:hi], args.batch, **wkw, **tkw)
+            kpu, ru = net.scene_normalise(kp, road, xy_norm, valid=valid_d, **wkw)
             return kpu.cpu(), ru.cpu()
-        kp, road, emb = net.scene_pass1(scene, xy[lo:hi], args.batch, **wkw)
-        kpu, ru = net.scene_normalise(kp, road, xy, **wkw)
+        kp, road, emb = net.scene_pass1(scene, xy[lo:hi], args.batch, **wkw, **tkw)
+        kpu, ru = net.scene_normalise(kp, road, xy_norm, **wkw)
         return kpu.cpu(), ru.cpu()
 
     pass1()
@@ -194,6 +202,7 @@ def main():
     nodes, edges, kp, road = res
     print(json.dumps({"scene": f"synthetic {H}x{W} u8, {n_all} tiles of 512^2 ({per_edge} per edge, margin 64)", "n_gpus": world,
                       "fuse_window": args.fuse_window or "uniform",
+                      "tta": tta_names,
                       "valid_frac": None if valid is None else round(float(valid.mean()), 4), "tiles_kept": len(infos), "tiles_all": n_all,
                       "ms_weight_share": round(1e3 * t_w, 2) if world > 1 else None, "per_rank": per_rank,
                       "infer_batch_size": args.batch, "ms_per_scene_pass1": round(1e3 * p1, 2),
