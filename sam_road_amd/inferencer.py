@@ -13,16 +13,44 @@ With torch.distributed initialised (one process per GPU) the tile list is split 
 chunks per rank; canvases are summed on rank 0, points broadcast, edge votes gathered
 (sam_road_amd/distributed.py).  Only rank 0 returns the graph; other ranks return None.
 """
+import ctypes as C
+import dataclasses
+import functools
+import os
+import time
 import warnings
 
 import numpy as np
 import scipy.spatial
 import torch
 
+from . import _lib
 from . import distributed as D
 from .graph_points import extract_graph_points
 from .hostcpu import fill_threads, usable_cpus, worker_threads
 from .tiling import get_patch_info_hw, get_patch_info_one_img, patches_per_axis, shard_tiles
+
+
+def _vp(a):
+    return a.ctypes.data_as(C.c_void_p)
+
+
+class _Laps:
+    """The tuning aid of SRH_PROFILE_HOST=1: `[tag] label: ms` since the previous lap, printed as each section ends.  `sync`: a device to
+    synchronise before the clock is read (infer_one_img's stages); None: host wall time only.  Off (tag None, or the variable not set) a
+    lap costs one test."""
+
+    def __init__(self, tag=None, sync=None):
+        self.on = tag is not None and os.environ.get("SRH_PROFILE_HOST") == "1"
+        self.tag, self.sync, self.t = tag, sync, time.perf_counter()
+
+    def __call__(self, label):
+        if self.on and label:
+            if self.sync is not None:
+                torch.cuda.synchronize(self.sync)
+            t = time.perf_counter()
+            print(f"[{self.tag}] {label}: {(t - self.t) * 1e3:.1f} ms", flush=True)
+            self.t = t
 
 
 def build_patch_queries(graph_points, x0, y0, x1, y1, config):
@@ -88,7 +116,6 @@ def _kdtree_selfcheck():
     except Exception:
         ok = False
     if not ok:
-        import warnings
         warnings.warn(f"the kd-tree tie-breaking restated in libsamroad_hip (validated against scipy 1.15) differs from the installed scipy "
                       f"{scipy.__version__}: pass-2 queries fall back to the per-tile scipy path", RuntimeWarning)
     _KDTREE_OK[0] = ok
@@ -102,9 +129,6 @@ def build_all_patch_queries(graph_points, infos, lo, hi, config, flat=False):
     of scipy's kd-tree on their tile's points (ids ascending; csrc/kdtree_emul.hpp), so those rows equal the reference's call
     element for element; elsewhere the order inside a group of equidistant neighbours is (distance, index) where scipy's is
     heap-internal.  Returns a list of per-tile tuples, or the flat form."""
-    import ctypes as C
-    import os
-    from . import _lib
     k, r = int(config.MAX_NEIGHBOR_QUERIES), config.NEIGHBOR_RADIUS
     n_tiles = hi - lo
     if n_tiles <= 0:
@@ -113,19 +137,12 @@ def build_all_patch_queries(graph_points, infos, lo, hi, config, flat=False):
         if flat:
             return None
         return [build_patch_queries(graph_points, *infos[t][1], *infos[t][2], config) for t in range(lo, hi)]
-    import time
-    prof = os.environ.get("SRH_PROFILE_HOST") == "1"
-    t_sec = [time.perf_counter()]
-    def lap(name):
-        if prof:
-            t_sec.append(time.perf_counter())
-            print(f"[queries] {name}: {(t_sec[-1] - t_sec[-2]) * 1e3:.1f} ms", flush=True)
+    lap = _Laps("queries")
     lib = _lib.load()
     pts = np.ascontiguousarray(graph_points, dtype=np.int64)
     boxes = np.ascontiguousarray([[*infos[t][1], *infos[t][2]] for t in range(lo, hi)], dtype=np.int32)
     counts = np.zeros(n_tiles, dtype=np.int64)
-    vp = lambda a: a.ctypes.data_as(C.c_void_p)
-    if lib.srh_pass2_count(vp(pts), pts.shape[0], vp(boxes), n_tiles, vp(counts)) != 0:
+    if lib.srh_pass2_count(_vp(pts), pts.shape[0], _vp(boxes), n_tiles, _vp(counts)) != 0:
         raise _lib.SrhError("srh_pass2_count failed")
     offsets = np.zeros(n_tiles + 1, dtype=np.int64)
     np.cumsum(counts, out=offsets[1:])
@@ -134,7 +151,7 @@ def build_all_patch_queries(graph_points, infos, lo, hi, config, flat=False):
     knn = np.empty((total, k), dtype=np.int32)
     amb = np.empty(total, dtype=np.uint8)
     local = np.empty((total, 2), dtype=np.int64)
-    if lib.srh_pass2_fill(vp(pts), pts.shape[0], vp(boxes), n_tiles, k, int(r), vp(offsets), vp(ids), vp(knn), vp(amb), vp(local),
+    if lib.srh_pass2_fill(_vp(pts), pts.shape[0], _vp(boxes), n_tiles, k, int(r), _vp(offsets), _vp(ids), _vp(knn), _vp(amb), _vp(local),
                           fill_threads()) != 0:
         raise _lib.SrhError("srh_pass2_fill failed")
     lap("count + fill (library)")
@@ -159,10 +176,6 @@ def _collate(xs):
 PASS2_SORT_TILES = True       # False: batches of consecutive tiles, as the reference forms them (tools / tests set it; no environment switch)
 
 
-def _sort_pass2_tiles():
-    return PASS2_SORT_TILES
-
-
 def _pass2_plan(fq, bs, sort_tiles=None):
     """Which tiles share a TopoNet batch: [(tiles int64 [nb] — indices into fq —, n_max, base_row)]; a batch is padded to its longest
     tile (graph_collate_fn-style, inferencer.py:179-185) and owns rows [base, base + nb * n_max) of the staging buffers.
@@ -172,7 +185,7 @@ def _pass2_plan(fq, bs, sort_tiles=None):
     instead — 68 k padded rows, a little over half the device time and half the upload / download bytes of pass 2 — and the votes
     are still read in tile order (the reference's visiting order).  Empty tiles join no batch."""
     counts = np.diff(fq.offsets)
-    if _sort_pass2_tiles() if sort_tiles is None else sort_tiles:
+    if PASS2_SORT_TILES if sort_tiles is None else sort_tiles:
         idx = np.flatnonzero(counts > 0)
         idx = idx[np.argsort(counts[idx], kind="stable")]
         groups = [idx[i:i + bs] for i in range(0, len(idx), bs)]
@@ -202,7 +215,6 @@ def _pack_pass2_batches(fq, lo, hi, bs, K, alloc=None, sort_tiles=None):
     pts_h = alloc("points", (max(rows_total, 1), 2), np.float32)
     pairs_h = alloc("pairs", (max(rows_total, 1), K, 2), np.int32)
     valid_h = alloc("valid", (max(rows_total, 1), K), np.uint8)
-    from . import _lib
     lib = _lib.load()
     local = np.ascontiguousarray(fq.local, dtype=np.int64)
     offsets = np.ascontiguousarray(fq.offsets, dtype=np.int64)
@@ -267,7 +279,6 @@ def _pack_pass2_ragged(fq, K, alloc=None):
     [R,K,2], valid u8 [R,K]); rows keep their position in the flat query arrays, so tile t's scores are rows offsets[t] .. offsets[t+1]."""
     if alloc is None:
         alloc = lambda name, shape, dtype: np.zeros(shape, dtype)
-    from . import _lib
     lib = _lib.load()
     offsets = np.ascontiguousarray(fq.offsets, dtype=np.int64)
     R = int(offsets[-1] - offsets[0])
@@ -318,10 +329,7 @@ def _tile_slots(fq, lo, batches, K):
 def _votes_from_scores(fq, lo, batches, n_pts, K):
     """inferencer.py:209-221's visiting order (tile, source point, neighbour slot) as flat (key, score) vote arrays; batches as in
     _tile_slots, on the host (srh_pass2_votes, csrc/host_geom.hip; it also enforces the reference's 0 <= score <= 1 assertion)."""
-    import ctypes as C
-    from . import _lib
     lib = _lib.load()
-    vp = lambda a: a.ctypes.data_as(C.c_void_p)
     slots, keep = _tile_slots(fq, lo, batches, K)
     cap = int((fq.knn >= 0).sum())
     k = np.empty(cap, np.int64)
@@ -336,7 +344,7 @@ def _votes_from_scores(fq, lo, batches, n_pts, K):
         j = i + 1
         while j < len(slots) and slots[j][0] == slots[j - 1][0] + 1 and slots[j][2] == n_max and slots[j][1] == slots[j - 1][1] + n_max * K * 4:
             j += 1
-        rc = lib.srh_pass2_votes(addr, j - i, n_max, K, a_off + t * 8, vp(fq.ids), vp(fq.knn), n_pts, vp(k), vp(s), cap, C.byref(cnt_c))
+        rc = lib.srh_pass2_votes(addr, j - i, n_max, K, a_off + t * 8, _vp(fq.ids), _vp(fq.knn), n_pts, _vp(k), _vp(s), cap, C.byref(cnt_c))
         if rc != 0:
             raise AssertionError("edge score outside [0, 1] (reference inferencer.py:219) or inconsistent query arrays")
         i = j
@@ -350,10 +358,7 @@ def _vote_sums(fq, lo, batches, n_pts, K):
     csrc/host_geom.hip; visiting order per key kept, so the float64 sums, counts and first-vote positions are the same, bit for
     bit — tests/test_host_logic.py).  batches as in _tile_slots (every tile is handed over as a "batch" of one: where its scores
     lie does not matter)."""
-    import ctypes as C
-    from . import _lib
     lib = _lib.load()
-    vp = lambda a: a.ctypes.data_as(C.c_void_p)
     slots, keep = _tile_slots(fq, lo, batches, K)
     nb = len(slots)
     ptrs = (C.c_void_p * max(nb, 1))(*[a for _, a, _ in slots])
@@ -363,8 +368,8 @@ def _vote_sums(fq, lo, batches, n_pts, K):
     cap = int(fq.knn.size)                     # >= the number of distinct edges; the pages beyond them are never touched
     uk, sums, cnts, first = np.empty(cap, np.int64), np.empty(cap, np.float64), np.empty(cap, np.float64), np.empty(cap, np.int64)
     nu = C.c_int64(0)
-    rc = lib.srh_pass2_vote_sums(ptrs, vp(tile0), vp(cnt), vp(n_max), nb, K, vp(fq.offsets), fq.n_tiles, vp(fq.ids), vp(fq.knn),
-                                 n_pts, vp(uk), vp(sums), vp(cnts), vp(first), cap, C.byref(nu), worker_threads())
+    rc = lib.srh_pass2_vote_sums(ptrs, _vp(tile0), _vp(cnt), _vp(n_max), nb, K, _vp(fq.offsets), fq.n_tiles, _vp(fq.ids), _vp(fq.knn),
+                                 n_pts, _vp(uk), _vp(sums), _vp(cnts), _vp(first), cap, C.byref(nu), worker_threads())
     del keep
     if rc != 0:
         raise AssertionError("edge score outside [0, 1] (reference inferencer.py:219) or inconsistent query arrays")
@@ -374,17 +379,47 @@ def _vote_sums(fq, lo, batches, n_pts, K):
 def _accumulate_votes(k, s):
     """The reference's dict accumulation (float64 sums in visiting order) as a stable radix sort by key + one sequential pass
     in the library's host code (np.unique + np.bincount did the same in 11 ms per CityScale scene)."""
-    import ctypes as C
-    from . import _lib
     if k.shape[0] == 0:
         return np.zeros(0, np.int64), np.zeros(0), np.zeros(0), np.zeros(0, np.int64)
-    vp = lambda a: a.ctypes.data_as(C.c_void_p)
     uk, sums, cnts, first = np.empty_like(k), np.empty_like(s), np.empty_like(s), np.empty_like(k)
     nu = C.c_int64(0)
-    if _lib.load().srh_edge_vote_accumulate_mt(vp(k), vp(s), k.shape[0], vp(uk), vp(sums), vp(cnts), vp(first), C.byref(nu),
+    if _lib.load().srh_edge_vote_accumulate_mt(_vp(k), _vp(s), k.shape[0], _vp(uk), _vp(sums), _vp(cnts), _vp(first), C.byref(nu),
                                                worker_threads()) != 0:
         raise _lib.SrhError("srh_edge_vote_accumulate failed")
     return uk[:nu.value], sums[:nu.value], cnts[:nu.value], first[:nu.value]
+
+
+def _queue_pass2(net, emb, fq, bs, K, ragged, io):
+    """Pass 2 of fq's tiles (embeddings emb[t]) on its way: collate into `io`'s staging arrays, upload, launch the sampler + TopoNet, NaN
+    -> -100 (as the reference does before its range check); nothing is fetched.  Every array of a kind is ONE host buffer and one copy:
+    per-batch non_blocking uploads of pageable numpy memory went through torch's pinned-staging allocator and stalled 30-40 ms in some
+    scenes (profiles/r02_scene_stages.txt).  ragged: every query row in ONE unpadded launch (srh_toponet_ragged: 68 k padded rows -> 48 k
+    real ones on a CityScale scene); else the padded batches of _pass2_plan.  Returns (plan, score tensors on the device) for
+    _collect_pass2; plan is empty when there is no query row (nothing was launched)."""
+    if ragged:
+        R, *host = _pack_pass2_ragged(fq, K, io.alloc)
+        if R == 0:
+            return [], []
+        dev = [io.upload_packed(name, x[:R]) for name, x in zip(("points", "point_tile", "pairs", "valid"), host)]
+        io.step("pass 2 uploaded")
+        scores = net.infer_toponet_ragged(emb, *dev, tile_offsets=_ragged_offsets(fq))
+        plan, scores = "ragged", [torch.where(torch.isnan(scores), -100.0, scores)]
+    else:
+        plan, *host = _pack_pass2_batches(fq, 0, fq.n_tiles, bs, K, io.alloc)
+        if not plan:
+            return [], []
+        dev = [io.upload_packed(name, x) for name, x in zip(("points", "pairs", "valid"), host)]
+        io.step("pass 2 uploaded")
+        scores = [sc for _, sc in _launch_pass2_batches(net, emb, plan, *dev, K)]
+    io.step("pass 2 launched")
+    return plan, scores
+
+
+def _collect_pass2(fq, plan, scores, n_pts, K, raw=False):
+    """The votes of a pass 2 that _queue_pass2 launched, from its scores on the host (numpy, in the order returned): the unique keys with
+    their sums, counts and first-vote positions (_vote_sums), or for raw=True the votes themselves in visiting order."""
+    batches = _ragged_batches(fq, scores[0]) if plan == "ragged" else [(tiles, sc) for (tiles, _, _), sc in zip(plan, scores)]
+    return (_votes_from_scores if raw else _vote_sums)(fq, 0, batches, n_pts, K)
 
 
 def edge_votes(net, emb, graph_points, infos, lo, hi, config, device, raw=False):
@@ -393,86 +428,56 @@ def edge_votes(net, emb, graph_points, infos, lo, hi, config, device, raw=False)
     accumulated in float64 in the reference's order (tile, point, neighbour slot), so they are bit-identical to its dict loop
     for the tiles of THIS call (a multi-rank merge of such results: see distributed.gather_edge_votes).  raw=True returns the
     votes themselves, (keys int64, scores float64) in visiting order, for an exact merge on one rank."""
-    import os
-    import time
-    prof = os.environ.get("SRH_PROFILE_HOST") == "1"      # tuning aid: print the wall time of each section
-    t_sec = [time.perf_counter()]
-    def lap(name):
-        if prof:
-            t_sec.append(time.perf_counter())
-            print(f"[edge_votes] {name}: {(t_sec[-1] - t_sec[-2]) * 1e3:.1f} ms", flush=True)
+    lap = _Laps("edge_votes")                             # tuning aid: the wall time of each section
     bs = int(config.INFER_BATCH_SIZE)
     n_pts = graph_points.shape[0]
     K = int(config.MAX_NEIGHBOR_QUERIES)
     empty = (np.zeros(0, np.int64), np.zeros(0)) if raw else (np.zeros(0, np.int64), np.zeros(0), np.zeros(0), np.zeros(0, np.int64))
     fq = build_all_patch_queries(graph_points, infos, lo, hi, config, flat=True)
     lap("build_all_patch_queries")
-    if fq is None:
-        # non-integer coordinates / radius: the reference's per-tile scipy path, votes gathered in numpy
-        if hi - lo <= 0:
-            return empty
-        all_q = [build_patch_queries(graph_points, *infos[t][1], *infos[t][2], config) for t in range(lo, hi)]
-    # launch every batch before fetching any scores.  All batches' padded arrays are built into ONE host buffer per kind and
-    # uploaded with one blocking copy each: per-batch non_blocking uploads of pageable numpy memory went through torch's
-    # pinned-staging allocator and stalled 30-40 ms in some scenes (profiles/r02_scene_stages.txt).
-    launched = []
-    if fq is not None and _ragged_pass2(net, config):
-        # every query row of this call's tiles in ONE unpadded launch (68 k padded rows -> 48 k real ones on a CityScale scene)
-        R, pts_h, tile_h, pairs_h, valid_h = _pack_pass2_ragged(fq, K)
-        if R == 0:
-            return empty
-        scores = net.infer_toponet_ragged(emb, *(torch.from_numpy(x[:R]).to(device) for x in (pts_h, tile_h, pairs_h, valid_h)),
-                                          tile_offsets=_ragged_offsets(fq))
-        scores = torch.where(torch.isnan(scores), -100.0, scores)
-        lap("collate + H2D + launch (ragged)")
-        host_scores = _ragged_batches(fq, scores.cpu().numpy())
-        if not raw:
-            out = _vote_sums(fq, lo, host_scores, n_pts, K)
-            lap("score fetch + vote sums")
-            return out
-        return _votes_from_scores(fq, lo, host_scores, n_pts, K)          # raw: the votes themselves, in visiting order
     if fq is not None:
-        plan, pts_h, pairs_h, valid_h = _pack_pass2_batches(fq, lo, hi, bs, K)
-        pts_d, pairs_d, valid_d = (torch.from_numpy(x).to(device) for x in (pts_h, pairs_h, valid_h))
-        launched = [(tiles, None, None, sc) for tiles, sc in _launch_pass2_batches(net, emb, plan, pts_d, pairs_d, valid_d, K)]
-    else:
-        for off in range(lo, hi, bs):
-            end = min(off + bs, hi)
-            qs = all_q[off - lo:end - lo]
-            if max(q[1].shape[0] for q in qs) == 0:
-                continue
-            pts = _collate([q[1].astype(np.float32) for q in qs])
-            pairs = _collate([q[2].astype(np.int32) for q in qs])
-            valid = _collate([q[3] for q in qs])
-            scores = net.infer_toponet(emb[off - lo:end - lo], torch.as_tensor(pts).to(device), torch.as_tensor(pairs).to(device),
-                                       torch.as_tensor(valid).to(device))
-            launched.append((off, end, qs, torch.where(torch.isnan(scores), -100.0, scores).squeeze(-1)))
-    lap("collate + H2D + launch")
-    if not launched:
+        # the library path: queue everything, then fetch with blocking copies (infer_imgs does the same two steps through its lane)
+        ragged = _ragged_pass2(net, config)
+        plan, scores = _queue_pass2(net, emb, fq, bs, K, ragged, _BlockingIO(device))
+        lap("collate + H2D + launch (ragged)" if ragged else "collate + H2D + launch")
+        if not plan:
+            return empty
+        out = _collect_pass2(fq, plan, [sc.cpu().numpy() for sc in scores], n_pts, K, raw)
+        lap("score fetch + keys" if raw else "score fetch + vote sums")
+        return out
+    # non-integer coordinates / radius: the reference's per-tile scipy path, every batch launched before any scores are fetched, votes
+    # gathered in numpy
+    if hi - lo <= 0:
         return empty
-    if fq is not None:
-        host_scores = [(tiles, sc.cpu().numpy()) for tiles, _, _, sc in launched]
-        if not raw:
-            out = _vote_sums(fq, lo, host_scores, n_pts, K)
-            lap("score fetch + vote sums")
-            return out
-        k, s = _votes_from_scores(fq, lo, host_scores, n_pts, K)
-    else:
-        keys_l, score_l = [], []
-        for off, end, qs, scores_dev in launched:
-            scores = scores_dev.cpu().numpy()
-            for b, (ids, _, prs, vld) in enumerate(qs):
-                n = len(ids)
-                if n == 0:
-                    continue
-                sc = scores[b, :n][vld]
-                assert ((sc >= 0.0) & (sc <= 1.0)).all()
-                keys_l.append(ids[prs[:, :, 0]][vld].astype(np.int64) * n_pts + ids[prs[:, :, 1]][vld].astype(np.int64))
-                score_l.append(sc.astype(np.float64))
-        if not keys_l:
-            return empty
-        k = np.ascontiguousarray(np.concatenate(keys_l), dtype=np.int64)
-        s = np.ascontiguousarray(np.concatenate(score_l), dtype=np.float64)
+    all_q = [build_patch_queries(graph_points, *infos[t][1], *infos[t][2], config) for t in range(lo, hi)]
+    launched = []
+    for off in range(lo, hi, bs):
+        end = min(off + bs, hi)
+        qs = all_q[off - lo:end - lo]
+        if max(q[1].shape[0] for q in qs) == 0:
+            continue
+        pts = _collate([q[1].astype(np.float32) for q in qs])
+        pairs = _collate([q[2].astype(np.int32) for q in qs])
+        valid = _collate([q[3] for q in qs])
+        scores = net.infer_toponet(emb[off - lo:end - lo], torch.as_tensor(pts).to(device), torch.as_tensor(pairs).to(device),
+                                   torch.as_tensor(valid).to(device))
+        launched.append((qs, torch.where(torch.isnan(scores), -100.0, scores).squeeze(-1)))
+    lap("collate + H2D + launch")
+    keys_l, score_l = [], []
+    for qs, scores_dev in launched:
+        scores = scores_dev.cpu().numpy()
+        for b, (ids, _, prs, vld) in enumerate(qs):
+            n = len(ids)
+            if n == 0:
+                continue
+            sc = scores[b, :n][vld]
+            assert ((sc >= 0.0) & (sc <= 1.0)).all()
+            keys_l.append(ids[prs[:, :, 0]][vld].astype(np.int64) * n_pts + ids[prs[:, :, 1]][vld].astype(np.int64))
+            score_l.append(sc.astype(np.float64))
+    if not keys_l:
+        return empty
+    k = np.ascontiguousarray(np.concatenate(keys_l), dtype=np.int64)
+    s = np.ascontiguousarray(np.concatenate(score_l), dtype=np.float64)
     lap("score fetch + keys")
     if raw:
         return k, s
@@ -495,13 +500,10 @@ def votes_to_edges(uk, sums, cnts, first, n_pts, threshold):
         keep = (sums / np.maximum(cnts, 1.0)) > threshold
         k = uk[keep][np.argsort(first[keep], kind="stable")]
         return np.stack([k // n_pts, k % n_pts], axis=1).reshape(-1, 2)
-    import ctypes as C
-    from . import _lib
-    vp = lambda a: a.ctypes.data_as(C.c_void_p)
     out = np.empty((n, 2), dtype=np.int64)
     ne = C.c_int64(0)
     # library host code (srh_votes_to_edges): the kept edges dropped into a table indexed by first-vote position, read back in order
-    rc = _lib.load().srh_votes_to_edges(*(vp(a) for a in arrs), n, int(n_pts), float(threshold), vp(out), C.byref(ne))
+    rc = _lib.load().srh_votes_to_edges(*(_vp(a) for a in arrs), n, int(n_pts), float(threshold), _vp(out), C.byref(ne))
     if rc != 0:
         raise _lib.SrhError(f"srh_votes_to_edges failed ({rc})")
     return out[:ne.value].copy()
@@ -647,11 +649,6 @@ def select_tiles(counts, patch_size, min_valid_fraction):
     return np.flatnonzero((counts > 0) & (counts >= float(min_valid_fraction) * int(patch_size) * int(patch_size)))
 
 
-def _tile_counts(net, valid_d, xy_dev):
-    """Valid pixels per candidate tile on the host (int32 [n]): the model's count kernel + n int32 back + one wait."""
-    return net.scene_tile_valid(valid_d, xy_dev).cpu().numpy()
-
-
 def scene_tiles(shape, config, valid=None, net=None):
     """The tiles infer_one_img runs for a scene of `shape` = (H, W[, 3]): the list of (0, (x0, y0), (x1, y1)) in the reference's
     x-outer / y-inner order.  With `valid` (see infer_one_img) only the kept tiles, selected exactly as infer_one_img selects them: the
@@ -669,7 +666,7 @@ def scene_tiles(shape, config, valid=None, net=None):
     if net is None:
         raise ValueError("scene_tiles needs the model (net=) to count valid pixels on the device")
     device = next(net.parameters()).device
-    counts = _tile_counts(net, torch.from_numpy(v8).to(device), torch.as_tensor(all_xy).to(device))
+    counts = net.scene_tile_valid(torch.from_numpy(v8).to(device), torch.as_tensor(all_xy).to(device)).cpu().numpy()
     return TilePlan([infos[i] for i in select_tiles(counts, config.PATCH_SIZE, frac)], orientations)
 
 
@@ -719,12 +716,6 @@ def fuse_window(config):
         bad = int(np.flatnonzero(~(np.isfinite(w32) & (w32 >= lo) & (w32 <= hi)))[0])
         raise ValueError(f"FUSE_WINDOW: every value must be finite and inside [2^-20, 2^20]; value {bad} is {w[bad]!r}")
     return np.ascontiguousarray(w32)
-
-
-def _window_kw(window, device):
-    """The keyword a window adds to net.scene_pass1 / net.scene_normalise: none at all for the uniform case, so that those calls get
-    exactly the arguments they always got."""
-    return {} if window is None else dict(window=torch.from_numpy(window).to(device))
 
 
 # ---- test-time augmentation over the 8 orientations of a tile (TTA) ------------------------------------------------------------------
@@ -796,105 +787,9 @@ class TilePlan(list):
         self.orientations = list(orientations)
 
 
-def _tta_kw(codes):
-    """The keyword TTA adds to net.scene_pass1: none at all for ['id'], so that the call gets exactly the arguments it always got."""
-    return {} if len(codes) == 1 else dict(tta=list(codes))
-
-
-def _tta_list(xy_dev, codes):
-    """The tile list scene_normalise gets: repeated once per orientation (the coverage count becomes k * count, the weight sum runs
-    over k * n terms in list order: DESIGN.md §6f); the list itself for ['id']."""
-    return xy_dev if len(codes) == 1 else xy_dev.repeat(len(codes), 1)
-
-
 def _empty_result(H, W):
     """What a scene without a kept tile returns: no nodes, no edges, zero masks."""
     return np.zeros((0, 2), dtype=np.int64), np.zeros((0, 2), dtype=np.int32), np.zeros((H, W), np.uint8), np.zeros((H, W), np.uint8)
-
-
-def _infer_one_img(net, img, config, device=None, valid=None):
-    device = torch.device(device) if device is not None else next(net.parameters()).device
-    img, infos, all_xy = _scene_plan(img, config)
-    if valid is not None:
-        valid, min_frac, fill = _valid_plan(valid, img.shape[:2], config)
-    window = fuse_window(config)
-    tta = tta_plan(config)[1]
-    bs = int(config.INFER_BATCH_SIZE)
-    world = torch.distributed.get_world_size() if D.is_distributed() else 1
-    rank = torch.distributed.get_rank() if D.is_distributed() else 0
-
-    import os
-    import time
-    prof = os.environ.get("SRH_PROFILE_HOST") == "1"      # tuning aid: wall time of each stage (synchronises the device)
-    t_sec = [time.perf_counter()]
-    def lap(name):
-        if prof:
-            torch.cuda.synchronize(device)
-            t_sec.append(time.perf_counter())
-            print(f"[infer_one_img] {name}: {(t_sec[-1] - t_sec[-2]) * 1e3:.1f} ms", flush=True)
-
-    # ---- pass 1 (GPU): crop -> encoder -> decoder -> fused canvases; embeddings stay resident
-    scene = torch.as_tensor(np.ascontiguousarray(img), dtype=torch.uint8).to(device)
-    xy_dev = torch.as_tensor(all_xy).to(device)
-    lap("scene upload")
-    valid_d = None
-    if valid is not None:
-        # every rank holds the scene and the mask, computes the same integer counts and therefore the same kept list: from here
-        # on infos / all_xy / xy_dev ARE the kept tiles (a subsequence of an x-outer list is x-outer, so the banded reduce stays valid)
-        valid_d = torch.from_numpy(valid).to(device)
-        kept = select_tiles(_tile_counts(net, valid_d, xy_dev), config.PATCH_SIZE, min_frac)
-        lap("tile selection (count kernel + counts D2H)")
-        if len(kept) == 0:                             # nothing to run: the encoder is not launched
-            return _empty_result(*img.shape[:2]) if rank == 0 else None
-        infos, all_xy = [infos[i] for i in kept], np.ascontiguousarray(all_xy[kept])
-        xy_dev = torch.as_tensor(all_xy).to(device)
-        if scene.device.type != "cuda":                # a CPU tensor (the stand-in models of the gloo tests) shares the caller's memory
-            scene = scene.clone()
-        scene = net.scene_fill_invalid(scene, valid_d, fill)
-        lap("nodata fill")
-    lo, hi = shard_tiles(len(infos), world, rank)
-    wkw = _window_kw(window, device)                   # FUSE_WINDOW: the window applies to the kept list; uniform: no argument at all
-    # TTA: every orientation runs the kept list (selection and fill happened once, above); ['id']: no argument at all
-    kp_c, road_c, emb = net.scene_pass1(scene, xy_dev[lo:hi], bs, **wkw, **_tta_kw(tta))      # an empty shard (world > n_tiles) returns zero canvases
-    lap("pass 1 (GPU)")
-    D.reduce_canvases(kp_c, road_c, dst=0, bands=D.tile_bands(all_xy, int(config.PATCH_SIZE), world) if world > 1 else None)
-    graph_points = None
-    kp_mask = road_mask = None
-    if rank == 0:
-        xy_norm = _tta_list(xy_dev, tta)
-        kp_u8, road_u8 = net.scene_normalise(kp_c, road_c, xy_norm, **wkw) if valid_d is None else \
-            net.scene_normalise(kp_c, road_c, xy_norm, valid=valid_d, **wkw)
-        kp_mask, road_mask = kp_u8.cpu().numpy(), road_u8.cpu().numpy()
-        _poll_finite(net, device)                      # the masks are on the host, so every LayerNorm pass of pass 1 has reported
-        lap("normalise + mask D2H")
-        graph_points = extract_graph_points(kp_mask, road_mask, config)
-        lap("extract_graph_points")
-    graph_points = D.broadcast_points(graph_points, src=0, device=device if world > 1 else None)
-    if graph_points.shape[0] == 0:
-        if rank != 0:
-            return None
-        return graph_points, np.zeros((0, 2), dtype=np.int32), kp_mask, road_mask
-
-    # ---- pass 2: per-tile queries (host) -> sampler + TopoNet (GPU) -> directed edge votes
-    n_pts = graph_points.shape[0]
-    if world > 1 and config.EXACT_VOTE_MERGE:
-        # exact multi-rank merge (extension key, default off): every raw vote goes to rank 0 in the one-process visiting order
-        k_raw, s_raw = edge_votes(net, emb, graph_points, infos, lo, hi, config, device, raw=True)
-        k_raw, s_raw = D.gather_raw_votes(k_raw, s_raw, dst=0, device=device)
-        if rank != 0:
-            return None
-        uk, sums, cnts, first = _accumulate_votes(k_raw, s_raw)
-    else:
-        uk, sums, cnts, first = edge_votes(net, emb, graph_points, infos, lo, hi, config, device)
-        lap("edge_votes")
-        uk, sums, cnts, first = D.gather_edge_votes(uk, sums, cnts, n_pts, dst=0, device=device if world > 1 else None,
-                                                    first=first)
-    if rank != 0:
-        return None
-    pred_edges = votes_to_edges(uk, sums, cnts, first, n_pts, config.TOPO_THRESHOLD)
-    pred_nodes = graph_points[:, ::-1]  # (row, col)
-    lap("threshold + edge list")
-    return pred_nodes, pred_edges, kp_mask, road_mask
 
 
 class _StagingPool:
@@ -974,8 +869,221 @@ class _Lane:
         return outs, ev
 
 
+class _BlockingIO:
+    """How infer_one_img and the tile-sharded loops move a scene's arrays: one blocking copy each way, pageable memory.  The other
+    implementation of the same four operations is _LaneIO.  `lap` (a _Laps) names the steps of pass 1 for the profile."""
+    STEPS = {"upload": "scene upload", "select": "tile selection (count kernel + counts D2H)", "fill": "nodata fill",
+             "pass 1": "pass 1 (GPU)"}
+    alloc = None                                       # the pass-2 collate fills plain numpy arrays
+
+    def __init__(self, device, lap=None, async_scene=False):
+        self.device, self.lap, self.async_scene = device, lap, async_scene
+
+    def upload(self, name, arr):
+        """numpy array -> device tensor.  On a CPU device the tensor shares the array's memory."""
+        return torch.from_numpy(np.ascontiguousarray(arr)).to(self.device, non_blocking=self.async_scene and name == "scene")
+
+    upload_packed = upload                             # an array that `alloc` supplied and the collate filled
+
+    def counts(self, fn):
+        """fn() -> the valid-pixel counts on the device; returns them on the host (int32 [n]) after one wait."""
+        return fn().cpu().numpy()
+
+    def step(self, name):
+        if self.lap is not None:
+            self.lap(self.STEPS.get(name))
+
+
+class _LaneIO:
+    """The operations of _BlockingIO on infer_imgs' lane, for ONE scene in flight (`pool`: its page-locked staging): uploads are staged
+    and stream-ordered, the counts come back over the copy stream, the pass-2 collate writes straight into the staging buffers.  With the
+    profile on, five device events time the scene's pass 1, pass 2 and score download."""
+    STEPS = {"upload": "stage + queue scene upload", "select": "tile selection (upload lane)", "pass 1": "queue pass 1"}
+    EVENTS = {"launch pass 1": 0, "normalised": 1, "pass 2 uploaded": 2, "pass 2 launched": 3, "pass 2 on its way back": 4}
+
+    def __init__(self, lane, pool, lap):
+        self.lane, self.pool, self.lap, self.stage = lane, pool, lap, {}
+        self.t = [torch.cuda.Event(enable_timing=True) for _ in self.EVENTS] if lap.on and lane.cuda else None
+
+    def upload(self, name, arr):
+        return self.lane.upload(self.pool, name, arr)
+
+    def alloc(self, name, shape, dtype):
+        self.stage[name] = self.pool.get("up_" + name, shape, torch.from_numpy(np.zeros(0, dtype)).dtype)
+        return self.stage[name].numpy()                # srh_pass2_pack writes every row, padding included
+
+    def upload_packed(self, name, arr):
+        return self.lane.upload_staged(self.stage[name][:arr.shape[0]])
+
+    def counts(self, fn):
+        # on the upload lane: the count kernel uses no workspace of the library context, so it and the n int32 on their way back are
+        # queued on the copy stream.  Like every upload of this lane they start after what the compute stream holds at this moment (the
+        # previous scene's TopoNet work, about a millisecond), and the host waits for the counts
+        return self.lane.on_copy_stream(self.pool, "counts", fn)
+
+    def step(self, name):
+        if self.t is not None and name in self.EVENTS:
+            self.t[self.EVENTS[name]].record()
+        self.lap(self.STEPS.get(name))
+
+
+class _SceneSetup:
+    """What one infer_one_img / infer_imgs / _infer_imgs_tile_sharded call fixes for all of its scenes.  sharded: the scenes' tiles are
+    split over the ranks of torch.distributed (world 1 without it); False: this process runs whole scenes and issues no collective."""
+
+    def __init__(self, net, config, device, sharded):
+        self.net, self.config, self.sharded = net, config, sharded
+        self.device = torch.device(device) if device is not None else next(net.parameters()).device
+        self.K = neighbor_queries(config)
+        self.bs = int(config.INFER_BATCH_SIZE)
+        dist = sharded and D.is_distributed()
+        self.world = torch.distributed.get_world_size() if dist else 1
+        self.rank = torch.distributed.get_rank() if dist else 0
+
+    @functools.cached_property
+    def features(self):
+        """(keywords FUSE_WINDOW and TTA add to scene_pass1, keywords FUSE_WINDOW adds to scene_normalise, number of orientations) — no
+        keyword at all for a feature that is off, so that those calls get exactly the arguments they always got.  Checked (FUSE_WINDOW,
+        then TTA) and the window uploaded at the first scene, once its shape and mask have passed: bad input is refused in that order,
+        before the device is touched."""
+        window, codes = fuse_window(self.config), tta_plan(self.config)[1]
+        wkw = {} if window is None else dict(window=torch.from_numpy(window).to(self.device))
+        return {**wkw, **({} if len(codes) == 1 else dict(tta=list(codes)))}, wkw, len(codes)
+
+
+@dataclasses.dataclass
 class _SceneJob:
-    pass
+    """One scene from pass 1 to its result."""
+    shape: tuple                      # (H, W)
+    infos: list                       # the tiles that run (the kept ones under a mask) and their origins int32 [n,2] (x0, y0)
+    all_xy: np.ndarray
+    empty: bool = False               # a mask kept no tile: nothing was launched and the fields below stay as they are
+    lo: int = 0                       # this rank's chunk of the tiles; emb holds their embeddings
+    hi: int = 0
+    emb: torch.Tensor = None
+    bands: list = None                # the column bands of the canvas reduce (world > 1)
+    kp_u8: torch.Tensor = None        # the two masks on the device (rank 0)
+    road_u8: torch.Tensor = None
+    # what infer_imgs' pipeline adds as the scene moves through it
+    io: _LaneIO = None
+    masks: list = None                # the masks on their way to the host, and the event that says they have landed
+    e1: object = None
+    kp_mask: np.ndarray = None
+    road_mask: np.ndarray = None
+    graph_points: np.ndarray = None
+    fq: _FlatQueries = None
+    plan: object = ()                 # _queue_pass2's plan, its scores on their way to the host and their event
+    scores: list = None
+    e2: object = None
+    votes: tuple = None
+
+
+def _pass1_front(ctx, io, img, valid=None):
+    """Pass 1 of one scene, queued (GPU): plan, upload, [tile selection, nodata fill,] crop -> encoder -> decoder -> fused canvases,
+    [canvas reduce,] normalise.  `io` decides how arrays travel and when the host waits (_BlockingIO / _LaneIO); everything else is the
+    same for every loop.  Returns the _SceneJob: embeddings resident, the u8 masks on the device of rank 0 — fetching them is the
+    caller's."""
+    net, config = ctx.net, ctx.config
+    img, infos, all_xy = _scene_plan(img, config)
+    if valid is not None:
+        valid, min_frac, fill = _valid_plan(valid, img.shape[:2], config)
+    pass1_kw, norm_kw, n_orient = ctx.features
+    scene = io.upload("scene", img)                    # the u8 scene, ONCE; tiles are cropped on the device
+    xy_dev = io.upload("xy", all_xy)
+    io.step("upload")
+    if valid is not None:
+        # every rank holds the scene and the mask, computes the same integer counts and therefore the same kept list: from here
+        # on infos / all_xy / xy_dev ARE the kept tiles (a subsequence of an x-outer list is x-outer, so the banded reduce stays valid)
+        valid_d = io.upload("valid_mask", valid)       # a key of its own: "valid" stages pass 2's pair flags
+        kept = select_tiles(io.counts(lambda: net.scene_tile_valid(valid_d, xy_dev)), config.PATCH_SIZE, min_frac)
+        io.step("select")
+        infos, all_xy = [infos[i] for i in kept], np.ascontiguousarray(all_xy[kept])
+        if len(kept) == 0:                             # nothing to run: the encoder is not launched and no exchange step is entered
+            return _SceneJob(img.shape[:2], infos, all_xy, empty=True)
+        xy_dev = io.upload("xy_kept", all_xy)
+        if scene.device.type != "cuda":                # a CPU tensor (the stand-in models of the gloo tests) may share the caller's memory
+            scene = scene.clone()
+        scene = net.scene_fill_invalid(scene, valid_d, fill)
+        io.step("fill")
+        norm_kw = dict(valid=valid_d, **norm_kw)
+    job = _SceneJob(img.shape[:2], infos, all_xy)
+    job.lo, job.hi = shard_tiles(len(infos), ctx.world, ctx.rank)
+    io.step("launch pass 1")
+    # FUSE_WINDOW: every rank weights its own chunk of the kept list.  TTA: every orientation runs that chunk (selection and fill happened
+    # once, above).  An empty shard (world > n_tiles) returns zero canvases
+    kp_c, road_c, job.emb = net.scene_pass1(scene, xy_dev[job.lo:job.hi], ctx.bs, **pass1_kw)
+    io.step("pass 1")
+    if ctx.sharded:
+        job.bands = D.tile_bands(all_xy, int(config.PATCH_SIZE), ctx.world) if ctx.world > 1 else None
+        D.reduce_canvases(kp_c, road_c, dst=0, bands=job.bands)
+    if ctx.rank == 0:
+        # the full kept list, repeated once per orientation (the coverage count becomes k * count, the weight sum runs over k * n terms
+        # in list order: DESIGN.md §6f) — count and weight sum follow from the list alone, so there is no collective for them
+        xy_norm = xy_dev if n_orient == 1 else xy_dev.repeat(n_orient, 1)
+        job.kp_u8, job.road_u8 = net.scene_normalise(kp_c, road_c, xy_norm, **norm_kw)
+    io.step("normalised")
+    return job
+
+
+def _pass2_sharded(ctx, job, kp_mask, road_mask, stats=None, lap=None):
+    """From a scene's masks on the host (rank 0; None elsewhere) to its result tuple on rank 0, None on the other ranks: graph points
+    (host, rank 0) -> broadcast -> per-tile queries (host) -> sampler + TopoNet (GPU) -> directed edge votes of this rank's tiles ->
+    gather -> edges.  The two exchange steps run in the same order on every rank.  `stats` collects wall times and exchanged bytes."""
+    import collections
+    net, config, device, world, rank = ctx.net, ctx.config, ctx.device, ctx.world, ctx.rank
+    stats = stats if stats is not None else collections.defaultdict(float)
+    lap = lap or _Laps()
+    if job.empty:
+        return _empty_result(*job.shape) if rank == 0 else None
+    t0 = time.perf_counter()
+    graph_points = None
+    if rank == 0:
+        graph_points = extract_graph_points(kp_mask, road_mask, config)
+        lap("extract_graph_points")
+    t1 = time.perf_counter()
+    stats["points_host_ms"] += 1e3 * (t1 - t0)
+    graph_points = D.broadcast_points(graph_points, src=0, device=device if world > 1 else None)
+    stats["points_bytes"] += 16 * graph_points.shape[0] * ((world - 1) if rank == 0 else 1)     # rank 0: sent to every peer; others: received
+    if graph_points.shape[0] == 0:
+        return None if rank != 0 else (graph_points, np.zeros((0, 2), dtype=np.int32), kp_mask, road_mask)
+    n_pts = graph_points.shape[0]
+    if world > 1 and config.EXACT_VOTE_MERGE:
+        # exact multi-rank merge (extension key, default off): every raw vote goes to rank 0 in the one-process visiting order
+        k_raw, s_raw = edge_votes(net, job.emb, graph_points, job.infos, job.lo, job.hi, config, device, raw=True)
+        t2 = time.perf_counter()
+        stats["votes_bytes"] += 16 * k_raw.shape[0]
+        k_raw, s_raw = D.gather_raw_votes(k_raw, s_raw, dst=0, device=device)
+        if rank != 0:
+            stats["pass2_ms"] += 1e3 * (t2 - t1)
+            return None
+        uk, sums, cnts, first = _accumulate_votes(k_raw, s_raw)
+    else:
+        uk, sums, cnts, first = edge_votes(net, job.emb, graph_points, job.infos, job.lo, job.hi, config, device)
+        lap("edge_votes")
+        t2 = time.perf_counter()
+        stats["votes_bytes"] += 32 * uk.shape[0]
+        uk, sums, cnts, first = D.gather_edge_votes(uk, sums, cnts, n_pts, dst=0, device=device if world > 1 else None, first=first)
+    stats["pass2_ms"] += 1e3 * (t2 - t1)
+    job.emb = None
+    if rank != 0:
+        return None
+    t3 = time.perf_counter()
+    pred_edges = votes_to_edges(uk, sums, cnts, first, n_pts, config.TOPO_THRESHOLD)
+    stats["merge_host_ms"] += 1e3 * (time.perf_counter() - t3)
+    lap("threshold + edge list")
+    return graph_points[:, ::-1], pred_edges, kp_mask, road_mask      # nodes as (row, col)
+
+
+def _infer_one_img(net, img, config, device=None, valid=None):
+    ctx = _SceneSetup(net, config, device, sharded=True)
+    lap = _Laps("infer_one_img", sync=ctx.device)      # tuning aid: wall time of each stage (synchronises the device)
+    job = _pass1_front(ctx, _BlockingIO(ctx.device, lap), img, valid)
+    kp_mask = road_mask = None
+    if job.kp_u8 is not None:                          # rank 0 of a scene that ran
+        kp_mask, road_mask = job.kp_u8.cpu().numpy(), job.road_u8.cpu().numpy()
+        _poll_finite(net, ctx.device)                  # the masks are on the host, so every LayerNorm pass of pass 1 has reported
+        lap("normalise + mask D2H")
+    return _pass2_sharded(ctx, job, kp_mask, road_mask, lap=lap)
 
 
 def _valid_iter(valids):
@@ -1014,58 +1122,20 @@ def infer_imgs(net, imgs, config, device=None, tile_sharded=None, pipelined=None
             for img in imgs:
                 yield infer_one_img(net, img, config, device=device, valid=next(valids))
         return
-    device = torch.device(device) if device is not None else next(net.parameters()).device
+    ctx = _SceneSetup(net, config, device, sharded=False)
+    device, K = ctx.device, ctx.K
     lane = _Lane(device)
     pools = [_StagingPool(device), _StagingPool(device)]
-    bs, K = int(config.INFER_BATCH_SIZE), neighbor_queries(config)
-    wkw = _window_kw(fuse_window(config), device)      # FUSE_WINDOW: one upload for the whole sequence
-    tta = tta_plan(config)[1]
-    import os
-    import time
-    prof = os.environ.get("SRH_PROFILE_HOST") == "1"      # tuning aid: host wall time of each step (no device synchronisation)
-    t_sec = [time.perf_counter()]
-    def lap(name):
-        if prof:
-            t_sec.append(time.perf_counter())
-            print(f"[infer_imgs] {name}: {(t_sec[-1] - t_sec[-2]) * 1e3:.1f} ms", flush=True)
+    lap = _Laps("infer_imgs")                          # tuning aid: host wall time of each step (no device synchronisation)
 
     def launch_pass1(img, pool, valid=None):           # G1: upload, pass 1, normalise, masks on their way to the host
-        job = _SceneJob()
-        img, job.infos, all_xy = _scene_plan(img, config)
-        if valid is not None:
-            valid, min_frac, fill = _valid_plan(valid, img.shape[:2], config)
-        job.pool = pool
-        scene = lane.upload(pool, "scene", img)
-        xy_dev = lane.upload(pool, "xy", all_xy)
-        lap("stage + queue scene upload")
-        valid_d = None
-        if valid is not None:
-            # selection on the upload lane: mask upload, count kernel (it uses no workspace of the library context) and the n int32
-            # on their way back are queued on the copy stream.  Like every upload of this lane they start after what the compute
-            # stream holds at this moment (the previous scene's TopoNet work, about a millisecond), and the host waits for the counts
-            valid_d = lane.upload(pool, "valid_mask", valid)   # a key of its own: "valid" stages pass 2's pair flags (points_and_pass2)
-            counts = lane.on_copy_stream(pool, "counts", lambda: net.scene_tile_valid(valid_d, xy_dev))
-            kept = select_tiles(counts, config.PATCH_SIZE, min_frac)
-            lap("tile selection (upload lane)")
-            job.infos, all_xy = [job.infos[i] for i in kept], np.ascontiguousarray(all_xy[kept])
-            if len(kept) == 0:                         # nothing to run: zero masks, no nodes, the encoder is not launched
-                job.n_tiles, job.e1, job.emb = 0, None, None
-                job.masks = [torch.zeros(img.shape[:2], dtype=torch.uint8) for _ in range(2)]
-                return job
-            xy_dev = lane.upload(pool, "xy_kept", all_xy)
-            scene = net.scene_fill_invalid(scene, valid_d, fill)       # the device copy of this scene, not the caller's array
-        job.n_tiles = len(job.infos)
-        if prof and lane.cuda:
-            job.t = [torch.cuda.Event(enable_timing=True) for _ in range(5)]
-            job.t[0].record()
-        kp_c, road_c, job.emb = net.scene_pass1(scene, xy_dev, bs, **wkw, **_tta_kw(tta))
-        lap("queue pass 1")
-        xy_norm = _tta_list(xy_dev, tta)
-        kp_u8, road_u8 = net.scene_normalise(kp_c, road_c, xy_norm, **wkw) if valid_d is None else \
-            net.scene_normalise(kp_c, road_c, xy_norm, valid=valid_d, **wkw)
-        if prof and lane.cuda:
-            job.t[1].record()
-        job.masks, job.e1 = lane.download(pool, "mask", [kp_u8, road_u8])
+        io = _LaneIO(lane, pool, lap)
+        job = _pass1_front(ctx, io, img, valid)
+        job.io = io
+        if job.empty:                                  # zero masks, no nodes
+            job.masks = [torch.zeros(job.shape, dtype=torch.uint8) for _ in range(2)]
+            return job
+        job.masks, job.e1 = lane.download(pool, "mask", [job.kp_u8, job.road_u8])
         lap("queue normalise + mask download")
         return job
 
@@ -1075,50 +1145,21 @@ def infer_imgs(net, imgs, config, device=None, tile_sharded=None, pipelined=None
         job.kp_mask, job.road_mask = (m.numpy().copy() for m in job.masks)
         job.graph_points = extract_graph_points(job.kp_mask, job.road_mask, config)
         lap("extract_graph_points")
-        job.fq = job.plan = job.votes = None
         if job.graph_points.shape[0] == 0:
             return
-        job.fq = build_all_patch_queries(job.graph_points, job.infos, 0, job.n_tiles, config, flat=True)
+        job.fq = build_all_patch_queries(job.graph_points, job.infos, 0, len(job.infos), config, flat=True)
         lap("build_all_patch_queries")
         if job.fq is None:                             # non-integer radius: the serial per-tile path
-            job.votes = edge_votes(net, job.emb, job.graph_points, job.infos, 0, job.n_tiles, config, device)
+            job.votes = edge_votes(net, job.emb, job.graph_points, job.infos, 0, len(job.infos), config, device)
             return
-        stage = {}
-        def alloc(name, shape, dtype):
-            stage[name] = job.pool.get("up_" + name, shape, torch.from_numpy(np.zeros(0, dtype)).dtype)
-            return stage[name].numpy()                 # srh_pass2_pack writes every row, padding included
-        if _ragged_pass2(net, config):                 # ONE unpadded launch for the scene's query rows (srh_toponet_ragged)
-            R = _pack_pass2_ragged(job.fq, K, alloc)[0]
-            job.plan = "ragged" if R else []
-            if not R:
-                return
-            pts_d, tile_d, pairs_d, valid_d = (lane.upload_staged(stage[n][:R]) for n in ("points", "point_tile", "pairs", "valid"))
-            if prof and lane.cuda:
-                job.t[2].record()
-            sc = net.infer_toponet_ragged(job.emb, pts_d, tile_d, pairs_d, valid_d, tile_offsets=_ragged_offsets(job.fq))
-            sc = torch.where(torch.isnan(sc), -100.0, sc)
-            if prof and lane.cuda:
-                job.t[3].record()
-            job.scores, job.e2 = lane.download(job.pool, "score", [sc])
-            if prof and lane.cuda:
-                job.t[4].record()
-            job.emb = None
-            lap("pack + queue pass 2 (ragged)")
-            return
-        job.plan = _pack_pass2_batches(job.fq, 0, job.n_tiles, bs, K, alloc)[0]
+        ragged = _ragged_pass2(net, config)
+        job.plan, scores = _queue_pass2(net, job.emb, job.fq, ctx.bs, K, ragged, job.io)
         if not job.plan:
             return
-        pts_d, pairs_d, valid_d = (lane.upload_staged(stage[n]) for n in ("points", "pairs", "valid"))
-        if prof and lane.cuda:
-            job.t[2].record()
-        launched = _launch_pass2_batches(net, job.emb, job.plan, pts_d, pairs_d, valid_d, K, 0)
-        if prof and lane.cuda:
-            job.t[3].record()
-        job.scores, job.e2 = lane.download(job.pool, "score", [sc for _, sc in launched])
-        if prof and lane.cuda:
-            job.t[4].record()
+        job.scores, job.e2 = lane.download(job.io.pool, "score", scores)
+        job.io.step("pass 2 on its way back")
         job.emb = None
-        lap("pack + queue pass 2")
+        lap("pack + queue pass 2 (ragged)" if ragged else "pack + queue pass 2")
 
     def finish(job):                                   # H2: votes -> edges
         nodes = job.graph_points[:, ::-1]              # (row, col)
@@ -1132,13 +1173,11 @@ def infer_imgs(net, imgs, config, device=None, tile_sharded=None, pipelined=None
             if job.e2 is not None:
                 job.e2.synchronize()
             lap("wait for pass-2 scores")
-            if prof and lane.cuda:
-                t = job.t
+            if job.io.t is not None:
+                t = job.io.t
                 print(f"[infer_imgs] device: pass 1 {t[0].elapsed_time(t[1]):.1f} ms, mask download -> pass 2 start {t[1].elapsed_time(t[2]):.1f} ms, "
                       f"pass 2 {t[2].elapsed_time(t[3]):.1f} ms, score download {t[3].elapsed_time(t[4]):.1f} ms", flush=True)
-            batches = _ragged_batches(job.fq, job.scores[0].numpy()) if job.plan == "ragged" else \
-                [(tiles, sc.numpy()) for (tiles, _, _), sc in zip(job.plan, job.scores)]
-            job.votes = _vote_sums(job.fq, 0, batches, n_pts, K)
+            job.votes = _collect_pass2(job.fq, job.plan, [sc.numpy() for sc in job.scores], n_pts, K)
         edges = votes_to_edges(*job.votes, n_pts, config.TOPO_THRESHOLD)
         lap("votes -> edges")
         return nodes, edges, job.kp_mask, job.road_mask
@@ -1179,16 +1218,10 @@ def _infer_imgs_tile_sharded(net, imgs, config, device=None, stats=None, valids=
     the same order on every rank:   stage1(i+1): reduce_canvases(i+1)   |   stage2(i): broadcast_points(i), gather_*_votes(i).
     Results per scene are those of infer_one_img under the same world size (same kernels, same summation orders); rank 0 yields
     the tuples, the other ranks yield None.  `stats` (a dict) collects per-stage wall times and the bytes of every exchange."""
-    import time
-    device = torch.device(device) if device is not None else next(net.parameters()).device
-    world = torch.distributed.get_world_size() if D.is_distributed() else 1
-    rank = torch.distributed.get_rank() if D.is_distributed() else 0
-    bs = int(config.INFER_BATCH_SIZE)
+    ctx = _SceneSetup(net, config, device, sharded=True)
+    device, rank = ctx.device, ctx.rank
     cuda = device.type == "cuda"
-    # FUSE_WINDOW: every rank weights its own chunk; the bands of the reduce are unchanged, and rank 0 normalises with the full kept
-    # list — the weight sum follows from the list alone, so there is no collective for it
-    wkw = _window_kw(fuse_window(config), device)
-    tta = tta_plan(config)[1]                          # TTA: every rank runs its chunk in every orientation; rank 0 normalises with the k-fold list
+    io = _BlockingIO(device, async_scene=cuda)
     stats = stats if stats is not None else {}
     for k in ("pass1_queue_ms", "points_host_ms", "pass2_ms", "merge_host_ms", "canvas_bytes", "points_bytes", "votes_bytes", "scenes"):
         stats.setdefault(k, 0.0)
@@ -1196,90 +1229,34 @@ def _infer_imgs_tile_sharded(net, imgs, config, device=None, stats=None, valids=
     valids = _valid_iter(valids)
 
     def stage1(img, valid=None):
-        job = _SceneJob()
         t0 = time.perf_counter()
-        job.img, job.infos, job.all_xy = _scene_plan(img, config)
-        if valid is not None:
-            valid, min_frac, fill = _valid_plan(valid, job.img.shape[:2], config)
-        scene = torch.as_tensor(np.ascontiguousarray(job.img), dtype=torch.uint8).to(device, non_blocking=cuda)
-        job.xy_dev = torch.as_tensor(job.all_xy).to(device)
-        job.empty, valid_d = False, None
-        if valid is not None:                          # the same integer counts, hence the same kept list, on every rank
-            valid_d = torch.from_numpy(valid).to(device)
-            kept = select_tiles(_tile_counts(net, valid_d, job.xy_dev), config.PATCH_SIZE, min_frac)
-            job.infos, job.all_xy = [job.infos[i] for i in kept], np.ascontiguousarray(job.all_xy[kept])
-            if len(kept) == 0:                         # no rank runs anything and no exchange step is entered
-                job.empty = True
-                stats["pass1_queue_ms"] += 1e3 * (time.perf_counter() - t0)
-                return job
-            job.xy_dev = torch.as_tensor(job.all_xy).to(device)
-            if not cuda:
-                scene = scene.clone()
-            scene = net.scene_fill_invalid(scene, valid_d, fill)
-        job.lo, job.hi = shard_tiles(len(job.infos), world, rank)
-        kp_c, road_c, job.emb = net.scene_pass1(scene, job.xy_dev[job.lo:job.hi], bs, **wkw, **_tta_kw(tta))
-        bands = D.tile_bands(job.all_xy, int(config.PATCH_SIZE), world) if world > 1 else None
-        D.reduce_canvases(kp_c, road_c, dst=0, bands=bands)
-        if bands is not None:
+        job = _pass1_front(ctx, io, img, valid)
+        if job.bands is not None:
             # this rank's own share: the band it ships to rank 0 (rank 0: what it receives), so that per-rank statistics are per rank
-            x0, x1 = bands[rank]
-            rows = job.img.shape[0]                    # a band is a strip of columns of the full scene HEIGHT
-            stats["canvas_bytes"] += D.canvas_bytes(bands, rows) if rank == 0 else 2 * 4 * rows * max(0, x1 - x0)
-        job.masks = job.e1 = None
-        if rank == 0:
-            xy_norm = _tta_list(job.xy_dev, tta)
-            kp_u8, road_u8 = net.scene_normalise(kp_c, road_c, xy_norm, **wkw) if valid_d is None else \
-                net.scene_normalise(kp_c, road_c, xy_norm, valid=valid_d, **wkw)
+            x0, x1 = job.bands[rank]
+            rows = job.shape[0]                        # a band is a strip of columns of the full scene HEIGHT
+            stats["canvas_bytes"] += D.canvas_bytes(job.bands, rows) if rank == 0 else 2 * 4 * rows * max(0, x1 - x0)
+        if job.kp_u8 is not None:
             if cuda:       # asynchronous download behind the scene's own kernels: the host does not wait here
-                job.masks = [torch.empty(t.shape, dtype=t.dtype, pin_memory=True) for t in (kp_u8, road_u8)]
-                for h, t in zip(job.masks, (kp_u8, road_u8)):
+                job.masks = [torch.empty(t.shape, dtype=t.dtype, pin_memory=True) for t in (job.kp_u8, job.road_u8)]
+                for h, t in zip(job.masks, (job.kp_u8, job.road_u8)):
                     h.copy_(t, non_blocking=True)
                 job.e1 = torch.cuda.Event()
                 job.e1.record(torch.cuda.current_stream(device))
             else:
-                job.masks = [kp_u8, road_u8]
+                job.masks = [job.kp_u8, job.road_u8]
         stats["pass1_queue_ms"] += 1e3 * (time.perf_counter() - t0)
         return job
 
     def stage2(job):
-        if job.empty:
-            return _empty_result(*job.img.shape[:2]) if rank == 0 else None
         t0 = time.perf_counter()
-        graph_points = kp_mask = road_mask = None
-        if rank == 0:
+        kp_mask = road_mask = None
+        if job.masks is not None:
             if job.e1 is not None:
                 job.e1.synchronize()
-            kp_mask, road_mask = (np.array(m.numpy() if isinstance(m, torch.Tensor) else m) for m in job.masks)
-            graph_points = extract_graph_points(kp_mask, road_mask, config)
-        t1 = time.perf_counter()
-        stats["points_host_ms"] += 1e3 * (t1 - t0)
-        graph_points = D.broadcast_points(graph_points, src=0, device=device if world > 1 else None)
-        stats["points_bytes"] += 16 * graph_points.shape[0] * ((world - 1) if rank == 0 else 1)     # rank 0: sent to every peer; others: received
-        if graph_points.shape[0] == 0:
-            return None if rank != 0 else (graph_points, np.zeros((0, 2), dtype=np.int32), kp_mask, road_mask)
-        n_pts = graph_points.shape[0]
-        if world > 1 and config.EXACT_VOTE_MERGE:
-            k_raw, s_raw = edge_votes(net, job.emb, graph_points, job.infos, job.lo, job.hi, config, device, raw=True)
-            t2 = time.perf_counter()
-            stats["votes_bytes"] += 16 * k_raw.shape[0]
-            k_raw, s_raw = D.gather_raw_votes(k_raw, s_raw, dst=0, device=device)
-            if rank != 0:
-                stats["pass2_ms"] += 1e3 * (t2 - t1)
-                return None
-            uk, sums, cnts, first = _accumulate_votes(k_raw, s_raw)
-        else:
-            uk, sums, cnts, first = edge_votes(net, job.emb, graph_points, job.infos, job.lo, job.hi, config, device)
-            t2 = time.perf_counter()
-            stats["votes_bytes"] += 32 * uk.shape[0]
-            uk, sums, cnts, first = D.gather_edge_votes(uk, sums, cnts, n_pts, dst=0, device=device if world > 1 else None, first=first)
-        stats["pass2_ms"] += 1e3 * (t2 - t1)
-        job.emb = None
-        if rank != 0:
-            return None
-        t3 = time.perf_counter()
-        pred_edges = votes_to_edges(uk, sums, cnts, first, n_pts, config.TOPO_THRESHOLD)
-        stats["merge_host_ms"] += 1e3 * (time.perf_counter() - t3)
-        return graph_points[:, ::-1], pred_edges, kp_mask, road_mask
+            kp_mask, road_mask = (np.array(m.numpy()) for m in job.masks)
+            stats["points_host_ms"] += 1e3 * (time.perf_counter() - t0)      # the wait for the masks counts as host time of the points
+        return _pass2_sharded(ctx, job, kp_mask, road_mask, stats)
 
     it = iter(imgs)
     img = next(it, None)
@@ -1299,7 +1276,6 @@ def _infer_imgs_tile_sharded(net, imgs, config, device=None, stats=None, valids=
 
 def get_img_paths(root_dir, image_indices):
     """inferencer.py:38-44."""
-    import os
     return [os.path.join(root_dir, f"region_{ind}_sat.png") for ind in image_indices]
 
 
@@ -1353,7 +1329,6 @@ def spacenet_data_partition():
 
 def create_output_dir_and_save_config(output_dir_prefix, config, specified_dir=None):
     """utils.py:11-29."""
-    import os
     import yaml
     from datetime import datetime
     out = specified_dir if specified_dir else f"{output_dir_prefix}_{datetime.now().strftime('%Y%m%d_%H%M%S')}"
@@ -1393,9 +1368,7 @@ def main(argv=None):
     `--valid-masks m0.png m1.npy ...` (parallel to `--images`; `-` = no mask for that scene) gives every scene a validity mask
     (infer_one_img's `valid`); without it an RGBA `--images` file uses its alpha > 0.  Output formats do not change."""
     import argparse
-    import os
     import pickle
-    import time
     from PIL import Image
     from .config import load_config
     from .formats import convert_to_sat2graph_format

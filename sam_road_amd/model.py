@@ -526,28 +526,18 @@ class SAMRoad(nn.Module):
         emb = torch.empty((n, h, h, 256), dtype=torch.float32, device=dev)
         if n == 0:                                   # a rank without tiles (world_size > tile count): nothing to add
             return canvas_kp, canvas_road, emb.permute(0, 3, 1, 2)
-        if tta is not None:
-            codes = self._tta_codes(tta)
-            if window is not None:
-                window = self._window_f32(window, dev)
-            with torch.cuda.device(dev):
-                ctx.check(ctx.lib.srh_scene_pass1_tta_hw(ctx.handle, wh, scene_u8.data_ptr(), H, W, tile_xy.data_ptr(), n, int(batch_size),
-                                                         codes, len(codes), window.data_ptr() if window is not None else None,
-                                                         canvas_kp.data_ptr(), canvas_road.data_ptr(), emb.data_ptr(), self._stream(dev)),
-                          "srh_scene_pass1_tta_hw")
-            return canvas_kp, canvas_road, emb.permute(0, 3, 1, 2)
+        codes = self._tta_codes(tta) if tta is not None else None
         if window is not None:
             window = self._window_f32(window, dev)
-            with torch.cuda.device(dev):
-                ctx.check(ctx.lib.srh_scene_pass1_window_hw(ctx.handle, wh, scene_u8.data_ptr(), H, W, tile_xy.data_ptr(), n,
-                                                            int(batch_size), window.data_ptr(), canvas_kp.data_ptr(),
-                                                            canvas_road.data_ptr(), emb.data_ptr(), self._stream(dev)),
-                          "srh_scene_pass1_window_hw")
-            return canvas_kp, canvas_road, emb.permute(0, 3, 1, 2)
+        if codes is not None:
+            entry, extra = "srh_scene_pass1_tta_hw", (codes, len(codes), window.data_ptr() if window is not None else None)
+        elif window is not None:
+            entry, extra = "srh_scene_pass1_window_hw", (window.data_ptr(),)
+        else:
+            entry, extra = "srh_scene_pass1_hw", ()
         with torch.cuda.device(dev):
-            ctx.check(ctx.lib.srh_scene_pass1_hw(ctx.handle, wh, scene_u8.data_ptr(), H, W, tile_xy.data_ptr(), n,
-                                                 int(batch_size), canvas_kp.data_ptr(), canvas_road.data_ptr(),
-                                                 emb.data_ptr(), self._stream(dev)), "srh_scene_pass1_hw")
+            ctx.check(getattr(ctx.lib, entry)(ctx.handle, wh, scene_u8.data_ptr(), H, W, tile_xy.data_ptr(), n, int(batch_size), *extra,
+                                              canvas_kp.data_ptr(), canvas_road.data_ptr(), emb.data_ptr(), self._stream(dev)), entry)
         return canvas_kp, canvas_road, emb.permute(0, 3, 1, 2)
 
     @torch.no_grad()
@@ -564,28 +554,18 @@ class SAMRoad(nn.Module):
         road = torch.empty((H, W), dtype=torch.uint8, device=dev)
         if window is not None:
             window = self._window_f32(window, dev)
-            if valid is not None:
-                valid = self._valid_u8(valid, H, W, dev)
-            with torch.cuda.device(dev):
-                ctx.check(ctx.lib.srh_scene_normalise_window_hw(ctx.handle, canvas_kp.data_ptr(), canvas_road.data_ptr(), H, W,
-                                                                tile_xy.data_ptr(), tile_xy.shape[0], self.image_size, window.data_ptr(),
-                                                                valid.data_ptr() if valid is not None else None,
-                                                                kp.data_ptr(), road.data_ptr(), self._stream(dev)),
-                          "srh_scene_normalise_window_hw")
-            return kp, road
         if valid is not None:
             valid = self._valid_u8(valid, H, W, dev)
-            with torch.cuda.device(dev):
-                ctx.check(ctx.lib.srh_scene_normalise_valid_hw(ctx.handle, canvas_kp.data_ptr(), canvas_road.data_ptr(), H, W,
-                                                               tile_xy.data_ptr(), tile_xy.shape[0], self.image_size, valid.data_ptr(),
-                                                               kp.data_ptr(), road.data_ptr(), self._stream(dev)),
-                          "srh_scene_normalise_valid_hw")
-            return kp, road
+        if window is not None:
+            entry, extra = "srh_scene_normalise_window_hw", (window.data_ptr(), valid.data_ptr() if valid is not None else None)
+        elif valid is not None:
+            entry, extra = "srh_scene_normalise_valid_hw", (valid.data_ptr(),)
+        else:
+            entry, extra = "srh_scene_normalise_hw", ()
         with torch.cuda.device(dev):
-            ctx.check(ctx.lib.srh_scene_normalise_hw(ctx.handle, canvas_kp.data_ptr(), canvas_road.data_ptr(), H, W,
-                                                     tile_xy.data_ptr(), tile_xy.shape[0], self.image_size,
-                                                     kp.data_ptr(), road.data_ptr(), self._stream(dev)),
-                      "srh_scene_normalise_hw")
+            ctx.check(getattr(ctx.lib, entry)(ctx.handle, canvas_kp.data_ptr(), canvas_road.data_ptr(), H, W, tile_xy.data_ptr(),
+                                              tile_xy.shape[0], self.image_size, *extra, kp.data_ptr(), road.data_ptr(),
+                                              self._stream(dev)), entry)
         return kp, road
 
     @staticmethod

@@ -261,6 +261,40 @@ def test_tta_scene_on_the_standin(standin):
         _same_tuple(list(infer_imgs(net, [img], cw, device="cpu", **kw))[0], gw)
 
 
+def test_the_four_entry_paths_make_the_same_calls(standin):
+    """infer_one_img, infer_imgs, and the serial and the pipelined tile-sharded loop share one pass-1 front end: for every feature
+    combination they call the model with the same arguments in the same order and return the same tuple."""
+    net, cfg = standin
+    H, W = 384, 640
+    img = _rect_scene(H, W, 60)
+    band = make_mask("band", H, W)
+    n = 15
+    kept = sum(bool(band[p[1][1]:p[2][1], p[1][0]:p[2][0]].any()) for p in inf.scene_tiles((H, W), Config(cfg)))
+    combos = [(dict(), None, [("pass1", n), ("normalise", n)]),
+              (dict(FUSE_WINDOW="hann"), band, [("tile_valid", n), ("fill", (124, 116, 104)), ("pass1_window", kept), ("normalise", kept),
+                                                ("normalise_window", kept)]),
+              (dict(FUSE_WINDOW="hann", TTA=["id", "rot90"]), band,
+               [("tile_valid", n), ("fill", (124, 116, 104)), ("pass1_tta", kept, (0, 5), True), ("normalise", 2 * kept), ("normalise_window", 2 * kept)])]
+    paths = [lambda c, v: infer_one_img(net, img, c, device="cpu", valid=v)]
+    for kw in (dict(), dict(tile_sharded=True), dict(tile_sharded=True, pipelined=True)):
+        paths.append(lambda c, v, kw=kw: list(infer_imgs(net, [img], c, device="cpu", valids=[v], **kw))[0])
+    results = []
+    for extra, valid, want_calls in combos:
+        c = Config(dict(cfg, **extra))
+        first = None
+        for run in paths:
+            net.calls.clear()
+            got = run(c, valid)
+            assert net.calls == want_calls
+            if first is None:
+                first = got
+                assert got[0].shape[0] > 30 and got[1].shape[0] > 100
+            else:
+                _same_tuple(got, first)
+        results.append(first)
+    assert not np.array_equal(results[0][3], results[1][3]) and not np.array_equal(results[1][3], results[2][3])
+
+
 # ---- CLI --------------------------------------------------------------------------------------------------------------------------
 def test_cli_takes_the_key_and_the_flag(tmp_path, monkeypatch, standin):
     import yaml
