@@ -257,6 +257,45 @@ int srh_op_conv3x3(srh_ctx* ctx, const void* A_f16, const void* W_f16, int B, in
                    float* out_f32, void* stream);
 int srh_op_layernorm(srh_ctx* ctx, const float* x, const float* gamma, const float* beta, float eps, int M,
                      int D, int gelu, float* out_f32, void* out_f16, void* stream);
+/* The residual-stream passes (test-only; additive, the ABI stays 11).  The encoder keeps the residual stream x in f32 and folds the
+ * residual adds of a ViT block (reference model.py:245-258 builds the SAM fork's ImageEncoderViT: Block.forward's x = shortcut + attn(..)
+ * and x = x + mlp(norm2(x)), ImageEncoderViT.forward's x = patch_embed(x) + pos_embed; run at model.py:424 / :469) into the LayerNorm
+ * pass that reads x next.  srh_op_layernorm_ex launches that pass with the parameter patterns srh_encode_decode produces (api.hip
+ * encode_batch: block_ln, fold_pending and the neck's cast), every optional member 0 / NULL being srh_op_layernorm:
+ *   delta16            x' = x + delta16 (fp16 [M,D]: proj, fc2 or the patch embedding when the persistent 256x192 GEMM wrote it) —
+ *                      Block.forward's residual adds; block_ln with one branch pending;
+ *   delta16 + delta16b x' = (x + delta16) + delta16b, the order in which Block.forward adds attention then MLP — the next block's norm1
+ *                      when both branch GEMMs of a block took the 256x192 kernel (encode_batch's defer_x, ViT-B at large batch);
+ *   x_period > 0       x has x_period rows and row m reads row m % x_period: pos_embed [S*S, D] as block 0's initial residual,
+ *                      x' = pos_embed[token] + delta16 (the patch embedding) — block_ln while x_is_pos;
+ *   slices             x' = ((slice 0 + slice 1 + ...) + slice_bias) + x over nslices f32 [M,D] partials slice_stride ELEMENTS apart:
+ *                      the split-K partials of a deferred fc2 (srh_op_gemm_partials), in the reduce pass's order — ViT-L / ViT-H at
+ *                      256 px; D = 1024 / 1280 only, not together with delta16, slice_bias required (else SRH_ERR_UNSUPPORTED);
+ *   x_out              where x' is written ([M,D] f32; may be x itself when x_period == 0) — block_ln's write_x; NULL: x' is only normalised;
+ *   gamma == NULL      cast-only: out_f16 = fp16(x') — the neck's first pass over the last block's output (no sentinel in this mode);
+ *   nf_tag             -1: no sentinel; 0 .. 63: a row of x' whose variance is not finite sets the context's flag nf_tag, which
+ *                      srh_ctx_check reports as SRH_ERR_NONFINITE naming encoder block nf_tag / 2, norm1 (even) / norm2 (odd).
+ * SRH_ERR_BAD_ARG: delta16b without delta16, nf_tag outside -1 .. 63.  SRH_ERR_UNSUPPORTED: D not one of 128 / 256 / 768 / 1024 / 1280
+ * and the slices cases above.  Nothing is launched in either case. */
+typedef struct {
+    const float* x; int32_t M, D, x_period;
+    const float* gamma; const float* beta; float eps; int32_t gelu;
+    const void* delta16; const void* delta16b; float* x_out;
+    const float* slices; int32_t nslices; size_t slice_stride; const float* slice_bias;
+    int32_t nf_tag;
+    float* out_f32; void* out_f16;
+} srh_op_norm_args;
+int srh_op_layernorm_ex(srh_ctx* ctx, const srh_op_norm_args* args, void* stream);
+/* The GEMM as a block's deferred fc2 runs it (encode_batch's branch_gemm with defer_reduce; Block.forward's mlp lin2): split-K into the
+ * context's workspace, no reduce pass.  *partials = that workspace (device, f32 [*nslices, M, N], slice stride M * N, valid until the
+ * next GEMM on the context), to be folded with `bias` by srh_op_layernorm_ex's slices.  SRH_ERR_UNSUPPORTED, nothing launched, for a
+ * shape the dispatch runs without split-K. */
+int srh_op_gemm_partials(srh_ctx* ctx, const void* A_f16, const void* W_f16, const float* bias, int M, int N, int K,
+                         const float** partials, int* nslices, void* stream);
+/* out_f32 = A W^T + bias + pos[m % pos_rows] (pos f32 [pos_rows, N]): the patch embedding plus pos_embed in the GEMM epilogue
+ * (ImageEncoderViT.forward), as encode_batch runs it whenever the 256x192 kernel is not preferred for that layer. */
+int srh_op_gemm_pos(srh_ctx* ctx, const void* A_f16, const void* W_f16, const float* bias, const float* pos, int pos_rows,
+                    int M, int N, int K, float* out_f32, void* stream);
 /* SAM attention on a fused qkv tensor [B*S*S, 3*heads*64] fp16: rel-pos tables [2*win-1, 64] fp16,
  * qkv bias fp16 [3*heads*64] (pad-key rows), win = 14 (windowed) or S (global). out fp16 [B*S*S, heads*64]. */
 int srh_op_attention(srh_ctx* ctx, const void* qkv_f16, const void* relpos_h_f16, const void* relpos_w_f16,

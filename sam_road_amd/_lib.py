@@ -35,8 +35,19 @@ class ProfileRow(C.Structure):
                 ("bytes", C.c_double)]
 
 
-# every symbol include/samroad_hip.h declares: (restype, argtypes)
 _P, _I, _F = C.c_void_p, C.c_int, C.c_float
+
+
+class OpNormArgs(C.Structure):
+    """srh_op_norm_args (srh_op_layernorm_ex, test-only): zero-initialised = plain srh_op_layernorm; nf_tag -1 = no sentinel."""
+    _fields_ = [("x", _P), ("M", C.c_int32), ("D", C.c_int32), ("x_period", C.c_int32),
+                ("gamma", _P), ("beta", _P), ("eps", _F), ("gelu", C.c_int32),
+                ("delta16", _P), ("delta16b", _P), ("x_out", _P),
+                ("slices", _P), ("nslices", C.c_int32), ("slice_stride", C.c_size_t), ("slice_bias", _P),
+                ("nf_tag", C.c_int32), ("out_f32", _P), ("out_f16", _P)]
+
+
+# every symbol include/samroad_hip.h declares: (restype, argtypes)
 SYMBOLS = {
     "srh_abi_version": (_I, []),
     "srh_build_id": (C.c_char_p, []),
@@ -67,6 +78,9 @@ SYMBOLS = {
     "srh_ctx_device_bytes": (C.c_size_t, [_P]),
     "srh_op_conv3x3": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P]),
     "srh_op_layernorm": (_I, [_P, _P, _P, _P, _F, _I, _I, _I, _P, _P, _P]),
+    "srh_op_layernorm_ex": (_I, [_P, C.POINTER(OpNormArgs), _P]),
+    "srh_op_gemm_partials": (_I, [_P, _P, _P, _P, _I, _I, _I, C.POINTER(_P), C.POINTER(_I), _P]),
+    "srh_op_gemm_pos": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P]),
     "srh_op_attention": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P]),
     "srh_op_attention_hd": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P]),
     "srh_op_map_decoder": (_I, [_P, _P, _P, _I, _P, _P, _P]),

@@ -1315,6 +1315,53 @@ extern "C" int srh_op_layernorm(srh_ctx* c, const float* x, const float* gamma, 
     return 0;
 }
 
+// The residual-stream passes at op level: the NormParams patterns of encode_batch's block_ln / fold_pending / neck cast, and the two
+// GEMM modes that feed them (branch_gemm's deferred split-K, the patch embedding's f32 + pos epilogue), on caller-supplied buffers.
+extern "C" int srh_op_layernorm_ex(srh_ctx* c, const srh_op_norm_args* a, void* stream) {
+    if (!c || !a || !a->x) return fail(c, SRH_ERR_BAD_ARG, "srh_op_layernorm_ex: null argument");
+    if (a->delta16b && !a->delta16) return fail(c, SRH_ERR_BAD_ARG, "srh_op_layernorm_ex: delta16b needs delta16 (it is folded after it)");
+    if (a->nf_tag < -1 || a->nf_tag >= NF_NECK) return fail(c, SRH_ERR_BAD_ARG, "srh_op_layernorm_ex: nf_tag must be -1 (no sentinel) or 0 to 63");
+    if (a->M < 0 || a->x_period < 0 || a->nslices < 0) return fail(c, SRH_ERR_BAD_ARG, "srh_op_layernorm_ex: bad sizes");
+    hipSetDevice(c->device);
+    NormParams ln;
+    ln.x = a->x; ln.M = a->M; ln.D = a->D; ln.x_period = a->x_period;
+    ln.gamma = a->gamma; ln.beta = a->beta; ln.eps = a->eps; ln.act = a->gelu;
+    ln.delta16 = (const f16*)a->delta16; ln.delta16b = (const f16*)a->delta16b; ln.x_out = a->x_out;
+    ln.slices = a->slices; ln.nslices = a->nslices; ln.slice_stride = a->slice_stride; ln.slice_bias = a->slice_bias;
+    if (a->nf_tag >= 0) { ln.nf = c->nf_dev; ln.nf_tag = a->nf_tag; }
+    ln.out_f32 = a->out_f32; ln.out_f16 = (f16*)a->out_f16;
+    hipStream_t s = (hipStream_t)stream;
+    TRYK(c, "layernorm", 0, 0, s, launch_layernorm(ln, s));
+    return 0;
+}
+
+extern "C" int srh_op_gemm_partials(srh_ctx* c, const void* A, const void* W, const float* bias, int M, int N, int K,
+                                    const float** partials, int* nslices, void* stream) {
+    if (!c || !A || !W || !partials || !nslices) return fail(c, SRH_ERR_BAD_ARG, "srh_op_gemm_partials: null argument");
+    *partials = nullptr; *nslices = 0;
+    hipSetDevice(c->device);
+    GemmParams g;                                 // branch_gemm's gp: f32 in-place residual epilogue, which the deferred reduce leaves to the caller
+    g.A = (const f16*)A; g.lda = K; g.W = (const f16*)W; g.ldw = K; g.M = M; g.N = N; g.K = K; g.bias = bias;
+    g.resid = c->x.as<float>(); g.ldr = N; g.out_f32 = c->x.as<float>(); g.ldc = N;   // named, never touched: the partials are the only output
+    const int sk = gemm_splitk_factor(g);         // what gemm() splits by
+    if (sk <= 1) return fail(c, SRH_ERR_UNSUPPORTED, "srh_op_gemm_partials: this shape runs without split-K");
+    g.defer_reduce = 1;
+    TRY(gemm(c, "gemm_op", g, (hipStream_t)stream));
+    *partials = c->split_ws.as<float>(); *nslices = sk;
+    return 0;
+}
+
+extern "C" int srh_op_gemm_pos(srh_ctx* c, const void* A, const void* W, const float* bias, const float* pos, int pos_rows,
+                               int M, int N, int K, float* out_f32, void* stream) {
+    if (!c || !A || !W || !pos || !out_f32) return fail(c, SRH_ERR_BAD_ARG, "srh_op_gemm_pos: null argument");
+    if (pos_rows <= 0) return fail(c, SRH_ERR_BAD_ARG, "srh_op_gemm_pos: pos_rows must be positive");
+    hipSetDevice(c->device);
+    GemmParams g;
+    g.A = (const f16*)A; g.lda = K; g.W = (const f16*)W; g.ldw = K; g.M = M; g.N = N; g.K = K; g.bias = bias;
+    g.pos = pos; g.pos_rows = pos_rows; g.out_f32 = out_f32; g.ldc = N;
+    return gemm(c, "gemm_op", g, (hipStream_t)stream);
+}
+
 // The heads after the encoder at op level: the same launchers, with the parameters the model path gives them (encode_batch,
 // toponet_impl), on caller-supplied inputs.
 extern "C" int srh_op_map_decoder(srh_ctx* c, const srh_weights* w, const void* emb_f16, int B, float* mask_logits, float* mask_scores,

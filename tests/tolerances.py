@@ -50,6 +50,18 @@ DEC_OP_SCORE = 3e-3          # measured 1.01e-3 .. 1.06e-3
 # typical rounding is far below that worst case, and integer points are exact up to the taps' products.
 SAMPLE_OP_F32 = 2e-6         # measured 2.6e-7 .. 7.1e-7 (f32 points), 5.3e-8 .. 8.8e-8 (i64 points)
 
+# ---- residual-stream passes at op level (tests/test_gpu_residual.py, against float64 references; the folds themselves are exact;
+# the record of the measured values is profiles/parity_measured_op_residual.json) ----------
+# LayerNorm of the folded x' at tests/test_gpu_ops.py test_layernorm's distributions (x ~ 3 N(0,1) + 1.5, gamma / beta ~ N(0,1)), max-abs.
+# A priori: outputs reach |y| ~ 16 on 10^7 elements; f32: a few ulp of that (2e-6 each); f16: half an fp16 ulp of the output, 3.9e-3 at |y| in [8, 16).
+RESID_LN_F32 = 6e-6          # measured 8.4e-7 .. 2.3e-6 (47 cases: every width, 197 .. 33285 rows, every fused mode); test_layernorm's bound is 2e-5
+# The fp16 bound is absolute for |y| < 16 and counts in units of the fp16 spacing relative to [8, 16) beyond (x 2 in [16, 32)): a handful of
+# the 10^7 outputs of the large shapes exceed 16 (seen on the CPU, in the float64 reference alone), where half an ulp is 7.8e-3 by itself.
+RESID_LN_F16 = 5e-3          # measured 1.9e-3 .. 3.91e-3 (half an fp16 ulp in [8, 16)); test_layernorm's bound
+# GEMM f32 output (the deferred split-K chain's x', the pos epilogue): max-abs error / (max(|ref|, 1) * sqrt(K / 64)), test_gemm's formula
+# (its coefficient there is 2e-4, against a float32 product; against float64, with f32 accumulation of K <= 5120 terms of O(0.03):)
+RESID_GEMM_F32 = 1e-7        # measured 1.8e-8 .. 2.3e-8 (split-K chain), 2.5e-8 .. 3.7e-8 (pos epilogue), 8.2e-9 .. 8.7e-9 (pos against a host-side add)
+
 _REC = {}
 
 
