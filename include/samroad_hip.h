@@ -260,7 +260,7 @@ int srh_op_layernorm(srh_ctx* ctx, const float* x, const float* gamma, const flo
 /* The residual-stream passes (test-only; additive, the ABI stays 11).  The encoder keeps the residual stream x in f32 and folds the
  * residual adds of a ViT block (reference model.py:245-258 builds the SAM fork's ImageEncoderViT: Block.forward's x = shortcut + attn(..)
  * and x = x + mlp(norm2(x)), ImageEncoderViT.forward's x = patch_embed(x) + pos_embed; run at model.py:424 / :469) into the LayerNorm
- * pass that reads x next.  srh_op_layernorm_ex launches that pass with the parameter patterns srh_encode_decode produces (api.hip
+ * pass that reads x next.  srh_op_layernorm_ex launches that pass with the parameter patterns srh_encode_decode produces (api_model.hip
  * encode_batch: block_ln, fold_pending and the neck's cast), every optional member 0 / NULL being srh_op_layernorm:
  *   delta16            x' = x + delta16 (fp16 [M,D]: proj, fc2 or the patch embedding when the persistent 256x192 GEMM wrote it) —
  *                      Block.forward's residual adds; block_ln with one branch pending;

@@ -1,0 +1,163 @@
+// C ABI, scene level: pass 1 of infer_one_img over a resident scene (tile batches through encode_batch, api_model.hip) and the mask
+// normalisation, with their nodata / FUSE_WINDOW / TTA variants.
+#include "ctx.hpp"
+
+// ---- scene level ------------------------------------------------------------------------------------------
+static int scene_pass1_impl(srh_ctx* c, const char* who, const srh_weights* w, const uint8_t* scene, int H, int W,
+                            const int32_t* tile_xy, int n_tiles, int B, float* canvas_kp, float* canvas_road,
+                            float* embeddings_all, void* stream, bool has_window = false, const float* profile = nullptr,
+                            const uint8_t* orients = nullptr, int k = 1) {
+    if (!c || !w || !scene || !tile_xy || !canvas_kp || !canvas_road || !embeddings_all || (has_window && !profile))
+        return fail(c, SRH_ERR_BAD_ARG, std::string(who) + ": null argument");
+    if (n_tiles < 0 || B <= 0 || H < w->cfg.patch_size || W < w->cfg.patch_size || !scene_dims_ok(H, W))
+        return fail(c, SRH_ERR_BAD_ARG, std::string(who) + ": bad sizes");
+    TRY(nonfinite_check(c, who));
+    hipSetDevice(c->device);
+    hipStream_t s = (hipStream_t)stream;
+    const int P = w->cfg.patch_size;
+    if (c->scores_ws.ensure((size_t)B * P * P * 2 * 4)) return fail(c, SRH_ERR_HIP, "scores workspace allocation failed");
+    const size_t emb_per_tile = (size_t)w->S * w->S * 256;
+    if (k > 1 && n_tiles > 0) {       // TTA: an oriented batch's scores before the un-orient, and its embeddings, which nobody reads
+        const size_t nb_max = (size_t)std::min(B, n_tiles);
+        if (c->tta_scores_ws.ensure(nb_max * P * P * 2 * 4)) return fail(c, SRH_ERR_HIP, "TTA scores workspace allocation failed");
+        if (c->emb_ws.ensure(nb_max * emb_per_tile * 4)) return fail(c, SRH_ERR_HIP, "TTA embeddings workspace allocation failed");
+    }
+    for (int j = 0; j < k; ++j) {     // summation order (orientation, tile); k == 1: the loop of every earlier ABI
+        const int orient = orients ? orients[j] : 0;
+        for (int off = 0; off < n_tiles; off += B) {
+            const int nb = std::min(B, n_tiles - off);
+            PatchParams pp;
+            pp.src = scene; pp.src_is_u8 = 1; pp.scene_W = W; pp.tile_xy = tile_xy + 2 * off;
+            const float* scores = c->scores_ws.as<float>();
+            if (orient) {             // oriented crop -> the same encoder and decoder -> scores back to the scene frame (scene_tta.hip)
+                TRY(encode_batch(c, w, pp, nb, nullptr, c->tta_scores_ws.as<float>(), c->emb_ws.as<float>(), s, orient, H));
+                TRYK(c, "scores_unorient", 0, (double)nb * P * P * 8 * 2, s,
+                     launch_scores_unorient(c->tta_scores_ws.as<float>(), nb, P, orient, c->scores_ws.as<float>(), s));
+            } else {
+                TRY(encode_batch(c, w, pp, nb, nullptr, c->scores_ws.as<float>(), embeddings_all + emb_per_tile * off, s));
+            }
+            if (has_window)      // FUSE_WINDOW (scene_window.hip): only this launch differs, the encoder and decoder are the same calls
+                TRYK(c, "scene_add_window", 0, (double)nb * P * P * 8 * 3, s,
+                     launch_scene_add_window(scores, nb, P, tile_xy + 2 * off, profile, canvas_kp, canvas_road, H, W, s));
+            else
+                TRYK(c, "scene_add", 0, (double)nb * P * P * 8 * 3, s,
+                     launch_scene_add(scores, nb, P, tile_xy + 2 * off, canvas_kp, canvas_road, H, W, s));
+        }
+    }
+    return 0;
+}
+
+extern "C" int srh_scene_pass1_hw(srh_ctx* c, const srh_weights* w, const uint8_t* scene, int H, int W, const int32_t* tile_xy,
+                                  int n_tiles, int B, float* canvas_kp, float* canvas_road, float* embeddings_all,
+                                  void* stream) {
+    return scene_pass1_impl(c, "srh_scene_pass1_hw", w, scene, H, W, tile_xy, n_tiles, B, canvas_kp, canvas_road, embeddings_all, stream);
+}
+
+extern "C" int srh_scene_pass1(srh_ctx* c, const srh_weights* w, const uint8_t* scene, int S, const int32_t* tile_xy,
+                               int n_tiles, int B, float* canvas_kp, float* canvas_road, float* embeddings_all,
+                               void* stream) {
+    return scene_pass1_impl(c, "srh_scene_pass1", w, scene, S, S, tile_xy, n_tiles, B, canvas_kp, canvas_road, embeddings_all, stream);
+}
+
+// valid (has_valid): the masks are also 0 on nodata — only the LAST launch differs; without it the two launches of every earlier ABI
+static int scene_normalise_impl(srh_ctx* c, const char* who, const float* canvas_kp, const float* canvas_road, int H, int W,
+                                const int32_t* tile_xy, int n_tiles, int P, uint8_t* kp_u8, uint8_t* road_u8, void* stream,
+                                bool has_valid = false, const uint8_t* valid = nullptr) {
+    if (!c || !canvas_kp || !canvas_road || !tile_xy || !kp_u8 || !road_u8 || (has_valid && !valid))
+        return fail(c, SRH_ERR_BAD_ARG, std::string(who) + ": null argument");
+    if (!scene_dims_ok(H, W) || n_tiles < 0 || P <= 0) return fail(c, SRH_ERR_BAD_ARG, std::string(who) + ": bad sizes");
+    hipSetDevice(c->device);
+    hipStream_t s = (hipStream_t)stream;
+    const size_t npx = (size_t)H * W;
+    if (c->counter.ensure(npx * 4)) return fail(c, SRH_ERR_HIP, "counter allocation failed");
+    TRYK(c, "scene_count", 0, (double)npx * 4, s, launch_scene_count(c->counter.as<float>(), H, W, tile_xy, n_tiles, P, s));
+    SceneNormParams np;
+    np.canvas_kp = canvas_kp; np.canvas_road = canvas_road; np.counter = c->counter.as<float>();
+    np.kp_u8 = kp_u8; np.road_u8 = road_u8; np.n = (int)npx;
+    if (has_valid) TRYK(c, "scene_norm_valid", 0, (double)npx * 15, s, launch_scene_normalise_valid(np, valid, s));
+    else TRYK(c, "scene_normalise", 0, (double)npx * 14, s, launch_scene_normalise(np, s));
+    return 0;
+}
+
+extern "C" int srh_scene_normalise_hw(srh_ctx* c, const float* canvas_kp, const float* canvas_road, int H, int W,
+                                      const int32_t* tile_xy, int n_tiles, int P, uint8_t* kp_u8, uint8_t* road_u8,
+                                      void* stream) {
+    return scene_normalise_impl(c, "srh_scene_normalise_hw", canvas_kp, canvas_road, H, W, tile_xy, n_tiles, P, kp_u8, road_u8, stream);
+}
+
+extern "C" int srh_scene_normalise(srh_ctx* c, const float* canvas_kp, const float* canvas_road, int S,
+                                   const int32_t* tile_xy, int n_tiles, int P, uint8_t* kp_u8, uint8_t* road_u8,
+                                   void* stream) {
+    return scene_normalise_impl(c, "srh_scene_normalise", canvas_kp, canvas_road, S, S, tile_xy, n_tiles, P, kp_u8, road_u8, stream);
+}
+
+// ---- scene level, validity mask (kernels in scene_valid.hip) -------------------------------------------------------------------
+extern "C" int srh_scene_tile_valid(srh_ctx* c, const uint8_t* valid, int H, int W, const int32_t* tile_xy, int n_tiles, int P,
+                                    int32_t* counts, void* stream) {
+    if (!c || !valid || !tile_xy || !counts) return fail(c, SRH_ERR_BAD_ARG, "srh_scene_tile_valid: null argument");
+    if (n_tiles < 0 || P < 32 || (P & 15) || H < P || W < P || !scene_dims_ok(H, W))
+        return fail(c, SRH_ERR_BAD_ARG, "srh_scene_tile_valid: bad sizes");
+    if (n_tiles == 0) return 0;
+    hipSetDevice(c->device);
+    hipStream_t s = (hipStream_t)stream;
+    TRYK(c, "tile_valid_count", 0, (double)n_tiles * P * P, s, launch_tile_valid_count(valid, H, W, tile_xy, n_tiles, P, counts, s));
+    return 0;
+}
+
+extern "C" int srh_scene_fill_invalid(srh_ctx* c, uint8_t* scene, const uint8_t* valid, int H, int W, int fill_r, int fill_g,
+                                      int fill_b, void* stream) {
+    if (!c || !scene || !valid) return fail(c, SRH_ERR_BAD_ARG, "srh_scene_fill_invalid: null argument");
+    if (!scene_dims_ok(H, W) || ((fill_r | fill_g | fill_b) & ~255)) return fail(c, SRH_ERR_BAD_ARG, "srh_scene_fill_invalid: bad sizes or fill colour");
+    hipSetDevice(c->device);
+    hipStream_t s = (hipStream_t)stream;
+    TRYK(c, "scene_fill_invalid", 0, (double)H * W, s, launch_scene_fill_invalid(scene, valid, H, W, fill_r, fill_g, fill_b, s));
+    return 0;
+}
+
+extern "C" int srh_scene_normalise_valid_hw(srh_ctx* c, const float* canvas_kp, const float* canvas_road, int H, int W,
+                                            const int32_t* tile_xy, int n_tiles, int P, const uint8_t* valid, uint8_t* kp_u8,
+                                            uint8_t* road_u8, void* stream) {
+    return scene_normalise_impl(c, "srh_scene_normalise_valid_hw", canvas_kp, canvas_road, H, W, tile_xy, n_tiles, P, kp_u8, road_u8, stream,
+                                true, valid);
+}
+
+// ---- scene level, window-weighted fusion (kernels in scene_window.hip, behaviour in DESIGN.md §6e) -----------------------------
+extern "C" int srh_scene_pass1_window_hw(srh_ctx* c, const srh_weights* w, const uint8_t* scene, int H, int W, const int32_t* tile_xy,
+                                         int n_tiles, int B, const float* profile, float* canvas_kp, float* canvas_road,
+                                         float* embeddings_all, void* stream) {
+    return scene_pass1_impl(c, "srh_scene_pass1_window_hw", w, scene, H, W, tile_xy, n_tiles, B, canvas_kp, canvas_road, embeddings_all, stream,
+                            true, profile);
+}
+
+extern "C" int srh_scene_normalise_window_hw(srh_ctx* c, const float* canvas_kp, const float* canvas_road, int H, int W,
+                                             const int32_t* tile_xy, int n_tiles, int P, const float* profile, const uint8_t* valid,
+                                             uint8_t* kp_u8, uint8_t* road_u8, void* stream) {
+    if (!c || !canvas_kp || !canvas_road || !tile_xy || !profile || !kp_u8 || !road_u8)
+        return fail(c, SRH_ERR_BAD_ARG, "srh_scene_normalise_window_hw: null argument");
+    if (!scene_dims_ok(H, W) || n_tiles < 0 || !tile_size_ok(P)) return fail(c, SRH_ERR_BAD_ARG, "srh_scene_normalise_window_hw: bad sizes");
+    hipSetDevice(c->device);
+    hipStream_t s = (hipStream_t)stream;
+    const double npx = (double)H * W;
+    // one kernel: the weight sum stays in a register (no counter canvas), so the context's counter workspace is not used
+    TRYK(c, "scene_norm_window", 0, npx * (valid ? 11 : 10), s,
+         launch_scene_normalise_window(canvas_kp, canvas_road, H, W, tile_xy, n_tiles, P, profile, valid, kp_u8, road_u8, s));
+    return 0;
+}
+
+// ---- scene level, test-time augmentation over tile orientations (kernels in scene_tta.hip, behaviour in DESIGN.md §6f) ----------------
+extern "C" int srh_scene_pass1_tta_hw(srh_ctx* c, const srh_weights* w, const uint8_t* scene, int H, int W, const int32_t* tile_xy,
+                                      int n_tiles, int B, const uint8_t* orients, int k, const float* profile, float* canvas_kp,
+                                      float* canvas_road, float* embeddings_all, void* stream) {
+    if (!orients) return fail(c, SRH_ERR_BAD_ARG, "srh_scene_pass1_tta_hw: null argument");
+    if (k < 1 || k > 8) return fail(c, SRH_ERR_BAD_ARG, "srh_scene_pass1_tta_hw: 1 to 8 orientations");
+    unsigned seen = 0;
+    for (int j = 0; j < k; ++j) {
+        if (orients[j] > 7) return fail(c, SRH_ERR_BAD_ARG, "srh_scene_pass1_tta_hw: an orientation code is 0 to 7");
+        if (seen & (1u << orients[j])) return fail(c, SRH_ERR_BAD_ARG, "srh_scene_pass1_tta_hw: an orientation is listed twice");
+        seen |= 1u << orients[j];
+    }
+    if (orients[0] != 0) return fail(c, SRH_ERR_BAD_ARG, "srh_scene_pass1_tta_hw: the first orientation must be id (0): its embeddings feed pass 2");
+    return scene_pass1_impl(c, "srh_scene_pass1_tta_hw", w, scene, H, W, tile_xy, n_tiles, B, canvas_kp, canvas_road, embeddings_all, stream,
+                            profile != nullptr, profile, orients, k);
+}
+

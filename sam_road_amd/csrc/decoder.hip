@@ -9,6 +9,7 @@
 // token form a quad tree (pixel, sub1, sub2, sub3) that one wave can walk in registers.
 #include "common.hpp"
 #include "kernels.hpp"
+#include "pack_layout.hpp"
 
 namespace srh {
 
@@ -20,7 +21,7 @@ namespace srh {
 // intermediates through HBM for 0.84 GFLOP per tile.
 // Organisation: the transposed MFMA chain of topo_fused.hip.  Y^T[feature, token] = W . X^T with v_mfma_f32_16x16x32_f16, A = a
 // packed 16 x 32 weight fragment, B = activations; a C tile pair of one layer IS the B operand of the next if the next layer's
-// weights are packed with the k permutation 8 g + j -> 16 (j >> 2) + 4 g + (j & 3) (api.hip pack_decoder_fused).  A wave job is
+// weights are packed with the k permutation 8 g + j -> 16 (j >> 2) + 4 g + (j & 3) (pack_host.hpp pack_decoder_fused).  A wave job is
 // 16 * NCG tokens (NCG column groups that share every A fragment read) and ONE first-level sub-pixel sub1 of them: its slice of layer 0 is 128 of the
 // 512 output columns, LayerNorm2d normalises exactly those 128 channels (lane-local + two cross-lane adds), and the three later
 // layers expand it depth-first — per second-level sub-pixel 64 -> 4 x 32 channels -> 4 x (2 x 2 pixels x 2 classes) — so at most 64
@@ -30,7 +31,9 @@ namespace srh {
 // GELU = gelu_fast (degree-5 exponent polynomial, common.hpp; the degree-3 one of the z192 bodies saved 2.5 us and cost 0.5e-4 of the 5e-4
 // mask-score bound in the randomised sweep: not taken).  Bound: VALU (58.7 M GELUs + 8.4 M sigmoids per 16 tiles) behind a serial
 // per-wave chain; HBM floor 8 MB in + 33.5 MB out.  Measured (profiles/r06_decoder_probe.txt): 39 us alone at B = 16, ~45 in the model.
-constexpr int DF_W0 = 65536, DF_W3 = 65536, DF_W5 = 16384, DF_PRM_BYTES = 3072, DF_LDS = DF_W0 + DF_W3 + DF_W5 + DF_PRM_BYTES;   // parameters: 738 floats, packed into 3 KiB (api.hip)
+// LDS: one sub1 slice of layer 0, layers 3 and 5, the parameters (738 floats, packed into 3 KiB); the layout is pack_layout.hpp's
+constexpr int DF_W0 = DF_FRAGS0 / 4 * FRAG_BYTES, DF_W3 = DF_FRAGS3 * FRAG_BYTES, DF_W5 = DF_FRAGS5 * FRAG_BYTES, DF_PRM_BYTES = DF_NPRM * 4,
+              DF_LDS = DF_W0 + DF_W3 + DF_W5 + DF_PRM_BYTES;
 // NCG column groups of 16 tokens per wave job x NW waves per workgroup: <2, 8> shares every fragment read between two column groups
 // (half the LDS traffic, 170 VGPRs: two waves per SIMD; measured 52 us in the model); <1, 16> — the one launched — has four waves per
 // SIMD (104 VGPRs) to hide the serial MFMA -> bias -> GELU -> pack -> MFMA chain of a job behind other waves' phases (47 -> ~42 us).
@@ -75,11 +78,11 @@ __global__ __launch_bounds__(DF_WAVES * 64) void decode_fused_kernel(DecodeFused
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
         const int ch = 16 * (j >> 2) + 4 * g + (j & 3);
-        const float v = n < 8 ? prm[480 + n * 32 + ch] : 0.f;
+        const float v = n < 8 ? prm[DF_P_W7 + n * 32 + ch] : 0.f;
         a7h[j] = (f16)v;
         a7l[j] = (f16)(v - (float)a7h[j]);
     }
-    const float b7a = prm[736], b7b = prm[737];
+    const float b7a = prm[DF_P_B7], b7b = prm[DF_P_B7 + 1];
 #define DF_FR(base, fi) (*reinterpret_cast<const f16x8*>((base) + (fi) * 1024 + lane * 16))
     const int S = p.S, P = S * 16;
     constexpr int JT = 16 * NCG;                                     // tokens per wave job
@@ -122,7 +125,7 @@ __global__ __launch_bounds__(DF_WAVES * 64) void decode_fused_kernel(DecodeFused
             float sum = 0.f;
 #pragma unroll
             for (int rt = 0; rt < 8; ++rt) {
-                const f32x4 b = *reinterpret_cast<const f32x4*>(prm + 16 * rt + 4 * g);
+                const f32x4 b = *reinterpret_cast<const f32x4*>(prm + DF_P_B0 + 16 * rt + 4 * g);
 #pragma unroll
                 for (int r = 0; r < 4; ++r) { a0[rt][cg][r] += b[r]; sum += a0[rt][cg][r]; }
             }
@@ -137,8 +140,8 @@ __global__ __launch_bounds__(DF_WAVES * 64) void decode_fused_kernel(DecodeFused
             const float rstd = rsqrtf(var + 1e-6f);
 #pragma unroll
             for (int rt = 0; rt < 8; ++rt) {
-                const f32x4 ga = *reinterpret_cast<const f32x4*>(prm + 128 + 16 * rt + 4 * g);
-                const f32x4 be = *reinterpret_cast<const f32x4*>(prm + 256 + 16 * rt + 4 * g);
+                const f32x4 ga = *reinterpret_cast<const f32x4*>(prm + DF_P_LN_G + 16 * rt + 4 * g);
+                const f32x4 be = *reinterpret_cast<const f32x4*>(prm + DF_P_LN_B + 16 * rt + 4 * g);
 #pragma unroll
                 for (int r = 0; r < 4; ++r) a0[rt][cg][r] = gelu_fast(a0[rt][cg][r] * rstd * ga[r] + be[r]);
             }
@@ -177,7 +180,7 @@ __global__ __launch_bounds__(DF_WAVES * 64) void decode_fused_kernel(DecodeFused
             for (int cg = 0; cg < NCG; ++cg) {
 #pragma unroll
                 for (int rt = 0; rt < 4; ++rt) {
-                    const f32x4 b = *reinterpret_cast<const f32x4*>(prm + 384 + 16 * rt + 4 * g);
+                    const f32x4 b = *reinterpret_cast<const f32x4*>(prm + DF_P_B3 + 16 * rt + 4 * g);
 #pragma unroll
                     for (int r = 0; r < 4; ++r) a3[rt][cg][r] = gelu_fast(a3[rt][cg][r] + b[r]);
                 }
@@ -201,7 +204,7 @@ __global__ __launch_bounds__(DF_WAVES * 64) void decode_fused_kernel(DecodeFused
                 }
 #pragma unroll
             for (int rt = 0; rt < 8; ++rt) {
-                const f32x4 b = *reinterpret_cast<const f32x4*>(prm + 448 + 16 * (rt & 1) + 4 * g);
+                const f32x4 b = *reinterpret_cast<const f32x4*>(prm + DF_P_B5 + 16 * (rt & 1) + 4 * g);
 #pragma unroll
                 for (int cg = 0; cg < NCG; ++cg)
 #pragma unroll

@@ -184,7 +184,7 @@ static void launch_ln(const NormParams& p, hipStream_t s) {
 
 int launch_layernorm(const NormParams& p, hipStream_t s) {
     if (p.M <= 0) return 0;
-    if (p.slices) {      // the small-M models' pass after a split-K fc2 (api.hip): its own instantiations, the others stay as they were
+    if (p.slices) {      // the small-M models' pass after a split-K fc2 (api_model.hip): its own instantiations, the others stay as they were
         if (p.delta16 || p.delta16b || p.nslices < 1 || !p.slice_bias) return -2;
         switch (p.D) {
             case 1024: launch_ln<16, 4, 1, 0, true>(p, s); break;

@@ -9,7 +9,7 @@
 //     A = a 16x32 weight fragment, B = the activations.  In the C/D layout lane l holds token (l & 15) and features
 //     16 t + 4 (l >> 4) + r of row tile t; the B operand of the NEXT MFMA wants, per lane, 8 k-values of a 32-wide k block.
 //     Two consecutive row tiles give exactly 8 values per lane, i.e. a C tile pair IS a B operand if k index 8 g + j is read
-//     as feature 32 kb + 16 (j >> 2) + 4 g + (j & 3).  That permutation is baked into the packed weights (api.hip,
+//     as feature 32 kb + 16 (j >> 2) + 4 g + (j & 3).  That permutation is baked into the packed weights (pack_host.hpp,
 //     pack_topo_fused), so GEMM -> GEMM chains need no LDS round trip, no shuffles: cvt_pk only.
 //   * For one sequence the same register image is also the A operand "rows = tokens": V is produced token-major,
 //     V[token, d] = X . Wv^T, by swapping the operands of the same MFMA with the same packed fragments.
@@ -23,12 +23,13 @@
 //     so the kernel is LDS-read bound (TF_NW x 16 KiB per chunk at 128 B/clk against 272 clk of MFMA per wave).
 #include "common.hpp"
 #include "kernels.hpp"
+#include "pack_layout.hpp"
 
 namespace srh {
 
 typedef __attribute__((address_space(3))) void* lds_vptr;
 
-constexpr int TF_CHUNK = 16384, TF_NBUF = 4, TF_RING = TF_CHUNK * TF_NBUF;
+constexpr int TF_CHUNK = TF_CHUNK_FRAGS * FRAG_BYTES, TF_NBUF = 4, TF_RING = TF_CHUNK * TF_NBUF;
 constexpr int TF_NW = 8;                      // waves (= sequences) per workgroup; each issues 16 / TF_NW DMA pieces per chunk
 
 __device__ __forceinline__ f32x4 mfma16k16(f16x4 a, f16x4 b, f32x4 c) {
@@ -86,7 +87,6 @@ __device__ __forceinline__ void tf_layernorm(f32x4 (&x)[8], const f32x4 (&y)[8],
 //           computes S^T against the G key tiles, softmax over G x 16 keys (lane-local over the tiles, then the xor-16 / 32
 //           exchanges) and O^T = sum_j V_j^T P_j^T.  Tokens 16 j + n >= K are pad tokens as above, but attend the sequence's keys.
 constexpr int TF_XSLOT = 8192;                // G >= 2 exchange slot per wave: V (8 tiles x 512 B), K^T (4 heads x 1 KiB)
-constexpr int tf_nprm(int nl) { return 128 + 1280 * nl + 132; }
 constexpr int tf_lds(int nl, int G) { return TF_RING + tf_nprm(nl) * 4 + (G >= 2 ? TF_NW * TF_XSLOT + TF_NW * 4 : 0); }
 __host__ __device__ constexpr int tf_log2_ceil(int k) { int l = 0; while ((1 << l) < k) ++l; return l; }
 static_assert(tf_nprm(3) % 4 == 0 && tf_nprm(0) % 4 == 0, "exchange area alignment");
@@ -97,7 +97,7 @@ __global__ __launch_bounds__(TF_NW * 64) void topo_fused_kernel(TopoFusedParams 
     char* const ring = smem;
     float* const prm = reinterpret_cast<float*>(smem + TF_RING);
     char* const xch = smem + TF_RING + tf_nprm(NL) * 4;                  // G >= 2: TF_NW slots, then TF_NW tile valid masks
-    constexpr int NCH = 5 + 12 * NL;
+    constexpr int NCH = tf_nfrag(NL) / TF_CHUNK_FRAGS;
     constexpr int NPRM = tf_nprm(NL);
     constexpr int GT = G > 1 ? G : 1;                                     // key tiles per query
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -213,7 +213,7 @@ __global__ __launch_bounds__(TF_NW * 64) void topo_fused_kernel(TopoFusedParams 
             }
 #pragma unroll
             for (int t = 0; t < 8; ++t) {
-                const f32x4 b = TF_B4(16 * t + 4 * g);
+                const f32x4 b = TF_B4(TF_P_PAIR_B + 16 * t + 4 * g);
 #pragma unroll
                 for (int r = 0; r < 4; ++r) xs[t][r] = fmaxf(acc[t][r] + b[r], 0.f);
             }
@@ -223,7 +223,7 @@ __global__ __launch_bounds__(TF_NW * 64) void topo_fused_kernel(TopoFusedParams 
 
 #pragma unroll
         for (int L = 0; L < NL; ++L) {
-            const int FB = 80 + 192 * L, CB = 5 + 12 * L, PB = 128 + 1280 * L;
+            const int FB = tf_nfrag(L), CB = FB / TF_CHUNK_FRAGS, PB = tf_pb(L);
             // ---- V, token-major: V[key, d] = X . Wv^T  (A = the sequence, B = the packed fragment), 8 d tiles
             f16x4 vp[8];
 #pragma unroll
@@ -234,8 +234,8 @@ __global__ __launch_bounds__(TF_NW * 64) void topo_fused_kernel(TopoFusedParams 
                     const int c = 4 * q + cc;
                     f32x4 a = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-                    for (int kb = 0; kb < 4; ++kb) a = mfma16(xp[kb], TF_FR(FB + c * 4 + kb), a);
-                    const float bv = prm[PB + 256 + 16 * c + n];
+                    for (int kb = 0; kb < 4; ++kb) a = mfma16(xp[kb], TF_FR(FB + TF_F_V + c * 4 + kb), a);
+                    const float bv = prm[PB + TF_P_QKV_B + 256 + 16 * c + n];
 #pragma unroll
                     for (int r = 0; r < 4; ++r) a[r] += bv;
                     vp[c] = tf_pack4(a);
@@ -252,8 +252,8 @@ __global__ __launch_bounds__(TF_NW * 64) void topo_fused_kernel(TopoFusedParams 
                 for (int i = 0; i < 4; ++i) {
                     qk[i] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-                    for (int kb = 0; kb < 4; ++kb) qk[i] = mfma16(TF_FR(FB + 32 + 16 * h + i * 4 + kb), xp[kb], qk[i]);
-                    const f32x4 b = TF_B4(PB + (i >> 1) * 128 + 16 * (2 * h + (i & 1)) + 4 * g);
+                    for (int kb = 0; kb < 4; ++kb) qk[i] = mfma16(TF_FR(FB + TF_F_QK + 16 * h + i * 4 + kb), xp[kb], qk[i]);
+                    const f32x4 b = TF_B4(PB + TF_P_QKV_B + (i >> 1) * 128 + 16 * (2 * h + (i & 1)) + 4 * g);
 #pragma unroll
                     for (int r = 0; r < 4; ++r) qk[i][r] += b[r];
                 }
@@ -321,13 +321,13 @@ __global__ __launch_bounds__(TF_NW * 64) void topo_fused_kernel(TopoFusedParams 
                     const int t = 4 * q + tt;
                     f32x4 a = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-                    for (int kb = 0; kb < 4; ++kb) a = mfma16(TF_FR(FB + 96 + t * 4 + kb), op[kb], a);
-                    const f32x4 b = TF_B4(PB + 384 + 16 * t + 4 * g);
+                    for (int kb = 0; kb < 4; ++kb) a = mfma16(TF_FR(FB + TF_F_OUT + t * 4 + kb), op[kb], a);
+                    const f32x4 b = TF_B4(PB + TF_P_OUT_B + 16 * t + 4 * g);
 #pragma unroll
                     for (int r = 0; r < 4; ++r) y[t][r] = a[r] + b[r] + xs[t][r];
                 }
             }
-            tf_layernorm(xs, y, prm + PB + 512, prm + PB + 640, g);
+            tf_layernorm(xs, y, prm + PB + TF_P_LN1_G, prm + PB + TF_P_LN1_B, g);
 #pragma unroll
             for (int kb = 0; kb < 4; ++kb) xp[kb] = tf_pack8(xs[2 * kb], xs[2 * kb + 1]);
             // ---- FFN: relu(W1 x + b1), W2 h + b2 + residual -> LayerNorm 2
@@ -341,8 +341,8 @@ __global__ __launch_bounds__(TF_NW * 64) void topo_fused_kernel(TopoFusedParams 
                     const int t = 4 * q + tt;
                     f32x4 a = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-                    for (int kb = 0; kb < 4; ++kb) a = mfma16(TF_FR(FB + 128 + t * 4 + kb), xp[kb], a);
-                    const f32x4 b = TF_B4(PB + 768 + 16 * t + 4 * g);
+                    for (int kb = 0; kb < 4; ++kb) a = mfma16(TF_FR(FB + TF_F_FC1 + t * 4 + kb), xp[kb], a);
+                    const f32x4 b = TF_B4(PB + TF_P_FC1_B + 16 * t + 4 * g);
 #pragma unroll
                     for (int r = 0; r < 4; ++r) hh[tt][r] = fmaxf(a[r] + b[r], 0.f);
                 }
@@ -357,13 +357,13 @@ __global__ __launch_bounds__(TF_NW * 64) void topo_fused_kernel(TopoFusedParams 
                     const int t = 4 * q + tt;
                     f32x4 a = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-                    for (int kb = 0; kb < 4; ++kb) a = mfma16(TF_FR(FB + 160 + t * 4 + kb), hp[kb], a);
-                    const f32x4 b = TF_B4(PB + 896 + 16 * t + 4 * g);
+                    for (int kb = 0; kb < 4; ++kb) a = mfma16(TF_FR(FB + TF_F_FC2 + t * 4 + kb), hp[kb], a);
+                    const f32x4 b = TF_B4(PB + TF_P_FC2_B + 16 * t + 4 * g);
 #pragma unroll
                     for (int r = 0; r < 4; ++r) y[t][r] = a[r] + b[r] + xs[t][r];
                 }
             }
-            tf_layernorm(xs, y, prm + PB + 1024, prm + PB + 1152, g);
+            tf_layernorm(xs, y, prm + PB + TF_P_LN2_G, prm + PB + TF_P_LN2_B, g);
 #pragma unroll
             for (int kb = 0; kb < 4; ++kb) xp[kb] = tf_pack8(xs[2 * kb], xs[2 * kb + 1]);
         }
@@ -372,11 +372,11 @@ __global__ __launch_bounds__(TF_NW * 64) void topo_fused_kernel(TopoFusedParams 
         float d = 0.f;
 #pragma unroll
         for (int t = 0; t < 8; ++t) {
-            const f32x4 wv = TF_B4(128 + 1280 * NL + 16 * t + 4 * g);
+            const f32x4 wv = TF_B4(tf_pb(NL) + 16 * t + 4 * g);
 #pragma unroll
             for (int r = 0; r < 4; ++r) d = fmaf(xs[t][r], wv[r], d);
         }
-        d = tf_sum4(d) + prm[128 + 1280 * NL + 128];
+        d = tf_sum4(d) + prm[tf_pb(NL) + 128];
         if (G == 0 ? live && g == 0 : orow >= 0 && g == 0) {
             const size_t o = G == 0 ? (size_t)seq * 16 + n : (size_t)orow;
             if (p.logits) p.logits[o] = d;

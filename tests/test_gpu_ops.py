@@ -138,7 +138,7 @@ _MLP_SHAPES = [(8192, 768, 3072), (12288, 768, 3072), (16384, 768, 3072), (65536
 
 @pytest.mark.parametrize("M,D,H", _MLP_SHAPES)
 def test_gemm_z192_blocked_fc1_body(ctx, M, D, H):
-    """gemm_z192_kernel<3> — what the model's fc1 runs (csrc/api.hip: GELU, hidden activation WRITTEN in the blocked-16 layout) — alone,
+    """gemm_z192_kernel<3> — what the model's fc1 runs (csrc/api_model.hip: GELU, hidden activation WRITTEN in the blocked-16 layout) — alone,
     against fp32 torch; and bit-identical to the row-major GELU body (kernel<1>) on the same operands."""
     from sam_road_amd._lib import SRH_GEMM_OUT_BLOCKED16
     A, W1, _, b1, _ = _mlp_operands(M, D, H, M + H)
@@ -181,7 +181,7 @@ def test_gemm_z192_blocked_fc2_body(ctx, M, D, H):
 @pytest.mark.parametrize("M,D,H", _MLP_SHAPES)
 def test_gemm_z192_mlp_pair_blocked_hidden(ctx, M, D, H):
     """fc1 (body 3) -> fc2 (body 2) with the hidden activation handed over in the blocked-16 layout, exactly as srh_encode_decode
-    chains them (csrc/api.hip; reference: the SAM fork's MLPBlock via model.py:245-258), against fp32 torch on the fp16-rounded hidden
+    chains them (csrc/api_model.hip; reference: the SAM fork's MLPBlock via model.py:245-258), against fp32 torch on the fp16-rounded hidden
     activation — and against the row-major pair bit for bit."""
     from sam_road_amd._lib import SRH_GEMM_A_BLOCKED16, SRH_GEMM_OUT_BLOCKED16
     A, W1, W2, b1, b2 = _mlp_operands(M, D, H, M + D + H)

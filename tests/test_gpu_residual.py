@@ -1,5 +1,5 @@
 """Op-level tests of the residual-stream passes (through the C ABI's test-only exports srh_op_layernorm_ex, srh_op_gemm_partials and
-srh_op_gemm_pos): every fused mode of layernorm_kernel that encode_batch (api.hip) chooses among — x + delta16, (x + delta16) +
+srh_op_gemm_pos): every fused mode of layernorm_kernel that encode_batch (api_model.hip) chooses among — x + delta16, (x + delta16) +
 delta16b, pos_embed[row % period] + delta16, the split-K fold, the cast-only fold, the non-finite sentinel — and the two GEMM modes
 that feed them (deferred split-K partials, the f32 + pos epilogue).
 

@@ -56,7 +56,7 @@ def bench_attn(sizes, B, iters):
             ctx.check(ctx.lib.srh_op_attention(ctx.handle, _p(qkv), _p(rel_h), _p(rel_w), _p(bias), B, S, heads, S, _p(out), None),
                       "srh_op_attention")
         ms = _time(run, iters, 3)
-        flops = 4.0 * B * heads * S ** 4 * hd          # the two products over the real S^2 x S^2 scores (as api.hip attn_flops)
+        flops = 4.0 * B * heads * S ** 4 * hd          # the two products over the real S^2 x S^2 scores (as api_model.hip attn_flops)
         print(json.dumps({"op": "global_attention", "patch": 16 * S, "S": S, "B": B, "heads": heads, "hd": hd, "ms": round(ms, 4),
                           "tflops": round(flops / (ms * 1e-3) / 1e12, 1), "lib": os.path.basename(os.path.dirname(_lib.LIB_PATH))}),
               flush=True)
