@@ -234,6 +234,23 @@ int srh_op_patch_im2col(srh_ctx* ctx, const uint8_t* scene_u8, int H, int W, con
                         void* out_f16, void* stream);
 int srh_op_scores_unorient(srh_ctx* ctx, const float* scores_in, int n, int P, int orient, float* scores_out, void* stream);
 
+/* Scene border padding (config key SCENE_PAD; an extension).  One additive entry; the ABI number stays 11 because nothing
+ * existing changes, and a scene without the key does not call it.
+ *
+ * srh_scene_pad: dst u8 [H + top + bottom, W + left + right, C] = src u8 [H, W, C] (both on the device, dense rows, any byte address, not
+ *   overlapping) with the four borders added: pixel (Y, X) of dst holds pixel (f(Y - top, H), f(X - left, W)) of src, where for an axis of n
+ *   pixels SRH_PAD_REFLECT folds i with period T = 2 (n - 1): i mod T if that is below n, else T - (i mod T) (n = 1: always 0) — numpy's
+ *   pad mode "reflect" for any pad width; SRH_PAD_EDGE clamps i to [0, n - 1]; SRH_PAD_CONSTANT takes fill_rgb (HOST array of three ints,
+ *   C = 1 uses the first) wherever i falls outside [0, n).  Every byte of dst is written exactly once and nothing else is.  C must be 3
+ *   (a scene) or 1 (a validity mask), the pads >= 0, mode one of the three, H, W >= 1, H * W and the padded size <= 2^31 - 1 pixels and,
+ *   where fill_rgb is given, its values 0..255 (it may be NULL unless mode is SRH_PAD_CONSTANT): else SRH_ERR_BAD_ARG and nothing is
+ *   launched.  The call touches no workspace of the context. */
+#define SRH_PAD_REFLECT 0
+#define SRH_PAD_EDGE 1
+#define SRH_PAD_CONSTANT 2
+int srh_scene_pad(srh_ctx* ctx, const uint8_t* src, int H, int W, int C, int top, int bottom, int left, int right, int mode,
+                  const int32_t* fill_rgb, uint8_t* dst, void* stream);
+
 /* op level (used by the parity tests to localise a failure; same kernels as above) ----------------- */
 
 /* out = act(A[M,K] W[N,K]^T + bias) (+resid); A,W fp16; N%128==0, K%64==0. act: 0/1 GELU/2 ReLU. */

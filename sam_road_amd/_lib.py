@@ -13,6 +13,7 @@ LIB_PATH = os.environ.get("SRH_LIB_PATH") or os.path.join(_HERE, "libsamroad_hip
 SRH_F32, SRH_F16, SRH_U8, SRH_I32, SRH_I64 = 0, 1, 2, 3, 4
 ABI_VERSION = 11
 SRH_GEMM_A_BLOCKED16, SRH_GEMM_OUT_BLOCKED16 = 1, 2       # srh_op_gemm_ex flags (include/samroad_hip.h)
+SRH_PAD_MODES = {"reflect": 0, "edge": 1, "constant": 2}  # srh_scene_pad modes (SRH_PAD_*)
 
 
 class SrhError(RuntimeError):
@@ -71,6 +72,7 @@ SYMBOLS = {
     "srh_scene_normalise_window_hw": (_I, [_P, _P, _P, _I, _I, _P, _I, _I, _P, _P, _P, _P, _P]),
     "srh_op_scene_fuse_window": (_I, [_P, _P, _I, _I, _P, _P, _P, _P, _I, _I, _P]),
     "srh_scene_pass1_tta_hw": (_I, [_P, _P, _P, _I, _I, _P, _I, _I, _P, _I, _P, _P, _P, _P, _P]),
+    "srh_scene_pad": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P]),
     "srh_op_patch_im2col": (_I, [_P, _P, _I, _I, _P, _I, _I, _I, _P, _P]),
     "srh_op_scores_unorient": (_I, [_P, _P, _I, _I, _I, _P, _P]),
     "srh_op_gemm": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P]),

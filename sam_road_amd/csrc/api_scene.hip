@@ -161,3 +161,24 @@ extern "C" int srh_scene_pass1_tta_hw(srh_ctx* c, const srh_weights* w, const ui
                             profile != nullptr, profile, orients, k);
 }
 
+
+// ---- scene level, border padding (kernel in scene_pad.hip, behaviour in DESIGN.md §6g) ------------------------------------------------
+static_assert(SRH_PAD_REFLECT == PAD_REFLECT && SRH_PAD_EDGE == PAD_EDGE && SRH_PAD_CONSTANT == PAD_CONSTANT, "pad modes of the header and the kernel");
+
+extern "C" int srh_scene_pad(srh_ctx* c, const uint8_t* src, int H, int W, int C, int top, int bottom, int left, int right, int mode,
+                             const int32_t* fill_rgb, uint8_t* dst, void* stream) {
+    if (!c || !src || !dst || (mode == SRH_PAD_CONSTANT && !fill_rgb)) return fail(c, SRH_ERR_BAD_ARG, "srh_scene_pad: null argument");
+    if ((C != 1 && C != 3) || mode < SRH_PAD_REFLECT || mode > SRH_PAD_CONSTANT) return fail(c, SRH_ERR_BAD_ARG, "srh_scene_pad: bad channel count or mode");
+    const long long Hv = (long long)H + top + bottom, Wv = (long long)W + left + right;
+    if (top < 0 || bottom < 0 || left < 0 || right < 0 || !scene_dims_ok(H, W) || Hv > 2147483647LL || Wv > 2147483647LL ||
+        !scene_dims_ok((int)Hv, (int)Wv))
+        return fail(c, SRH_ERR_BAD_ARG, "srh_scene_pad: bad sizes");
+    if (fill_rgb && ((fill_rgb[0] | fill_rgb[1] | fill_rgb[2]) & ~255)) return fail(c, SRH_ERR_BAD_ARG, "srh_scene_pad: bad fill colour");
+    hipSetDevice(c->device);
+    hipStream_t s = (hipStream_t)stream;
+    ScenePadParams p;
+    p.src = src; p.dst = dst; p.H = H; p.W = W; p.Hv = (int)Hv; p.Wv = (int)Wv; p.top = top; p.left = left; p.C = C; p.mode = mode;
+    if (fill_rgb) p.fill = (uint32_t)fill_rgb[0] | ((uint32_t)fill_rgb[1] << 8) | ((uint32_t)fill_rgb[2] << 16);
+    TRYK(c, "scene_pad", 0, ((double)H * W + (double)Hv * Wv) * C, s, launch_scene_pad(p, s));
+    return 0;
+}

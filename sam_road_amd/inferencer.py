@@ -573,7 +573,8 @@ def neighbor_queries(config):
 
 
 def _scene_plan(img, config):
-    """Validated scene + its tile list (inferencer.py:63-76): (img u8 [H,W,3], infos, tile origins int32 [n,2] (x0, y0)).
+    """Validated scene + its tile list (inferencer.py:63-76): (img u8 [H,W,3], infos, tile origins int32 [n,2] (x0, y0)) — under
+    SCENE_PAD infos and origins are those of the padded scene (scene_pad_plan(img.shape, config) says how it is padded).
     H and W are independent; the reference's tile rule is applied per axis (tiling.get_patch_info_hw), and
     INFER_PATCHES_PER_EDGE may be an int or [n_y, n_x].  Everything that can be refused is refused here, before the device is
     touched."""
@@ -583,19 +584,26 @@ def _scene_plan(img, config):
     # non-square scene and silently convert a non-u8 one.  Here H and W are separate all the way down; non-u8 is refused
     if img.ndim != 3 or img.shape[2] != 3 or img.dtype != np.uint8:
         raise ValueError(f"infer_one_img expects an HxWx3 uint8 scene, got {img.dtype} {tuple(img.shape)}")
-    infos, all_xy = _tile_plan(int(img.shape[0]), int(img.shape[1]), config)
+    if img.shape[0] < 1 or img.shape[1] < 1:
+        raise ValueError(f"infer_one_img expects a scene of at least 1 x 1 pixels, got {tuple(img.shape)}")
+    pad = scene_pad_plan(img.shape, config)
+    top, bottom, left, right = pad[:4] if pad is not None else (0, 0, 0, 0)
+    # SCENE_PAD: the tiles are planned on the virtual (padded) scene; infos / origins are in ITS frame
+    infos, all_xy = _tile_plan(int(img.shape[0]) + top + bottom, int(img.shape[1]) + left + right, config, padded=pad is not None)
     return img, infos, all_xy
 
 
-def _tile_plan(H, W, config, stacklevel=3):
+def _tile_plan(H, W, config, stacklevel=3, padded=False):
     """The candidate tiles of an H x W scene: (infos, tile origins int32 [n,2] (x0, y0)), or ValueError.  A stride warning is attributed to
-    the caller of this function's caller (stacklevel): whoever called _scene_plan or scene_tiles."""
+    the caller of this function's caller (stacklevel): whoever called _scene_plan or scene_tiles.  padded: H x W is the virtual size of a
+    scene under SCENE_PAD (only the wording of the size limit differs: such a scene is never too small)."""
     P, m = int(config.PATCH_SIZE), int(config.SAMPLE_MARGIN or 0)
     for axis, size in (("height", H), ("width", W)):
         if size < P + 2 * m:
-            raise ValueError(f"scene {axis} {size} px is smaller than PATCH_SIZE + 2 * SAMPLE_MARGIN = {P + 2 * m}")
+            raise ValueError(f"scene {axis} {size} px is smaller than PATCH_SIZE + 2 * SAMPLE_MARGIN = {P + 2 * m} (the config key SCENE_PAD "
+                             f"pads such a scene at its borders)")
     if H * W > 2 ** 31 - 1:
-        raise ValueError(f"scene {H} x {W} has more than 2^31 - 1 pixels")
+        raise ValueError(f"scene {H} x {W}{' (padded by SCENE_PAD)' if padded else ''} has more than 2^31 - 1 pixels")
     n_y, n_x = patches_per_axis(config.INFER_PATCHES_PER_EDGE)
     for axis, size, n in (("height", H, n_y), ("width", W, n_x)):
         span = size - P - 2 * m                        # first to last tile origin
@@ -634,10 +642,73 @@ def _valid_plan(valid, shape_hw, config):
     frac = 0.0 if _absent(config.MIN_VALID_FRACTION) else config.MIN_VALID_FRACTION
     if not (_is_int(frac) or isinstance(frac, (float, np.floating))) or not 0.0 <= float(frac) <= 1.0:        # NaN fails the range
         raise ValueError(f"MIN_VALID_FRACTION must be a number in [0, 1], got {frac!r}")
+    return np.ascontiguousarray(valid).view(np.uint8), float(frac), _nodata_fill(config)
+
+
+def _nodata_fill(config):
+    """config.NODATA_FILL as three ints 0..255 (missing key: the rounded pixel mean), or ValueError."""
     fill = NODATA_FILL_DEFAULT if _absent(config.NODATA_FILL) else config.NODATA_FILL
     if not isinstance(fill, (list, tuple, np.ndarray)) or len(fill) != 3 or not all(_is_int(v) and 0 <= v <= 255 for v in fill):
         raise ValueError(f"NODATA_FILL must be three ints in 0..255, got {fill!r}")
-    return np.ascontiguousarray(valid).view(np.uint8), float(frac), tuple(int(v) for v in fill)
+    return tuple(int(v) for v in fill)
+
+
+# ---- scenes padded at their borders (SCENE_PAD) --------------------------------------------------------------------------------------
+SCENE_PAD_MODES = ("reflect", "edge", "constant")
+
+
+def scene_pad_key(config):
+    """config.SCENE_PAD (extension key) as (b_y, b_x, mode), or None for a missing key / None: nothing changes anywhere.
+    An int b >= 0 means {border: b}; otherwise a mapping with `border` (an int or [b_y, b_x], values >= 0, default 0) and `mode` (one of
+    SCENE_PAD_MODES, default 'reflect').  ValueError — before the device is touched — for anything else, unknown mapping keys included."""
+    v = config.SCENE_PAD
+    if _absent(v):                                       # None, or the empty node of a missing key (an empty mapping written out counts as that)
+        return None
+    if _is_int(v):
+        v = {"border": v}
+    if not isinstance(v, dict):
+        raise ValueError(f"SCENE_PAD must be an int >= 0 or a mapping with border / mode, got {v!r}")
+    unknown = sorted(set(v) - {"border", "mode"}, key=str)
+    if unknown:
+        raise ValueError(f"SCENE_PAD: unknown key {unknown[0]!r} (border, mode)")
+    b = v.get("border", 0)
+    if _is_int(b):
+        b = [b, b]
+    if not isinstance(b, (list, tuple)) or len(b) != 2 or not all(_is_int(x) and 0 <= x <= 2 ** 31 - 1 for x in b):
+        raise ValueError(f"SCENE_PAD: border must be an int >= 0 or [b_y, b_x] of two such ints, got {v.get('border')!r}")
+    mode = v.get("mode", "reflect")
+    name = mode.strip().lower() if isinstance(mode, str) else mode
+    if not isinstance(name, str) or name not in SCENE_PAD_MODES:
+        raise ValueError(f"SCENE_PAD: mode must be one of {SCENE_PAD_MODES}, got {mode!r}")
+    return int(b[0]), int(b[1]), name
+
+
+def scene_pad_plan(shape, config):
+    """How a scene of `shape` = (H, W[, 3]) is padded under config.SCENE_PAD: (top, bottom, left, right, mode, fill), or None when the key
+    is absent (scene_pad_key).  Per axis the border b is added on both sides, and what the scene still lacks to hold one tile, short =
+    max(0, PATCH_SIZE + 2 SAMPLE_MARGIN - (n + 2 b)), is split short // 2 before and the rest after.  fill: config.NODATA_FILL (the
+    colour of `constant` padding), checked here.  The virtual scene is (H + top + bottom) x (W + left + right); its size limit is
+    checked where the tiles are planned.  All four pads 0: the run is that of a scene without the key."""
+    key = scene_pad_key(config)
+    if key is None:
+        return None
+    b_y, b_x, mode = key
+    need = int(config.PATCH_SIZE) + 2 * int(config.SAMPLE_MARGIN or 0)
+    out = []
+    for n, b in ((int(shape[0]), b_y), (int(shape[1]), b_x)):
+        if n < 1:
+            raise ValueError(f"a scene has at least 1 x 1 pixels, got shape {tuple(shape)}")
+        short = max(0, need - (n + 2 * b))
+        out += [b + short // 2, b + short - short // 2]
+    return (*out, mode, _nodata_fill(config))
+
+
+def scene_pad_override(config, border=None, mode=None):
+    """The SCENE_PAD mapping of the command line's --scene-pad B / --scene-pad-mode MODE laid over the config's key: a flag that is given
+    replaces that field, the other field stays as the config has it (defaults: border 0, reflect)."""
+    key = scene_pad_key(config)
+    b_y, b_x, m = key if key is not None else (0, 0, "reflect")
+    return {"border": [b_y, b_x] if border is None else border, "mode": m if mode is None else mode}
 
 
 def select_tiles(counts, patch_size, min_valid_fraction):
@@ -653,21 +724,38 @@ def scene_tiles(shape, config, valid=None, net=None):
     """The tiles infer_one_img runs for a scene of `shape` = (H, W[, 3]): the list of (0, (x0, y0), (x1, y1)) in the reference's
     x-outer / y-inner order.  With `valid` (see infer_one_img) only the kept tiles, selected exactly as infer_one_img selects them: the
     counts come from `net.scene_tile_valid` on the model's device, so `net` is required then (there is no host fallback).  The list is
-    a TilePlan: its `orientations` are the names of config.TTA (['id'] without the key) — every tile of the list runs once per name."""
+    a TilePlan: its `orientations` are the names of config.TTA (['id'] without the key) — every tile of the list runs once per name.
+    Under config.SCENE_PAD the tiles are those of the padded scene in the frame of the REAL one — origin (x0 - left, y0 - top), so a tile
+    may start below 0 or overhang — and `pads` holds (top, bottom, left, right); the mask is padded like the scene before it is counted."""
     neighbor_queries(config)
     if len(shape) not in (2, 3) or (len(shape) == 3 and shape[2] != 3):
         raise ValueError(f"shape must be (H, W) or (H, W, 3), got {tuple(shape)}")
     H, W = int(shape[0]), int(shape[1])
     orientations = tta_plan(config)[0]
-    infos, all_xy = _tile_plan(H, W, config)
+    if H < 1 or W < 1:
+        raise ValueError(f"a scene has at least 1 x 1 pixels, got shape {tuple(shape)}")
+    pad = scene_pad_plan((H, W), config)
+    pads = pad[:4] if pad is not None else (0, 0, 0, 0)
+    infos, all_xy = _tile_plan(H + pads[0] + pads[1], W + pads[2] + pads[3], config, padded=pad is not None)
     if valid is None:
-        return TilePlan(infos, orientations)
+        return TilePlan(_shift_infos(infos, pads), orientations, pads)
     v8, frac, _ = _valid_plan(valid, (H, W), config)
     if net is None:
         raise ValueError("scene_tiles needs the model (net=) to count valid pixels on the device")
     device = next(net.parameters()).device
-    counts = net.scene_tile_valid(torch.from_numpy(v8).to(device), torch.as_tensor(all_xy).to(device)).cpu().numpy()
-    return TilePlan([infos[i] for i in select_tiles(counts, config.PATCH_SIZE, frac)], orientations)
+    valid_d = torch.from_numpy(v8).to(device)
+    if any(pads):
+        valid_d = net.scene_pad(valid_d, pads, pad[4], (0, 0, 0))
+    counts = net.scene_tile_valid(valid_d, torch.as_tensor(all_xy).to(device)).cpu().numpy()
+    return TilePlan(_shift_infos([infos[i] for i in select_tiles(counts, config.PATCH_SIZE, frac)], pads), orientations, pads)
+
+
+def _shift_infos(infos, pads):
+    """Tiles of the padded scene in the frame of the real one: every corner moved by (-left, -top)."""
+    top, _, left, _ = pads
+    if not top and not left:
+        return infos
+    return [(k, (x0 - left, y0 - top), (x1 - left, y1 - top)) for k, (x0, y0), (x1, y1) in infos]
 
 
 # ---- window-weighted fusion of overlapping tiles (FUSE_WINDOW) ----------------------------------------------------------------------
@@ -780,11 +868,13 @@ def tta_plan(config):
 
 
 class TilePlan(list):
-    """What scene_tiles returns: the list of tiles, and in `orientations` the names every one of them is run in."""
+    """What scene_tiles returns: the list of tiles, in `orientations` the names every one of them is run in, and in `pads` the (top, bottom,
+    left, right) of SCENE_PAD (zeros without it)."""
 
-    def __init__(self, infos, orientations):
+    def __init__(self, infos, orientations, pads=(0, 0, 0, 0)):
         super().__init__(infos)
         self.orientations = list(orientations)
+        self.pads = tuple(int(v) for v in pads)
 
 
 def _empty_result(H, W):
@@ -872,7 +962,7 @@ class _Lane:
 class _BlockingIO:
     """How infer_one_img and the tile-sharded loops move a scene's arrays: one blocking copy each way, pageable memory.  The other
     implementation of the same four operations is _LaneIO.  `lap` (a _Laps) names the steps of pass 1 for the profile."""
-    STEPS = {"upload": "scene upload", "select": "tile selection (count kernel + counts D2H)", "fill": "nodata fill",
+    STEPS = {"upload": "scene upload", "pad": "scene pad", "select": "tile selection (count kernel + counts D2H)", "fill": "nodata fill",
              "pass 1": "pass 1 (GPU)"}
     alloc = None                                       # the pass-2 collate fills plain numpy arrays
 
@@ -885,7 +975,7 @@ class _BlockingIO:
 
     upload_packed = upload                             # an array that `alloc` supplied and the collate filled
 
-    def counts(self, fn):
+    def counts(self, fn, after_compute=False):
         """fn() -> the valid-pixel counts on the device; returns them on the host (int32 [n]) after one wait."""
         return fn().cpu().numpy()
 
@@ -898,7 +988,7 @@ class _LaneIO:
     """The operations of _BlockingIO on infer_imgs' lane, for ONE scene in flight (`pool`: its page-locked staging): uploads are staged
     and stream-ordered, the counts come back over the copy stream, the pass-2 collate writes straight into the staging buffers.  With the
     profile on, five device events time the scene's pass 1, pass 2 and score download."""
-    STEPS = {"upload": "stage + queue scene upload", "select": "tile selection (upload lane)", "pass 1": "queue pass 1"}
+    STEPS = {"upload": "stage + queue scene upload", "pad": "queue scene pad", "select": "tile selection (upload lane)", "pass 1": "queue pass 1"}
     EVENTS = {"launch pass 1": 0, "normalised": 1, "pass 2 uploaded": 2, "pass 2 launched": 3, "pass 2 on its way back": 4}
 
     def __init__(self, lane, pool, lap):
@@ -915,7 +1005,10 @@ class _LaneIO:
     def upload_packed(self, name, arr):
         return self.lane.upload_staged(self.stage[name][:arr.shape[0]])
 
-    def counts(self, fn):
+    def counts(self, fn, after_compute=False):
+        # after_compute: fn reads what the compute stream produced (the padded mask of SCENE_PAD), so the upload lane waits for it first
+        if after_compute and self.lane.cuda:
+            self.lane.copy_stream.wait_stream(torch.cuda.current_stream(self.lane.device))
         # on the upload lane: the count kernel uses no workspace of the library context, so it and the n int32 on their way back are
         # queued on the copy stream.  Like every upload of this lane they start after what the compute stream holds at this moment (the
         # previous scene's TopoNet work, about a millisecond), and the host waits for the counts
@@ -954,9 +1047,10 @@ class _SceneSetup:
 @dataclasses.dataclass
 class _SceneJob:
     """One scene from pass 1 to its result."""
-    shape: tuple                      # (H, W)
-    infos: list                       # the tiles that run (the kept ones under a mask) and their origins int32 [n,2] (x0, y0)
-    all_xy: np.ndarray
+    shape: tuple                      # (H, W) of the real scene: what the masks and the nodes refer to
+    infos: list                       # the tiles that run (the kept ones under a mask), in the frame of the real scene (SCENE_PAD: shifted)
+    all_xy: np.ndarray                # their origins int32 [n,2] (x0, y0) on the canvases (SCENE_PAD: the virtual scene)
+    pads: tuple = (0, 0, 0, 0)        # SCENE_PAD's (top, bottom, left, right): the canvases are shape + pads
     empty: bool = False               # a mask kept no tile: nothing was launched and the fields below stay as they are
     lo: int = 0                       # this rank's chunk of the tiles; emb holds their embeddings
     hi: int = 0
@@ -979,34 +1073,46 @@ class _SceneJob:
 
 
 def _pass1_front(ctx, io, img, valid=None):
-    """Pass 1 of one scene, queued (GPU): plan, upload, [tile selection, nodata fill,] crop -> encoder -> decoder -> fused canvases,
-    [canvas reduce,] normalise.  `io` decides how arrays travel and when the host waits (_BlockingIO / _LaneIO); everything else is the
-    same for every loop.  Returns the _SceneJob: embeddings resident, the u8 masks on the device of rank 0 — fetching them is the
-    caller's."""
+    """Pass 1 of one scene, queued (GPU): plan, upload, [border padding,] [tile selection, nodata fill,] crop -> encoder -> decoder ->
+    fused canvases, [canvas reduce,] normalise[, masks cropped back].  `io` decides how arrays travel and when the host waits
+    (_BlockingIO / _LaneIO); everything else is the same for every loop.  Returns the _SceneJob: embeddings resident, the u8 masks on the
+    device of rank 0 — fetching them is the caller's.  SCENE_PAD lives here and nowhere else: the real scene (and mask)
+    is uploaded and padded on the device, everything up to the normalise runs on that virtual scene through the same calls, the u8 masks
+    are cropped to the real scene before they travel, and the job carries the tiles in the real scene's frame for pass 2."""
     net, config = ctx.net, ctx.config
     img, infos, all_xy = _scene_plan(img, config)
+    pad = scene_pad_plan(img.shape, config)
+    shape = tuple(int(v) for v in img.shape[:2])
+    pads = pad[:4] if pad is not None and any(pad[:4]) else None     # all four 0: the launches of a run without the key
     if valid is not None:
-        valid, min_frac, fill = _valid_plan(valid, img.shape[:2], config)
+        valid, min_frac, fill = _valid_plan(valid, shape, config)
     pass1_kw, norm_kw, n_orient = ctx.features
     scene = io.upload("scene", img)                    # the u8 scene, ONCE; tiles are cropped on the device
     xy_dev = io.upload("xy", all_xy)
+    if valid is not None:
+        valid_d = io.upload("valid_mask", valid)       # a key of its own: "valid" stages pass 2's pair flags
     io.step("upload")
+    if pads is not None:
+        scene = net.scene_pad(scene, pads, pad[4], pad[5])
+        if valid is not None:                          # the mask by the same rule: reflect / edge mirror its validity, constant padding is nodata
+            valid_d = net.scene_pad(valid_d, pads, pad[4], (0, 0, 0))
+        io.step("pad")
+    job_pads = pads or (0, 0, 0, 0)
     if valid is not None:
         # every rank holds the scene and the mask, computes the same integer counts and therefore the same kept list: from here
         # on infos / all_xy / xy_dev ARE the kept tiles (a subsequence of an x-outer list is x-outer, so the banded reduce stays valid)
-        valid_d = io.upload("valid_mask", valid)       # a key of its own: "valid" stages pass 2's pair flags
-        kept = select_tiles(io.counts(lambda: net.scene_tile_valid(valid_d, xy_dev)), config.PATCH_SIZE, min_frac)
+        kept = select_tiles(io.counts(lambda: net.scene_tile_valid(valid_d, xy_dev), after_compute=pads is not None), config.PATCH_SIZE, min_frac)
         io.step("select")
         infos, all_xy = [infos[i] for i in kept], np.ascontiguousarray(all_xy[kept])
         if len(kept) == 0:                             # nothing to run: the encoder is not launched and no exchange step is entered
-            return _SceneJob(img.shape[:2], infos, all_xy, empty=True)
+            return _SceneJob(shape, _shift_infos(infos, job_pads), all_xy, job_pads, empty=True)
         xy_dev = io.upload("xy_kept", all_xy)
         if scene.device.type != "cuda":                # a CPU tensor (the stand-in models of the gloo tests) may share the caller's memory
             scene = scene.clone()
         scene = net.scene_fill_invalid(scene, valid_d, fill)
         io.step("fill")
         norm_kw = dict(valid=valid_d, **norm_kw)
-    job = _SceneJob(img.shape[:2], infos, all_xy)
+    job = _SceneJob(shape, _shift_infos(infos, job_pads), all_xy, job_pads)
     job.lo, job.hi = shard_tiles(len(infos), ctx.world, ctx.rank)
     io.step("launch pass 1")
     # FUSE_WINDOW: every rank weights its own chunk of the kept list.  TTA: every orientation runs that chunk (selection and fill happened
@@ -1021,6 +1127,9 @@ def _pass1_front(ctx, io, img, valid=None):
         # in list order: DESIGN.md §6f) — count and weight sum follow from the list alone, so there is no collective for them
         xy_norm = xy_dev if n_orient == 1 else xy_dev.repeat(n_orient, 1)
         job.kp_u8, job.road_u8 = net.scene_normalise(kp_c, road_c, xy_norm, **norm_kw)
+        if pads is not None:                           # the real scene's window of the virtual masks, cut out on the device: H * W bytes travel
+            (top, _, left, _), (H, W) = pads, shape
+            job.kp_u8, job.road_u8 = (m[top:top + H, left:left + W].contiguous() for m in (job.kp_u8, job.road_u8))
     io.step("normalised")
     return job
 
@@ -1112,6 +1221,7 @@ def infer_imgs(net, imgs, config, device=None, tile_sharded=None, pipelined=None
     neighbor_queries(config)                          # fail before any scene touches the device
     fuse_window(config)
     tta_plan(config)
+    scene_pad_key(config)
     valids = _valid_iter(valids)
     if D.is_distributed() if tile_sharded is None else tile_sharded:
         if pipelined is None:
@@ -1234,7 +1344,7 @@ def _infer_imgs_tile_sharded(net, imgs, config, device=None, stats=None, valids=
         if job.bands is not None:
             # this rank's own share: the band it ships to rank 0 (rank 0: what it receives), so that per-rank statistics are per rank
             x0, x1 = job.bands[rank]
-            rows = job.shape[0]                        # a band is a strip of columns of the full scene HEIGHT
+            rows = job.shape[0] + job.pads[0] + job.pads[1]      # a band is a strip of columns of the full canvas HEIGHT
             stats["canvas_bytes"] += D.canvas_bytes(job.bands, rows) if rank == 0 else 2 * 4 * rows * max(0, x1 - x0)
         if job.kp_u8 is not None:
             if cuda:       # asynchronous download behind the scene's own kernels: the host does not wait here
@@ -1392,8 +1502,17 @@ def main(argv=None):
                     help="(extension) test-time augmentation, overriding the config's TTA: orientation names separated by commas, the first "
                          "one id (id,flip_h,flip_v,rot180,transpose,rot90,rot270,anti_transpose); every tile is run once per name and "
                          "the masks are averaged")
+    ap.add_argument("--scene-pad", default=None, type=int, metavar="B",
+                    help="(extension) pad every scene by B >= 0 pixels on all four sides on the device before it is tiled, overriding the "
+                         "border of the config's SCENE_PAD; the masks and the graph are those of the unpadded scene.  With the key (any B) "
+                         "a scene smaller than a tile is padded up to one instead of being refused")
+    ap.add_argument("--scene-pad-mode", default=None, metavar="MODE", choices=SCENE_PAD_MODES,
+                    help="(extension) how the padding is filled, overriding the mode of the config's SCENE_PAD: reflect (default), edge "
+                         "or constant (the colour NODATA_FILL)")
     args = ap.parse_args(argv)
     config = load_config(args.config)
+    if args.scene_pad is not None or args.scene_pad_mode is not None:
+        config.SCENE_PAD = scene_pad_override(config, args.scene_pad, args.scene_pad_mode)
     if args.fuse_window is not None:
         config.FUSE_WINDOW = args.fuse_window
     if args.tta is not None:
@@ -1401,6 +1520,7 @@ def main(argv=None):
     neighbor_queries(config)                     # a K the TopoNet trunk cannot run fails here, not after the first scene's pass 1
     fuse_window(config)                          # and so does a FUSE_WINDOW that cannot be used
     tta_plan(config)                             # and a TTA list that cannot be run
+    scene_pad_plan((1, 1), config)               # and a SCENE_PAD (or the NODATA_FILL it uses) that cannot be used
     device = torch.device("cuda") if args.device == "cuda" else torch.device(args.device)
     torch.set_num_threads(max(1, min(torch.get_num_threads(), usable_cpus() // max(1, int(os.environ.get("WORLD_SIZE", "1"))))))   # this rank's share of the container's CPU quota (hostcpu.py)
     _numpy_hugepages(False)                      # for the whole run: image decoding and output encoding allocate beside the GPU too (_host_quiet)

@@ -676,3 +676,28 @@ class SAMRoad(nn.Module):
             ctx.check(ctx.lib.srh_scene_fill_invalid(ctx.handle, scene_u8.data_ptr(), valid_u8.data_ptr(), H, W, r, g, b,
                                                      self._stream(dev)), "srh_scene_fill_invalid")
         return scene_u8
+
+    # ---- scene level, border padding (SCENE_PAD) --------------------------------------------------------------------
+    @torch.no_grad()
+    def scene_pad(self, t_u8, pads, mode="reflect", fill=(0, 0, 0)):
+        """t_u8 [H,W,3] (a scene) or [H,W] (a validity mask; bool allowed) uint8 on the GPU -> a NEW tensor [H + top + bottom, W + left +
+        right(, 3)] of the same dtype: pads = (top, bottom, left, right) >= 0, mode 'reflect' (numpy's pad mode of that name, any pad
+        width), 'edge' or 'constant' (the colour `fill`, three ints 0..255; a mask takes the first).  The source is not written
+        (srh_scene_pad); it may be any contiguous view, at any byte address."""
+        import ctypes
+        dev = t_u8.device
+        ctx, _ = self._weights(dev)
+        if t_u8.dtype not in (torch.uint8, torch.bool) or t_u8.dim() not in (2, 3) or (t_u8.dim() == 3 and t_u8.shape[2] != 3) or not t_u8.is_contiguous():
+            raise ValueError(f"scene_pad takes a contiguous uint8 [H,W,3] or uint8 / bool [H,W] tensor, got {t_u8.dtype} {tuple(t_u8.shape)}")
+        if mode not in _lib.SRH_PAD_MODES:
+            raise ValueError(f"mode must be one of {tuple(_lib.SRH_PAD_MODES)}, got {mode!r}")
+        top, bottom, left, right = (int(v) for v in pads)
+        rgb = (ctypes.c_int32 * 3)(*(int(v) for v in fill))
+        H, W, ch = int(t_u8.shape[0]), int(t_u8.shape[1]), 3 if t_u8.dim() == 3 else 1
+        if min(top, bottom, left, right) < 0 or H < 1 or W < 1:
+            raise ValueError(f"pads must be >= 0 and the tensor not empty, got pads {tuple(pads)} for {tuple(t_u8.shape)}")
+        out = torch.empty((H + top + bottom, W + left + right) + tuple(t_u8.shape[2:]), dtype=t_u8.dtype, device=dev)
+        with torch.cuda.device(dev):
+            ctx.check(ctx.lib.srh_scene_pad(ctx.handle, t_u8.data_ptr(), H, W, ch, top, bottom, left, right, _lib.SRH_PAD_MODES[mode], rgb,
+                                            out.data_ptr(), self._stream(dev)), "srh_scene_pad")
+        return out

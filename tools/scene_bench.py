@@ -13,6 +13,8 @@ The final map_decoder bias is lowered so that the random network yields sparse m
                                                                     # of the scene; only tiles that hold valid pixels run (kept / all is printed)
     python tools/scene_bench.py --fuse-window hann                  # overlapping tiles fused with a window (FUSE_WINDOW) instead of the uniform mean
     python tools/scene_bench.py --tta id,flip_h,rot90               # test-time augmentation (TTA): every tile runs once per orientation
+    python tools/scene_bench.py --scene-pad 64 [--scene-pad-mode edge]    # SCENE_PAD: the scene is padded by 64 px on every side on the device
+                                                                    # (reflect by default), the masks and the graph are those of the real scene
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 tools/scene_bench.py    # N GPUs:
         tiles sharded over the ranks (RCCL: packed-weight broadcast, banded canvas reduce, point broadcast, vote gather);
         rank 0 prints ms/scene (max over ranks) and the per-rank stage times
@@ -51,6 +53,10 @@ def main():
                     help="FUSE_WINDOW: how overlapping tiles are fused (default: the key is absent, the reference's uniform mean)")
     ap.add_argument("--tta", default=None, metavar="NAMES",
                     help="TTA: orientation names separated by commas, the first one id (default: the key is absent, one run per tile)")
+    ap.add_argument("--scene-pad", type=int, default=None, metavar="B",
+                    help="SCENE_PAD: pad the scene by B px on every side on the device (default: the key is absent)")
+    ap.add_argument("--scene-pad-mode", default=None, metavar="MODE", choices=("reflect", "edge", "constant"),
+                    help="SCENE_PAD's mode (default reflect)")
     ap.add_argument("--no-pipelined", action="store_true", help="skip the infer_imgs runs (12- and 48-scene streams)")
     args = ap.parse_args()
     H, W = parse_scene(args.scene)
@@ -79,9 +85,13 @@ def main():
         cfg.FUSE_WINDOW = args.fuse_window
     if args.tta is not None:
         cfg.TTA = [t.strip() for t in args.tta.split(",")]
-    from sam_road_amd.inferencer import fuse_window, tta_plan
+    if args.scene_pad is not None or args.scene_pad_mode is not None:
+        cfg.SCENE_PAD = {"border": args.scene_pad or 0, "mode": args.scene_pad_mode or "reflect"}
+    from sam_road_amd.inferencer import fuse_window, scene_pad_plan, tta_plan
     window = fuse_window(cfg)
     tta_names, tta = tta_plan(cfg)
+    pad = scene_pad_plan((H, W), cfg)
+    pads = pad[:4] if pad is not None and any(pad[:4]) else None      # all four 0: the run of a scene without the key
     net = SAMRoad(cfg)
     g = torch.Generator().manual_seed(1234)
     sd = {}
@@ -103,7 +113,7 @@ def main():
     coarse = rng.integers(0, 256, size=(H // 8, W // 8, 3)).astype(np.float32)
     img = np.kron(coarse, np.ones((8, 8, 1), np.float32)).astype(np.uint8)
 
-    img, infos, all_xy = _scene_plan(img, cfg)         # the product's own validation and tile list
+    img, infos, all_xy = _scene_plan(img, cfg)         # the product's own validation and tile list (SCENE_PAD: of the padded scene)
     n_all = len(infos)
     valid = None
     if args.valid_frac is not None:
@@ -115,6 +125,8 @@ def main():
         from sam_road_amd.inferencer import scene_tiles
         infos = scene_tiles(img.shape, cfg, valid=valid, net=net)
         all_xy = np.array([[p[1][0], p[1][1]] for p in infos], dtype=np.int32).reshape(-1, 2)
+        if pads is not None:                           # scene_tiles speaks of the real scene's frame, the canvases are the padded scene's
+            all_xy = all_xy + np.array([[pads[2], pads[0]]], dtype=np.int32)
     xy = torch.as_tensor(all_xy).to(dev)
     scene = torch.as_tensor(img).to(dev)
     valid_d = None if valid is None else torch.as_tensor(valid).to(dev)
@@ -123,16 +135,23 @@ def main():
     tkw = {} if len(tta) == 1 else dict(tta=tta)                      # TTA: pass 1 runs the list once per orientation,
     xy_norm = xy if len(tta) == 1 else xy.repeat(len(tta), 1)         # the normalise gets the k-fold list
 
+    def crop(m):              # SCENE_PAD: the real scene's window of a mask of the padded scene, cut out on the device
+        return m if pads is None else m[pads[0]:pads[0] + H, pads[2]:pads[2] + W].contiguous()
+
     def pass1():              # this rank's share of the tiles (no collective: tile throughput)
-        if valid_d is not None:    # the masked pass 1 from the resident scene: count, fill (of a copy), kept tiles, masked normalise
-            net.scene_tile_valid(valid_d, torch.as_tensor(_scene_plan(img, cfg)[2]).to(dev)).cpu()
-            filled = net.scene_fill_invalid(scene.clone(), valid_d, (124, 116, 104))
+        sc, vd = scene, valid_d
+        if pads is not None:       # from the resident real scene: the pad is part of every pass 1
+            sc = net.scene_pad(scene, pads, pad[4], pad[5])
+            vd = None if valid_d is None else net.scene_pad(valid_d, pads, pad[4], (0, 0, 0))
+        if vd is not None:         # the masked pass 1 from the resident scene: count, fill (of a copy), kept tiles, masked normalise
+            net.scene_tile_valid(vd, torch.as_tensor(_scene_plan(img, cfg)[2]).to(dev)).cpu()
+            filled = net.scene_fill_invalid(sc.clone(), vd, (124, 116, 104))
             kp, road, emb = net.scene_pass1(filled, xy[lo:hi], args.batch, **wkw, **tkw)
-            kpu, ru = net.scene_normalise(kp, road, xy_norm, valid=valid_d, **wkw)
-            return kpu.cpu(), ru.cpu()
-        kp, road, emb = net.scene_pass1(scene, xy[lo:hi], args.batch, **wkw, **tkw)
+            kpu, ru = net.scene_normalise(kp, road, xy_norm, valid=vd, **wkw)
+            return crop(kpu).cpu(), crop(ru).cpu()
+        kp, road, emb = net.scene_pass1(sc, xy[lo:hi], args.batch, **wkw, **tkw)
         kpu, ru = net.scene_normalise(kp, road, xy_norm, **wkw)
-        return kpu.cpu(), ru.cpu()
+        return crop(kpu).cpu(), crop(ru).cpu()
 
     pass1()
     torch.cuda.synchronize()
@@ -203,6 +222,7 @@ def main():
     print(json.dumps({"scene": f"synthetic {H}x{W} u8, {n_all} tiles of 512^2 ({per_edge} per edge, margin 64)", "n_gpus": world,
                       "fuse_window": args.fuse_window or "uniform",
                       "tta": tta_names,
+                      "scene_pad": None if pad is None else {"pads": list(pad[:4]), "mode": pad[4]},
                       "valid_frac": None if valid is None else round(float(valid.mean()), 4), "tiles_kept": len(infos), "tiles_all": n_all,
                       "ms_weight_share": round(1e3 * t_w, 2) if world > 1 else None, "per_rank": per_rank,
                       "infer_batch_size": args.batch, "ms_per_scene_pass1": round(1e3 * p1, 2),
