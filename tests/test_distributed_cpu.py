@@ -1,19 +1,17 @@
 """world_size-2 gloo tests of the N>1 exchange steps (sam_road_amd/distributed.py) on CPU."""
 import os
-import socket
 
 import numpy as np
+import pytest
 import torch
 import torch.distributed as dist
 import torch.multiprocessing as mp
 
-
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    port = s.getsockname()[1]
-    s.close()
-    return port
+from scene_kit import E2E_CFG as _E2E_CFG       # bench.py --plumbing-cpu takes _E2E_CFG and _CpuStandIn from this module
+from scene_kit import E2E_SCENE as _E2E_SCENE
+from scene_kit import SceneStandIn as _CpuStandIn
+from scene_kit import free_port as _free_port
+from scene_kit import make_fake_dataset, run_worlds
 
 
 def _worker(rank, world, port, out):
@@ -115,103 +113,18 @@ def test_exchange_steps_world2_gloo():
 
 # ---------------------------------------------------------------------------------------------------------------------------------
 # The whole N > 1 data flow of infer_one_img (tile sharding, canvas reduce, point broadcast, per-rank pass 2, vote gather with
-# first-vote order) on gloo, world 3, against the single-process run.  The GPU model is replaced by a CPU stand-in with the same
-# interface built on the oracle (test infrastructure) — what is under test is the orchestration in sam_road_amd/inferencer.py
-# and sam_road_amd/distributed.py, which is exactly the code the 8-GPU run executes.
+# first-vote order) on gloo, world 3, against the single-process run.  The GPU model is replaced by the CPU stand-in of
+# tests/scene_kit.py, built on the oracle (test infrastructure) — what is under test is the orchestration in
+# sam_road_amd/inferencer.py and sam_road_amd/distributed.py, which is exactly the code the 8-GPU run executes.
 # ---------------------------------------------------------------------------------------------------------------------------------
-_E2E_CFG = dict(SAM_VERSION="vit_b", PATCH_SIZE=256, TOPONET_VERSION="normal", SAM_CKPT_PATH="", ENCODER_DEPTH=1,
-                ENCODER_GLOBAL_ATTN_INDEXES=[], INFER_BATCH_SIZE=3, SAMPLE_MARGIN=16, INFER_PATCHES_PER_EDGE=3,
-                ITSC_THRESHOLD=0.5, ROAD_THRESHOLD=0.5, TOPO_THRESHOLD=0.5, ITSC_NMS_RADIUS=8, ROAD_NMS_RADIUS=16,
-                NEIGHBOR_RADIUS=64, MAX_NEIGHBOR_QUERIES=16)
-_E2E_SCENE = 352
-
-
-class _CpuStandIn(torch.nn.Module):
-    """SAMRoad's scene-level interface (scene_pass1 / scene_normalise / infer_toponet) on the CPU oracle."""
-
-    def __init__(self, cfg):
-        super().__init__()
-        from oracle.samroad import AttrDict, SAMRoadOracle
-        from oracle.synth import synth_state_dict
-        self.oracle = SAMRoadOracle(AttrDict(cfg)).eval()
-        sd = synth_state_dict(self.oracle, 77)
-        sd["map_decoder.7.bias"] = torch.tensor([-0.3, 0.2])
-        self.oracle.load_state_dict(sd, strict=True)
-        self.P = cfg["PATCH_SIZE"]
-
-    def scene_pass1(self, scene, tile_xy, bs):
-        S, P = scene.shape[0], self.P
-        kp, road = torch.zeros((S, S)), torch.zeros((S, S))
-        embs = []
-        for x0, y0 in tile_xy.tolist():
-            s, e = self.oracle.infer_masks_and_img_features(scene[y0:y0 + P, x0:x0 + P].float()[None])
-            kp[y0:y0 + P, x0:x0 + P] += s[0, :, :, 0]
-            road[y0:y0 + P, x0:x0 + P] += s[0, :, :, 1]
-            embs.append(e)
-        emb = torch.cat(embs) if embs else torch.zeros((0, 256, P // 16, P // 16))
-        return kp, road, emb
-
-    def scene_normalise(self, kp, road, tile_xy):
-        cnt = torch.zeros_like(kp)
-        for x0, y0 in tile_xy.tolist():
-            cnt[y0:y0 + self.P, x0:x0 + self.P] += 1.0
-        u8 = lambda t: torch.nan_to_num(t / cnt * 255, nan=0.0).to(torch.uint8)
-        return u8(kp), u8(road)
-
-    def infer_toponet(self, emb, points, pairs, valid):
-        return self.oracle.infer_toponet(emb, points, pairs.long(), valid.bool())
-
-
-def _e2e_run(world, rank, port, out, scene_size=_E2E_SCENE, overrides=None):
-    import warnings
-    warnings.simplefilter("ignore")
-    if world > 1:
-        os.environ["MASTER_ADDR"] = "127.0.0.1"
-        os.environ["MASTER_PORT"] = str(port)
-        dist.init_process_group("gloo", rank=rank, world_size=world)
-    try:
-        from oracle.synth import synth_scene
-        from sam_road_amd import Config
-        from sam_road_amd.inferencer import infer_one_img
-        torch.set_num_threads(2)
-        cfg = dict(_E2E_CFG, **(overrides or {}))
-        net = _CpuStandIn(cfg)
-        img = synth_scene(scene_size, seed=6)
-        res = infer_one_img(net, img, Config(cfg), device="cpu")
-        out.put((rank, None if res is None else [np.asarray(r) for r in res]))
-    except Exception as e:  # pragma: no cover
-        import traceback
-        out.put((rank, "ERR " + traceback.format_exc()))
-    finally:
-        if world > 1:
-            dist.destroy_process_group()
-
-
-import pytest
-
-
 @pytest.mark.parametrize("scene_size,overrides,must_be_identical", [
     (_E2E_SCENE, None, False),                                               # overlapping tiles (the shipped tilings)
     (512, dict(SAMPLE_MARGIN=0, INFER_PATCHES_PER_EDGE=2), True),            # disjoint tiles: every canvas pixel has ONE addend
     (512, dict(SAMPLE_MARGIN=0, INFER_PATCHES_PER_EDGE=2, EXACT_VOTE_MERGE=True), True),   # raw votes merged on rank 0 (exact sums)
 ])
 def test_infer_one_img_world3_matches_single_process(scene_size, overrides, must_be_identical):
-    ctx = mp.get_context("spawn")
-    results = {}
-    for world in (1, 3):
-        port = _free_port()
-        q = ctx.Queue()
-        procs = [ctx.Process(target=_e2e_run, args=(world, r, port, q, scene_size, overrides)) for r in range(world)]
-        for p in procs:
-            p.start()
-        got = dict(q.get(timeout=600) for _ in range(world))
-        for p in procs:
-            p.join(timeout=60)
-        for r, v in got.items():
-            assert not isinstance(v, str), v
-            assert (v is None) == (r != 0)                                   # only rank 0 returns the graph
-        results[world] = got[0]
-    (n1, e1, k1, r1), (n3, e3, k3, r3) = results[1], results[3]
+    results = run_worlds((1, 3), dict(base="e2e", overrides=overrides, shapes=[(scene_size, scene_size)], seeds=[6], mode="serial"))
+    (n1, e1, k1, r1), (n3, e3, k3, r3) = results[1][0], results[3][0]
     assert n1.shape[0] > 30 and e1.shape[0] > 100
     # canvases are summed in a different association order across ranks: the f32 sums may differ in the last bit, which the
     # u8 truncation can turn into one level on a few pixels
@@ -287,17 +200,14 @@ def _cli_rank(world, rank, port, work, out):
             dist.destroy_process_group()
 
 
-def test_cli_scene_sharding_world2(tmp_path):
+def test_cli_scene_sharding_world2(tmp_path, golden_dir):
     """The CLI under a 2-process launch, `--shard scenes` (default): ranks take the test scenes round-robin, write into ONE output
     directory, rank 0 writes config.yaml and inference_time.txt (max over ranks); every scene's files exist exactly once."""
     import pickle
-    import sys
     from PIL import Image
-    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-    import test_refrun_golden as T
-    g = np.load(f"{T.GOLD}/refrun_cli.npz")
     work = tmp_path / "cityscale"
-    ids = T._make_fake_dataset(T._mg(), work, "cityscale", g)
+    ids = [int(i) for i in np.load(f"{golden_dir}/refrun_cli.npz")["cityscale_ids"]]      # the test split the CLI reads
+    make_fake_dataset(work, "cityscale", ids, dict(_E2E_CFG, INFER_PATCHES_PER_EDGE=2), 288)
     ctx = mp.get_context("spawn")
     q, port = ctx.Queue(), _free_port()
     procs = [ctx.Process(target=_cli_rank, args=(2, r, port, str(work), q)) for r in range(2)]
@@ -328,72 +238,17 @@ def test_cli_scene_sharding_world2(tmp_path):
 # Tile-sharded scenes, software-pipelined (inferencer._infer_imgs_tile_sharded: pass 1 of scene i+1 is queued before the host
 # stages of scene i; the band receives are posted at once): world 8 on gloo against the single-process results.
 # ---------------------------------------------------------------------------------------------------------------------------------
-def _pipe_run(world, rank, port, out, scene_size, overrides, seeds):
-    import warnings
-    warnings.simplefilter("ignore")
-    if world > 1:
-        os.environ["MASTER_ADDR"] = "127.0.0.1"
-        os.environ["MASTER_PORT"] = str(port)
-        dist.init_process_group("gloo", rank=rank, world_size=world)
-    try:
-        from oracle.synth import synth_scene
-        from sam_road_amd import Config
-        from sam_road_amd import distributed as D
-        from sam_road_amd.inferencer import _infer_imgs_tile_sharded, infer_imgs, infer_one_img
-        torch.set_num_threads(1)
-        D._CHECK_BANDS[0] = True                  # every sender asserts that its canvas is zero outside the band it ships
-        cfg = dict(_E2E_CFG, **(overrides or {}))
-        net = _CpuStandIn(cfg)
-        imgs = [synth_scene(scene_size, seed=s) if s >= 0 else np.zeros((scene_size, scene_size, 3), np.uint8) for s in seeds]
-        stats = {}
-        if world > 1:
-            got = list(_infer_imgs_tile_sharded(net, iter(imgs), Config(cfg), device="cpu", stats=stats))
-            assert list(infer_imgs(net, iter([]), Config(cfg), device="cpu", tile_sharded=True)) == []
-            # infer_imgs under torch.distributed: the SERIAL scene-by-scene loop by default, the pipelined one by config key — same graphs
-            serial = list(infer_imgs(net, iter(imgs), Config(cfg), device="cpu"))
-            piped = list(infer_imgs(net, iter(imgs), Config(dict(cfg, TILE_SHARD_PIPELINE=True)), device="cpu"))
-            for a, b, c in zip(got, serial, piped):
-                assert (a is None) == (b is None) == (c is None) == (rank != 0)
-                if a is not None:
-                    for x, y, z in zip(a, b, c):
-                        np.testing.assert_array_equal(np.asarray(x), np.asarray(y))
-                        np.testing.assert_array_equal(np.asarray(x), np.asarray(z))
-        else:
-            got = [infer_one_img(net, im, Config(cfg), device="cpu") for im in imgs]
-        out.put((rank, [None if r is None else [np.asarray(a) for a in r] for r in got], stats))
-    except Exception:  # pragma: no cover
-        import traceback
-        out.put((rank, "ERR " + traceback.format_exc(), None))
-    finally:
-        if world > 1:
-            dist.destroy_process_group()
-
-
 def test_pipelined_tile_sharded_scenes_world8_match_single_process():
     """Three scenes (one of them all-zero pixels) through the pipelined tile-sharded generator on 8 ranks — more ranks than
     tiles, so half of them own an empty shard and an empty band — with disjoint tiles (every canvas pixel has one addend: the
     results must be IDENTICAL to the single-process run, edges in the same order)."""
-    ctx = mp.get_context("spawn")
-    overrides = dict(SAMPLE_MARGIN=0, INFER_PATCHES_PER_EDGE=2)
-    seeds = [6, -1, 9]
-    results = {}
-    for world in (1, 8):
-        port = _free_port()
-        q = ctx.Queue()
-        procs = [ctx.Process(target=_pipe_run, args=(world, r, port, q, 512, overrides, seeds)) for r in range(world)]
-        for p in procs:
-            p.start()
-        got = {}
-        for _ in range(world):
-            r, v, st = q.get(timeout=900)
-            assert not isinstance(v, str), v
-            got[r] = (v, st)
-        for p in procs:
-            p.join(timeout=60)
-        for r, (v, st) in got.items():
-            assert all((x is None) == (r != 0) for x in v)                   # only rank 0 yields the graphs
-        results[world] = got[0]
-    one, (eight, stats) = results[1][0], results[8]
+    # in the ranks: the generator itself, infer_imgs' serial tile-sharded loop (the default under torch.distributed) and the pipelined one
+    # by config key give the same graphs
+    spec = dict(base="e2e", overrides=dict(SAMPLE_MARGIN=0, INFER_PATCHES_PER_EDGE=2), shapes=[(512, 512)] * 3, seeds=[6, -1, 9],
+                mode="pipelined", threads=1, checks=("serial_loop", "sharded_generator"))
+    stats = {}
+    results = run_worlds((1, 8), spec, stats=stats)
+    one, eight = results[1], results[8]
     assert len(one) == len(eight) == 3 and one[0][0].shape[0] > 30 and one[2][1].shape[0] > 100
     for a, b in zip(one, eight):
         for x, y in zip(a, b):

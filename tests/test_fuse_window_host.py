@@ -1,9 +1,8 @@
 """FUSE_WINDOW (window-weighted fusion of overlapping tiles), the GPU-free part: the profiles against their formulas, the
 argument errors, the C-ABI surface, the orchestration of the three loops and of the tile-sharded loops on gloo / CPU, and the CLI —
-through a numpy stand-in of scene_pass1(window=) / scene_normalise(window=) on top of the CPU stand-in of tests/test_valid_mask_host.py.
+through scene_pass1(window=) / scene_normalise(window=) of the CPU stand-in of tests/scene_kit.py (features "valid", "window").
 Everything multi-rank here runs on gloo / CPU only."""
 import os
-import pickle
 import re
 import shutil
 import subprocess
@@ -12,18 +11,16 @@ import warnings
 import numpy as np
 import pytest
 import torch
-import torch.distributed as dist
-import torch.multiprocessing as mp
 
 from sam_road_amd import Config, _lib
-from sam_road_amd import distributed as D
 from sam_road_amd import inferencer as inf
 from sam_road_amd.inferencer import infer_imgs, infer_one_img
 
-from test_rect_scene_host import _CFG, _CpuStandIn, _free_port, _rect_scene
-from test_valid_mask_host import _MaskStandIn, _compare, _same_tuple, make_mask
+from scene_kit import HOST_CFG as _CFG
+from scene_kit import SceneStandIn, assert_abi_11, compare_worlds, make_mask, run_cli, run_worlds
+from scene_kit import rect_scene as _rect_scene
+from scene_kit import same_tuple as _same_tuple
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SIZES = (128, 208, 512, 1024)
 
 
@@ -112,48 +109,11 @@ def test_bad_windows_are_refused_before_the_model_is_touched():
 
 
 # ---- the pipeline on a stand-in ------------------------------------------------------------------------------------------------------
-class _WindowStandIn(_MaskStandIn):
-    """_MaskStandIn + window= on scene_pass1 / scene_normalise in CPU torch: the rule of DESIGN.md §6e in f32, tile by tile in list order.
-    Without a window the inherited methods run — and they do not know the argument, so passing it in the uniform case is an error."""
-
-    def scene_pass1(self, scene, tile_xy, bs, window=None):
-        if window is None:
-            return super().scene_pass1(scene, tile_xy, bs)
-        self.calls.append(("pass1_window", int(tile_xy.shape[0])))
-        assert window.dtype == torch.float32 and tuple(window.shape) == (self.P,)
-        (H, W), P = scene.shape[:2], self.P
-        w2 = window[:, None] * window[None, :]
-        kp, road = torch.zeros((H, W)), torch.zeros((H, W))
-        embs = []
-        for x0, y0 in tile_xy.tolist():
-            s, e = self.oracle.infer_masks_and_img_features(scene[y0:y0 + P, x0:x0 + P].float()[None])
-            kp[y0:y0 + P, x0:x0 + P] += w2 * s[0, :, :, 0]
-            road[y0:y0 + P, x0:x0 + P] += w2 * s[0, :, :, 1]
-            embs.append(e)
-        emb = torch.cat(embs) if embs else torch.zeros((0, 256, P // 16, P // 16))
-        return kp, road, emb
-
-    def scene_normalise(self, kp, road, tile_xy, valid=None, window=None):
-        if window is None:
-            return super().scene_normalise(kp, road, tile_xy, valid=valid)
-        self.calls.append(("normalise_window", int(tile_xy.shape[0])))
-        w2 = window[:, None] * window[None, :]
-        wsum = torch.zeros_like(kp)
-        for x0, y0 in tile_xy.tolist():
-            wsum[y0:y0 + self.P, x0:x0 + self.P] += w2
-        u8 = lambda t: torch.nan_to_num(t / wsum * 255, nan=0.0).to(torch.uint8)
-        kp_u8, road_u8 = u8(kp), u8(road)
-        if valid is not None:
-            kp_u8[valid == 0] = 0
-            road_u8[valid == 0] = 0
-        return kp_u8, road_u8
-
-
 @pytest.fixture(scope="module")
 def standin():
     warnings.simplefilter("ignore")
     cfg = dict(_CFG, INFER_PATCHES_PER_EDGE=[4, 6])                            # overlapping tiles: the window changes the masks
-    return _WindowStandIn(cfg), cfg
+    return SceneStandIn(cfg, ("valid", "window")), cfg
 
 
 def _fused_f64(net, img, infos, w1, valid=None):
@@ -179,7 +139,7 @@ def test_windowed_scene_on_the_standin(standin):
     img = _rect_scene(H, W, 60)
     n_tiles = 24
     # uniform / None / absent: the calls of today, with the arguments of today (the base stand-in does not know `window`)
-    base = _CpuStandIn(cfg)
+    base = SceneStandIn(cfg)
     plain = infer_one_img(base, img, Config(cfg), device="cpu")
     for v in ("uniform", None):
         _same_tuple(infer_one_img(base, img, Config(dict(cfg, FUSE_WINDOW=v)), device="cpu"), plain)
@@ -226,15 +186,7 @@ def test_windowed_scene_on_the_standin(standin):
 
 # ---- C ABI surface ------------------------------------------------------------------------------------------------------------------
 def test_abi_has_the_window_entries_and_stays_11():
-    header = open(os.path.join(ROOT, "include", "samroad_hip.h")).read()
-    declared = set(re.findall(r"^[A-Za-z_][\w \*]*?\b(srh_\w+)\(", header, flags=re.M))
-    assert declared == set(_lib.SYMBOLS), (declared ^ set(_lib.SYMBOLS))
-    lib = _lib.load()
-    assert lib.srh_abi_version() == _lib.ABI_VERSION == int(re.search(r"#define SRH_ABI_VERSION (\d+)", header).group(1)) == 11
-    for name, n_args in (("srh_scene_pass1_window_hw", 13), ("srh_scene_normalise_window_hw", 13), ("srh_op_scene_fuse_window", 11)):
-        assert hasattr(lib, name) and len(_lib.SYMBOLS[name][1]) == n_args
-        decl = re.search(r"\bint %s\(([^;]*)\);" % name, header).group(1)
-        assert len(decl.split(",")) == n_args
+    assert_abi_11((("srh_scene_pass1_window_hw", 13), ("srh_scene_normalise_window_hw", 13), ("srh_op_scene_fuse_window", 11)))
     assert len(_lib.SYMBOLS["srh_scene_pass1_window_hw"][1]) == len(_lib.SYMBOLS["srh_scene_pass1_hw"][1]) + 1
     assert len(_lib.SYMBOLS["srh_scene_normalise_window_hw"][1]) == len(_lib.SYMBOLS["srh_scene_normalise_valid_hw"][1]) + 1
 
@@ -256,56 +208,9 @@ def test_window_kernels_compile_for_gfx950_without_a_gpu():
 
 
 # ---- tile-sharded loops on gloo ---------------------------------------------------------------------------------------------------------
-def _rank(world, rank, port, out, shapes, kinds, overrides, mode):
-    warnings.simplefilter("ignore")
-    if world > 1:
-        os.environ["MASTER_ADDR"] = "127.0.0.1"
-        os.environ["MASTER_PORT"] = str(port)
-        dist.init_process_group("gloo", rank=rank, world_size=world)
-    try:
-        torch.set_num_threads(2)
-        D._CHECK_BANDS[0] = True
-        cfg = dict(_CFG, **(overrides or {}))
-        net = _WindowStandIn(cfg)
-        imgs = [_rect_scene(h, w, 60 + i) for i, (h, w) in enumerate(shapes)]
-        valids = [None if k is None else make_mask(k, h, w) for k, (h, w) in zip(kinds, shapes)]
-        net.calls.clear()
-        serial = [infer_one_img(net, im, Config(cfg), device="cpu", valid=v) for im, v in zip(imgs, valids)]
-        assert not [c for c in net.calls if c[0] in ("pass1", "normalise")]          # every pass 1 was the weighted one
-        assert ("normalise_window" in [c[0] for c in net.calls]) == (rank == 0)    # rank 0 alone normalises, with the full list
-        if mode == "pipelined" and world > 1:
-            got = list(infer_imgs(net, iter(imgs), Config(dict(cfg, TILE_SHARD_PIPELINE=True)), device="cpu", valids=valids))
-            for a, b in zip(got, serial):             # same world size: same summation orders, so the two loops agree exactly
-                assert (a is None) == (b is None) == (rank != 0)
-                if a is not None:
-                    _same_tuple(a, b)
-        else:
-            got = serial
-        out.put((rank, [None if r is None else [np.asarray(a) for a in r] for r in got]))
-    except Exception:  # pragma: no cover
-        import traceback
-        out.put((rank, "ERR " + traceback.format_exc()))
-    finally:
-        if world > 1:
-            dist.destroy_process_group()
-
-
-def _run_worlds(worlds, shapes, kinds, overrides, mode):
-    ctx = mp.get_context("spawn")
-    results = {}
-    for world in worlds:
-        port, q = _free_port(), ctx.Queue()
-        procs = [ctx.Process(target=_rank, args=(world, r, port, q, shapes, kinds, overrides, mode)) for r in range(world)]
-        for p in procs:
-            p.start()
-        got = dict(q.get(timeout=900) for _ in range(world))
-        for p in procs:
-            p.join(timeout=60)
-        for r, v in got.items():
-            assert not isinstance(v, str), v
-            assert all((x is None) == (r != 0) for x in v)
-        results[world] = got[0]
-    return results
+def _spec(shapes, kinds, overrides, mode):
+    """The windowed stand-in; every rank checks that each pass 1 was the weighted one and that rank 0 alone normalises."""
+    return dict(features=("valid", "window"), shapes=shapes, kinds=kinds, overrides=overrides, mode=mode, checks=("window_calls",))
 
 
 @pytest.mark.parametrize("overrides,must_be_identical", [
@@ -316,15 +221,15 @@ def test_serial_tile_sharded_world3_with_a_window(overrides, must_be_identical):
     """World 3 against one process, with the identity conditions of tests/test_valid_mask_host.py: a disjoint tiling is identical; with
     overlapping tiles the ranks' f32 partial sums are associated differently, so a u8 may differ by one level."""
     shapes, kinds = [(384, 640), (384, 640), (384, 640)], [None, "band", "left"]
-    res = _run_worlds((1, 3), shapes, kinds, overrides, "serial")
-    _compare(res[1], res[3], shapes, kinds, must_be_identical)
+    res = run_worlds((1, 3), _spec(shapes, kinds, overrides, "serial"))
+    compare_worlds(res[1], res[3], shapes, kinds, must_be_identical)
 
 
 def test_pipelined_tile_sharded_world2_with_a_window():
     shapes = [(384, 640), (640, 384), (401, 523), (448, 448)]
     kinds = ["band", None, "none", "hole"]
-    res = _run_worlds((1, 2), shapes, kinds, dict(FUSE_WINDOW="hann"), "pipelined")
-    _compare(res[1], res[2], shapes, kinds, False)
+    res = run_worlds((1, 2), _spec(shapes, kinds, dict(FUSE_WINDOW="hann"), "pipelined"))
+    compare_worlds(res[1], res[2], shapes, kinds, False)
 
 
 # ---- CLI ------------------------------------------------------------------------------------------------------------------------------
@@ -335,18 +240,11 @@ def test_cli_takes_the_key_and_the_flag(tmp_path, monkeypatch, standin):
     net, cfg = standin
     img = _rect_scene(384, 640, 60)
     monkeypatch.chdir(tmp_path)
-    for name, extra in (("plain", {}), ("hann", dict(FUSE_WINDOW="hann"))):
-        with open(f"{name}.yaml", "w") as f:
-            yaml.safe_dump(dict(cfg, DATASET="cityscale", **extra), f)
     Image.fromarray(img).save("rgb.png")
-    monkeypatch.setattr(inf, "_build_net", lambda config, checkpoint, device: net)
+    plain, hann = cfg, dict(cfg, FUSE_WINDOW="hann")
 
     def run(name, config, *argv):
-        inf.main(["--config", config, "--checkpoint", "none", "--device", "cpu", "--output_dir", name, "--images", "rgb.png", *argv])
-        with open(f"save/{name}/graph/rgb.p", "rb") as f:
-            g = pickle.load(f)
-        saved = yaml.safe_load(open(f"save/{name}/config.yaml"))
-        return np.array(Image.open(f"save/{name}/mask/rgb_itsc.png")), np.array(Image.open(f"save/{name}/mask/rgb_road.png")), g, saved
+        return run_cli(inf, net, tmp_path, monkeypatch, name, config, ["rgb.png"], *argv)["rgb"]
 
     want = {k: infer_one_img(net, img, Config(dict(cfg, **({} if k == "uniform" else dict(FUSE_WINDOW=k)))), device="cpu")
             for k in ("uniform", "hann", "triangle")}
@@ -357,14 +255,14 @@ def test_cli_takes_the_key_and_the_flag(tmp_path, monkeypatch, standin):
         np.testing.assert_array_equal(got[1], want[key][3])
         assert got[2] == convert_to_sat2graph_format(want[key][0], want[key][1])
 
-    check(run("a", "plain.yaml"), "uniform")
-    check(run("b", "hann.yaml"), "hann")                                        # the key comes from the YAML
-    got = run("c", "plain.yaml", "--fuse-window", "triangle")                  # the flag sets it
+    check(run("a", plain), "uniform")
+    check(run("b", hann), "hann")                                        # the key comes from the YAML
+    got = run("c", plain, "--fuse-window", "triangle")                  # the flag sets it
     check(got, "triangle")
     assert got[3]["FUSE_WINDOW"] == "triangle"
-    check(run("d", "hann.yaml", "--fuse-window", "uniform"), "uniform")        # and overrides the YAML
+    check(run("d", hann, "--fuse-window", "uniform"), "uniform")        # and overrides the YAML
     with pytest.raises(SystemExit):
-        inf.main(["--config", "plain.yaml", "--checkpoint", "none", "--device", "cpu", "--output_dir", "e", "--images", "rgb.png",
+        inf.main(["--config", "a.yaml", "--checkpoint", "none", "--device", "cpu", "--output_dir", "e", "--images", "rgb.png",
                   "--fuse-window", "gauss"])
     with open("bad.yaml", "w") as f:
         yaml.safe_dump(dict(cfg, DATASET="cityscale", FUSE_WINDOW="gauss"), f)

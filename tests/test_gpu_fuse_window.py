@@ -13,15 +13,15 @@ import numpy as np
 import pytest
 import torch
 
-import tolerances
-
 pytestmark = pytest.mark.gpu
 
-from oracle import scene as oscene
-from oracle.samroad import AttrDict
-
-from test_gpu_valid_mask import (CFG, FILL, PARITY_SCENES, SCENES, _net_for, _same, _thresholds, _xy, make_mask, np_kept, pair,  # noqa: F401
-                                 rect_grid, rect_scene)
+from scene_kit import (CFG, FILL, PARITY_SCENES, SCENES, check_scene_parity, fuse_f64, kernel_rows, make_mask, np_kept, oracle_scene, pair,  # noqa: F401
+                       rect_grid, rect_scene)
+from scene_kit import dev as _dev
+from scene_kit import net_for as _net_for
+from scene_kit import same_bits as _same
+from scene_kit import thresholds as _thresholds
+from scene_kit import xy_of as _xy
 
 
 def profile_f64(kind, P, seed=0):
@@ -36,23 +36,6 @@ def profile_f64(kind, P, seed=0):
     if kind == "ones":
         return np.ones(P)
     raise KeyError(kind)
-
-
-def fuse_f64(shape, xy, scores, w1_f32, prior=None):
-    """The weighted rule in float64: (kp, road, Wsum, cover count) for tile origins xy [n,2] (x0, y0) and scores [n,P,P,2]; the weights
-    are the exact products of the f32 profile values."""
-    H, W = shape
-    P = w1_f32.shape[0]
-    w2 = np.outer(w1_f32.astype(np.float64), w1_f32.astype(np.float64))       # [ly, lx]
-    kp = np.zeros((H, W)) if prior is None else prior[0].astype(np.float64)
-    road = np.zeros((H, W)) if prior is None else prior[1].astype(np.float64)
-    ws, cnt = np.zeros((H, W)), np.zeros((H, W), np.int64)
-    for (x0, y0), s in zip(np.asarray(xy).tolist(), scores):
-        kp[y0:y0 + P, x0:x0 + P] += w2 * s[:, :, 0]
-        road[y0:y0 + P, x0:x0 + P] += w2 * s[:, :, 1]
-        ws[y0:y0 + P, x0:x0 + P] += w2
-        cnt[y0:y0 + P, x0:x0 + P] += 1
-    return kp, road, ws, cnt
 
 
 def scene_shapes(P):
@@ -72,10 +55,6 @@ def tile_list(kind, H, W, P, seed):
         xy = np.concatenate([xy, [[0, 0], [W - P, H - P], [W - P, 0], [0, H - P]], xy[3:4], xy[3:4]]).astype(np.int32)
         return xy[rng.permutation(len(xy))]
     raise KeyError(kind)
-
-
-def _dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
 
 
 # ---- 1. the weighted add against float64 ------------------------------------------------------------------------------------------
@@ -302,9 +281,7 @@ def test_infer_imgs_with_a_window_equals_serial_and_uniform_equals_absent(pair):
     want = [infer_one_img(net, im, absent, valid=v) for im, v in zip(imgs[:3], valids[:3])]
     assert not np.array_equal(want[0][2], infer_one_img(net, imgs[0], Config(dict(CFG, FUSE_WINDOW="hann", **thr)))[2])
     ctx = _lib.Context.get(torch.cuda.current_device())
-    ctx.profile_read()
-    ctx.profile_enable(True)
-    try:
+    with kernel_rows(ctx) as rows:
         for v in ("uniform", None):
             cfg = Config(dict(absent, FUSE_WINDOW=v))
             for w, g in zip(want, [infer_one_img(net, im, cfg, valid=m) for im, m in zip(imgs[:3], valids[:3])]):
@@ -313,14 +290,10 @@ def test_infer_imgs_with_a_window_equals_serial_and_uniform_equals_absent(pair):
             for w, g in zip(want, infer_imgs(net, iter(imgs[:3]), cfg, valids=iter(valids[:3]))):
                 for a, b in zip(w, g):
                     _same(a, b)
-        torch.cuda.synchronize()
-        uniform = {r["name"] for r in ctx.profile_read() if r["launches"]}
+        uniform = rows()
         infer_one_img(net, imgs[0], Config(dict(absent, FUSE_WINDOW="hann")))
         infer_one_img(net, imgs[1], Config(dict(absent, FUSE_WINDOW="hann")), valid=valids[1])
-        torch.cuda.synchronize()
-        windowed = {r["name"] for r in ctx.profile_read() if r["launches"]}
-    finally:
-        ctx.profile_enable(False)
+        windowed = rows()
     new = {"scene_add_window", "scene_norm_window"}
     print("kernel classes, uniform:", sorted(uniform), "| windowed:", sorted(windowed))
     assert not (new & uniform) and {"scene_add", "scene_count", "scene_normalise"} <= uniform
@@ -374,27 +347,6 @@ def test_abi_rejects_bad_arguments(pair):
 
 
 # ---- 7. against the oracle ------------------------------------------------------------------------------------------------------------
-def oracle_windowed(oracle, img, valid, per_edge, w1_f32):
-    """The expectation from the oracle's per-tile scores on the CPU, fused by the float64 weighted rule: (kept infos, feats, kp u8, road
-    u8), the masks 0 where no tile covers the pixel and on nodata.  Uses nothing of sam_road_amd."""
-    H, W = img.shape[:2]
-    P, bs = CFG["PATCH_SIZE"], CFG["INFER_BATCH_SIZE"]
-    infos = rect_grid(H, W, CFG["SAMPLE_MARGIN"], P, per_edge)
-    filled = img
-    if valid is not None:
-        infos = [infos[i] for i in np_kept(valid, infos, P)]
-        filled = np.ascontiguousarray(np.where(valid[..., None], img, np.array(FILL, np.uint8)))
-    feats, scores = [], []
-    for i in range(0, len(infos), bs):
-        s, f = oracle.infer_masks_and_img_features(oscene.get_batch_img_patches(filled, infos[i:i + bs]))
-        feats.append(f)
-        scores.append(s.detach().numpy().astype(np.float64))
-    kp, road, ws, _ = fuse_f64((H, W), [p[1] for p in infos], np.concatenate(scores), w1_f32)
-    on = ws > 0 if valid is None else (ws > 0) & valid
-    to_u8 = lambda c: np.where(on, np.floor(c / np.where(ws > 0, ws, 1.0) * 255.0), 0.0).astype(np.uint8)
-    return infos, feats, to_u8(kp), to_u8(road)
-
-
 # Scenes, masks and windows were chosen WITH THE ORACLE ALONE on the CPU (points from the oracle's own masks) so that its graph has well
 # over 20 points and 50 voted edges:   (tiles, points, voted edges, oracle edges, share within TOPO_SCORE of the threshold)
 #   384x640 unmasked hann: 15, 470, 8834, 675, 0.34 %      523x701 hole triangle: 20, 593, 10232, 811, 0.33 %
@@ -406,39 +358,13 @@ PARITY_CASES = [("384x640", None, "hann"), ("523x701", "hole", "triangle"), ("38
 def test_windowed_scene_parity_with_oracle(pair, scene, kind, window):
     """The assertions and bounds of test_rect_scene_parity_with_oracle (tests/tolerances.py) on a window-fused scene."""
     from sam_road_amd import Config
-    from sam_road_amd.graph_points import extract_graph_points
     from sam_road_amd.inferencer import infer_one_img
     oracle, net = pair
     H, W, per_edge, seed = PARITY_SCENES[scene]
-    tag = f"fuse_window_{window}_{kind or 'unmasked'}_{scene}"
     img = rect_scene(H, W, seed)
     valid = None if kind is None else make_mask(kind, H, W)
     w1 = profile_f64(window, CFG["PATCH_SIZE"]).astype(np.float32)
-    infos, feats, kp_r, road_r = oracle_windowed(oracle, img, valid, per_edge, w1)
-    assert kp_r.max() > 0 and road_r.max() > 0
-    cfg = dict(CFG, INFER_PATCHES_PER_EDGE=per_edge, FUSE_WINDOW=window, **_thresholds(kp_r, road_r))
-    nodes, edges, kp, road = infer_one_img(net, img, Config(cfg), valid=valid)
-    for name, got, ref in (("kp", kp, kp_r), ("road", road, road_r)):
-        d = np.abs(got.astype(int) - ref.astype(int))
-        print(f"[parity] {tag}_{name}_u8_max_diff: {d.max()} levels (bound <= 2)")
-        tolerances.check(f"{tag}_{name}_u8_within1", (d <= 1).mean(), tolerances.U8_WITHIN1, at_least=True)
-        tolerances.check(f"{tag}_{name}_u8_max_diff", d.max(), 3)                 # integers: < 3 is <= 2 levels
-        assert d.max() <= 2
-        if valid is not None:
-            assert not got[~valid].any() and got[valid].any()
-    pts = extract_graph_points(kp, road, Config(cfg))
-    np.testing.assert_array_equal(pts, oscene.extract_graph_points(kp, road, AttrDict(cfg)))
-    np.testing.assert_array_equal(nodes, pts[:, ::-1])
-    assert pts.shape[0] > 20
-    edges_r, sums_r, cnts_r = oscene.infer_pass2(oracle, feats, pts, infos, AttrDict(cfg))
-    got = {(int(a), int(b)) for a, b in edges.tolist()}
-    ref = {(int(a), int(b)) for a, b in edges_r.tolist()}
-    firm = {e for e, s in sums_r.items() if abs(s / cnts_r[e] - cfg["TOPO_THRESHOLD"]) > tolerances.TOPO_SCORE}
-    left_out = 1.0 - len(firm) / len(sums_r)
-    print(f"[parity] {tag}: {len(infos)} tiles, {pts.shape[0]} points, {len(sums_r)} voted edges, {len(ref)} oracle edges, "
-          f"firm filter leaves out {left_out:.4f}, symmetric difference {len(got ^ ref)}")
-    assert len(sums_r) > 50
-    assert left_out <= 0.05
-    assert {e for e in ref if e in firm} == {e for e in got if e in firm}
-    tolerances.check(f"{tag}_edge_symdiff", len(got ^ ref), int(max(2, 0.02 * len(ref))) + 1)    # integers: < floor(b) + 1 is <= b
-    assert len(got ^ ref) <= max(2, 0.02 * len(ref))
+    ref = oracle_scene(oracle, img, per_edge, valid=valid, window=w1)
+    cfg = dict(CFG, INFER_PATCHES_PER_EDGE=per_edge, FUSE_WINDOW=window, **_thresholds(ref[2], ref[3]))
+    got = infer_one_img(net, img, Config(cfg), valid=valid)
+    check_scene_parity(f"fuse_window_{window}_{kind or 'unmasked'}_{scene}", got, ref, cfg, oracle, valid=valid)

@@ -10,8 +10,8 @@ import pytest
 import torch
 
 import heads_ref
+import scene_kit
 import tolerances as T
-from oracle import scene as oscene
 from oracle.samroad import AttrDict, SAMRoadOracle
 from oracle.synth import synth_queries, synth_scene, synth_state_dict, synth_state_dict_keyed, synth_tiles
 from test_gpu_heads import _decoder_net
@@ -205,40 +205,18 @@ SCENE = 640
 def test_scene_384_tiles():
     """infer_one_img with 384-px tiles (3 x 3 tiles over a 640-px scene, a ragged last batch of 1): the u8 masks of pass 1 against
     oracle.scene, then the graph stage-wise on identical inputs, as tests/test_gpu_scene.py does at 256 px."""
-    from sam_road_amd import Config, SAMRoad
-    from sam_road_amd.graph_points import extract_graph_points
+    from sam_road_amd import Config
     from sam_road_amd.inferencer import infer_one_img
-    warnings.simplefilter("ignore")
-    oracle = SAMRoadOracle(AttrDict(SCENE_CFG)).eval()
-    sd = synth_state_dict(oracle, 78)
-    sd["map_decoder.7.bias"] = torch.tensor([-0.3, 0.2])   # denser masks than the default -3
-    oracle.load_state_dict(sd, strict=True)
-    net = SAMRoad(Config(SCENE_CFG))
-    net.load_state_dict(sd, strict=True)
-    net.eval().to("cuda")
+    oracle, net = scene_kit.build_pair(SCENE_CFG, seed=78)
     img = synth_scene(SCENE, seed=9)
-    cfg = dict(SCENE_CFG)
-    infos, feats, kp_r, road_r = oscene.infer_pass1(oracle, img, AttrDict(cfg))
-    assert len(infos) == 9
-    cfg["ITSC_THRESHOLD"] = float(np.percentile(kp_r[kp_r > 0], 99.5)) / 255.0
-    cfg["ROAD_THRESHOLD"] = float(np.percentile(road_r[road_r > 0], 98.0)) / 255.0
-    nodes, edges, kp, road = infer_one_img(net, img, Config(cfg))
-    for got, ref in ((kp, kp_r), (road, road_r)):
-        d = np.abs(got.astype(int) - ref.astype(int))
-        assert d.max() <= 2
+    ref = scene_kit.oracle_scene(oracle, img, SCENE_CFG["INFER_PATCHES_PER_EDGE"], cfg=SCENE_CFG)
+    assert len(ref[0]) == 9
+    cfg = dict(SCENE_CFG, **scene_kit.thresholds(ref[2], ref[3]))
+    got = infer_one_img(net, img, Config(cfg))
+    for mask, mask_r in zip(got[2:], ref[2:]):
+        d = np.abs(mask.astype(int) - mask_r.astype(int))
         T.check("patch_sizes_scene384_u8_within1", (d <= 1).mean(), T.U8_WITHIN1, at_least=True)
-    assert kp_r.max() > 0 and road_r.max() > 0
-    pts = extract_graph_points(kp, road, Config(cfg))
-    np.testing.assert_array_equal(pts, oscene.extract_graph_points(kp, road, AttrDict(cfg)))
-    np.testing.assert_array_equal(nodes, pts[:, ::-1])
-    assert pts.shape[0] > 20, "synthetic scene produced too few points to be a meaningful test"
-    edges_r, sums_r, cnts_r = oscene.infer_pass2(oracle, feats, pts, infos, AttrDict(cfg))
-    got = {(int(a), int(b)) for a, b in edges.tolist()}
-    ref = {(int(a), int(b)) for a, b in edges_r.tolist()}
-    firm = {e for e, s in sums_r.items() if abs(s / cnts_r[e] - cfg["TOPO_THRESHOLD"]) > 0.003}
-    assert {e for e in ref if e in firm} == {e for e in got if e in firm}
-    assert len(got ^ ref) <= max(2, 0.02 * len(ref))
-    assert len(sums_r) > 50
+    scene_kit.check_scene_parity(None, got, ref, cfg, oracle)
 
 
 # ---- the range ------------------------------------------------------------------------------------------------------------------------

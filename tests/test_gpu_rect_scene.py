@@ -4,67 +4,27 @@ There is no reference behaviour for H != W (the reference reads img.shape[0] for
 rectangular scene embedded in the top-left corner of a zero square scene, run through the SQUARE C entry points (srh_scene_pass1 /
 srh_scene_normalise, one `int S`) with the rectangle's tile origins, reads identical pixels through identical kernels — the
 rectangular entry points must give the same bits.  The parity tests against the CPU oracle reuse the bounds tests/test_gpu_scene.py
-applies to this very configuration; the oracle's tile list is built here, independently of sam_road_amd/tiling.py.
+applies to this very configuration; the oracle's tile list is built in tests/scene_kit.py, independently of sam_road_amd/tiling.py.
 """
-import warnings
-
 import numpy as np
 import pytest
 import torch
 
-import tolerances
-
 pytestmark = pytest.mark.gpu
 
 from oracle import scene as oscene
-from oracle.samroad import AttrDict, SAMRoadOracle
-from oracle.synth import synth_scene, synth_state_dict
+from oracle.synth import synth_scene
 
-# the configuration of tests/test_gpu_scene.py
-CFG = dict(SAM_VERSION="vit_b", PATCH_SIZE=256, TOPONET_VERSION="normal", SAM_CKPT_PATH="",
-           ENCODER_DEPTH=2, ENCODER_GLOBAL_ATTN_INDEXES=[1],
-           INFER_BATCH_SIZE=5, SAMPLE_MARGIN=16, INFER_PATCHES_PER_EDGE=4,
-           ITSC_THRESHOLD=0.5, ROAD_THRESHOLD=0.5, TOPO_THRESHOLD=0.5,
-           ITSC_NMS_RADIUS=8, ROAD_NMS_RADIUS=16, NEIGHBOR_RADIUS=64, MAX_NEIGHBOR_QUERIES=16)
+from scene_kit import CFG, check_scene_parity, oracle_scene, pair, rect_grid, rect_scene, thresholds  # noqa: F401  (pair is a fixture)
+from scene_kit import same_bits as _same_bits
+from scene_kit import xy_of as _xy
+
 # (H, W, INFER_PATCHES_PER_EDGE, scene seed): H < W with a ragged last batch (15 tiles, batch 5 ... 3 x 5), H > W, and an odd
 # pitch whose rows are not 4-byte aligned.  Seeds and the percentile thresholds below were chosen WITH THE ORACLE ALONE on the CPU:
 #   384x640 seed 41: 453 points, 8419 voted edges, 0.38 % of them within TOPO_SCORE of the threshold
 #   640x384 seed 42: 489 points, 9302 voted edges, 0.22 %
 #   401x523 seed 43: 260 points, 4183 voted edges, 0.77 %
 SCENES = [(384, 640, [3, 5], 41), (640, 384, [5, 3], 42), (401, 523, 4, 43)]
-KP_PERCENTILE, ROAD_PERCENTILE = 99.5, 98.0
-
-
-def rect_scene(H, W, seed):
-    """oracle.synth.synth_scene is square: a contiguous rectangle cut out of a larger square."""
-    return np.ascontiguousarray(synth_scene(max(H, W), seed=seed)[:H, :W])
-
-
-def rect_grid(H, W, margin, P, per_edge):
-    """The reference's tile rule (dataset.py:56-67) per axis, restated here: x origins from W and n_x, y origins from H and n_y,
-    x outer / y inner.  per_edge: int or [n_y, n_x]."""
-    n_y, n_x = (per_edge, per_edge) if isinstance(per_edge, int) else per_edge
-    xs = [round(v) for v in np.linspace(start=margin, stop=W - (P + margin), num=n_x)]
-    ys = [round(v) for v in np.linspace(start=margin, stop=H - (P + margin), num=n_y)]
-    return [(0, (x, y), (x + P, y + P)) for x in xs for y in ys]
-
-
-@pytest.fixture(scope="module")
-def pair():
-    from sam_road_amd import Config, SAMRoad
-    warnings.simplefilter("ignore")
-    oracle = SAMRoadOracle(AttrDict(CFG)).eval()
-    sd = synth_state_dict(oracle, 77)
-    sd["map_decoder.7.bias"] = torch.tensor([-0.3, 0.2])   # denser masks than the default -3
-    oracle.load_state_dict(sd, strict=True)
-    net = SAMRoad(Config(CFG))
-    net.load_state_dict(sd, strict=True)
-    net.eval().to("cuda")
-    return oracle, net
-
-
-def _xy(infos):
-    return torch.tensor([[p[1][0], p[1][1]] for p in infos], dtype=torch.int32).cuda()
 
 
 def _abi_pass1(net, entry, scene, dims, xy, bs):
@@ -91,12 +51,6 @@ def _abi_normalise(net, entry, kp_c, road_c, dims, xy):
         ctx.check(getattr(ctx.lib, entry)(ctx.handle, kp_c.data_ptr(), road_c.data_ptr(), *dims, xy.data_ptr(), xy.shape[0],
                                           net.image_size, kp.data_ptr(), road.data_ptr(), net._stream(dev)), entry)
     return kp, road
-
-
-def _same_bits(a, b):
-    a, b = a.contiguous().cpu().numpy(), b.contiguous().cpu().numpy()
-    assert a.dtype == b.dtype and a.shape == b.shape
-    np.testing.assert_array_equal(a.view(np.uint8), b.view(np.uint8))
 
 
 @pytest.mark.parametrize("H,W,per_edge,seed", SCENES)
@@ -130,9 +84,7 @@ def test_rect_equals_square_path_bit_for_bit(pair, H, W, per_edge, seed):
     # whole pipeline: infer_one_img on the rectangle == the product's stages on the cropped square-path masks and embeddings
     kp_m = np.ascontiguousarray(kpu_sq[:H, :W].cpu().numpy())
     road_m = np.ascontiguousarray(roadu_sq[:H, :W].cpu().numpy())
-    cfg = Config(dict(CFG, INFER_PATCHES_PER_EDGE=per_edge,
-                      ITSC_THRESHOLD=float(np.percentile(kp_m[kp_m > 0], KP_PERCENTILE)) / 255.0,
-                      ROAD_THRESHOLD=float(np.percentile(road_m[road_m > 0], ROAD_PERCENTILE)) / 255.0))
+    cfg = Config(dict(CFG, INFER_PATCHES_PER_EDGE=per_edge, **thresholds(kp_m, road_m)))
     pts = extract_graph_points(kp_m, road_m, cfg)
     assert pts.shape[0] > 20
     votes = edge_votes(net, emb_sq.permute(0, 3, 1, 2), pts, infos, 0, len(infos), cfg, torch.device("cuda"))
@@ -148,62 +100,25 @@ def test_rect_equals_square_path_bit_for_bit(pair, H, W, per_edge, seed):
     assert nodes[:, 1].max() >= H if W > H else nodes[:, 0].max() >= W
 
 
-def _oracle_pass1(oracle, img, infos, bs):
-    feats, scores = [], []
-    for i in range(0, len(infos), bs):
-        s, f = oracle.infer_masks_and_img_features(oscene.get_batch_img_patches(img, infos[i:i + bs]))
-        feats.append(f)
-        scores.append(s)
-    return feats, oscene.fuse_masks(img.shape[:2], infos, scores)
-
-
 @pytest.mark.parametrize("H,W,per_edge,seed", SCENES)
 def test_rect_scene_parity_with_oracle(pair, H, W, per_edge, seed):
     """Pass-1 u8 masks against the oracle's fuse_masks with the bounds of test_scene_pass1_masks; pass 2 on identical points with
     the bounds of test_infer_one_img_end_to_end.  The three conditions on the scene (points, voted edges, share of edges the "firm"
     filter leaves out) are asserted on the oracle's numbers."""
     from sam_road_amd import Config
-    from sam_road_amd.graph_points import extract_graph_points
     from sam_road_amd.inferencer import infer_one_img
     oracle, net = pair
-    tag = f"rect_{H}x{W}"
     img = rect_scene(H, W, seed)
-    m, P, bs = CFG["SAMPLE_MARGIN"], CFG["PATCH_SIZE"], CFG["INFER_BATCH_SIZE"]
-    infos = rect_grid(H, W, m, P, per_edge)
-    feats, (kp_r, road_r) = _oracle_pass1(oracle, img, infos, bs)
-    assert kp_r.shape == road_r.shape == (H, W) and kp_r.max() > 0 and road_r.max() > 0
-    cfg = dict(CFG, INFER_PATCHES_PER_EDGE=per_edge,
-               ITSC_THRESHOLD=float(np.percentile(kp_r[kp_r > 0], KP_PERCENTILE)) / 255.0,
-               ROAD_THRESHOLD=float(np.percentile(road_r[road_r > 0], ROAD_PERCENTILE)) / 255.0)
-    nodes, edges, kp, road = infer_one_img(net, img, Config(cfg))
-    assert kp.shape == road.shape == (H, W) and kp.dtype == road.dtype == np.uint8
-    for name, got, ref in (("kp", kp, kp_r), ("road", road, road_r)):
-        d = np.abs(got.astype(int) - ref.astype(int))
-        print(f"[parity] {tag}_{name}_u8_max_diff: {d.max()} levels (bound <= 2)")
-        tolerances.check(f"{tag}_{name}_u8_within1", (d <= 1).mean(), tolerances.U8_WITHIN1, at_least=True)
-        tolerances.check(f"{tag}_{name}_u8_max_diff", d.max(), 3)                 # integers: < 3 is <= 2 levels
-        assert d.max() <= 2
+    m = CFG["SAMPLE_MARGIN"]
+    ref = oracle_scene(oracle, img, per_edge)
+    assert ref[2].shape == ref[3].shape == (H, W)
+    cfg = dict(CFG, INFER_PATCHES_PER_EDGE=per_edge, **thresholds(ref[2], ref[3]))
+    got = infer_one_img(net, img, Config(cfg))
+    check_scene_parity(f"rect_{H}x{W}", got, ref, cfg, oracle)
+    for mask in got[2:]:
         # the margin no tile covers is 0 on all four sides
-        assert (got[:m] == 0).all() and (got[-m:] == 0).all() and (got[:, :m] == 0).all() and (got[:, -m:] == 0).all()
-        assert (got[m:-m, m:-m] > 0).any()
-    # points: product host stage on the product masks == oracle host stage on the same masks
-    pts = extract_graph_points(kp, road, Config(cfg))
-    np.testing.assert_array_equal(pts, oscene.extract_graph_points(kp, road, AttrDict(cfg)))
-    np.testing.assert_array_equal(nodes, pts[:, ::-1])
-    assert pts.shape[0] > 20, "scene produced too few points to be a meaningful test"
-    assert pts[:, 0].max() < W and pts[:, 1].max() < H                             # (x, y)
-    # pass 2 on the same points: oracle (its own fp32 features) vs HIP (its own features)
-    edges_r, sums_r, cnts_r = oscene.infer_pass2(oracle, feats, pts, infos, AttrDict(cfg))
-    got = {(int(a), int(b)) for a, b in edges.tolist()}
-    ref = {(int(a), int(b)) for a, b in edges_r.tolist()}
-    firm = {e for e, s in sums_r.items() if abs(s / cnts_r[e] - cfg["TOPO_THRESHOLD"]) > tolerances.TOPO_SCORE}
-    assert len(sums_r) > 50
-    left_out = 1.0 - len(firm) / len(sums_r)
-    print(f"[parity] {tag}: {pts.shape[0]} points, {len(sums_r)} voted edges, {len(ref)} oracle edges, firm filter leaves out {left_out:.4f}")
-    assert left_out <= 0.05
-    assert {e for e in ref if e in firm} == {e for e in got if e in firm}
-    tolerances.check(f"{tag}_edge_symdiff", len(got ^ ref), int(max(2, 0.02 * len(ref))) + 1)    # integers: < floor(b) + 1 is <= b
-    assert len(got ^ ref) <= max(2, 0.02 * len(ref))
+        assert (mask[:m] == 0).all() and (mask[-m:] == 0).all() and (mask[:, :m] == 0).all() and (mask[:, -m:] == 0).all()
+        assert (mask[m:-m, m:-m] > 0).any()
 
 
 def test_square_stays_square(pair):
@@ -228,8 +143,7 @@ def test_square_stays_square(pair):
     assert int(na[0].max()) > 0 and int(na[1].max()) > 0
     kp0 = na[0].cpu().numpy()
     road0 = na[1].cpu().numpy()
-    thr = dict(ITSC_THRESHOLD=float(np.percentile(kp0[kp0 > 0], KP_PERCENTILE)) / 255.0,
-               ROAD_THRESHOLD=float(np.percentile(road0[road0 > 0], ROAD_PERCENTILE)) / 255.0)
+    thr = thresholds(kp0, road0)
     one = infer_one_img(net, img, Config(dict(CFG, INFER_PATCHES_PER_EDGE=4, **thr)))
     two = infer_one_img(net, img, Config(dict(CFG, INFER_PATCHES_PER_EDGE=[4, 4], **thr)))
     assert one[0].shape[0] > 20 and one[1].shape[0] > 20
@@ -272,8 +186,7 @@ def test_infer_imgs_pipeline_rect_scenes_equal_serial(pair):
     imgs = [rect_scene(h, w, 50 + i) for i, (h, w) in enumerate(shapes)]
     assert [im.shape[:2] for im in imgs] == shapes and imgs[0].nbytes == imgs[1].nbytes
     _, _, kp0, road0 = infer_one_img(net, imgs[0], Config(dict(CFG)))
-    cfg = Config(dict(CFG, ITSC_THRESHOLD=float(np.percentile(kp0[kp0 > 0], KP_PERCENTILE)) / 255.0,
-                      ROAD_THRESHOLD=float(np.percentile(road0[road0 > 0], ROAD_PERCENTILE)) / 255.0))      # 4 tiles per axis for every shape
+    cfg = Config(dict(CFG, **thresholds(kp0, road0)))      # 4 tiles per axis for every shape
     want = [infer_one_img(net, im, cfg) for im in imgs]
     print("points / edges per scene:", [(w[0].shape[0], w[1].shape[0]) for w in want])
     assert min(w[0].shape[0] for w in want) > 20 and min(w[1].shape[0] for w in want) > 20

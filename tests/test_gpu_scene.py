@@ -1,52 +1,24 @@
 """Scene-level parity (pass 1 of infer_one_img and the whole pipeline) of the HIP path vs the CPU oracle.
 Run on an MI355X: pytest -m gpu."""
-import warnings
-
 import numpy as np
 import pytest
 import torch
 
 pytestmark = pytest.mark.gpu
 
-from oracle import scene as oscene
-from oracle.samroad import AttrDict, SAMRoadOracle
-from oracle.synth import synth_scene, synth_state_dict
+from oracle.samroad import AttrDict
+from oracle.synth import synth_scene
 
-CFG = dict(SAM_VERSION="vit_b", PATCH_SIZE=256, TOPONET_VERSION="normal", SAM_CKPT_PATH="",
-           ENCODER_DEPTH=2, ENCODER_GLOBAL_ATTN_INDEXES=[1],
-           INFER_BATCH_SIZE=5, SAMPLE_MARGIN=16, INFER_PATCHES_PER_EDGE=4,
-           ITSC_THRESHOLD=0.5, ROAD_THRESHOLD=0.5, TOPO_THRESHOLD=0.5,
-           ITSC_NMS_RADIUS=8, ROAD_NMS_RADIUS=16, NEIGHBOR_RADIUS=64, MAX_NEIGHBOR_QUERIES=16)
+from scene_kit import CFG, check_scene_parity, oracle_scene, pair, thresholds  # noqa: F401  (pair is a fixture)
+
 SCENE = 448
-
-
-@pytest.fixture(scope="module")
-def pair():
-    from sam_road_amd import Config, SAMRoad
-    warnings.simplefilter("ignore")
-    oracle = SAMRoadOracle(AttrDict(CFG)).eval()
-    sd = synth_state_dict(oracle, 77)
-    sd["map_decoder.7.bias"] = torch.tensor([-0.3, 0.2])   # denser masks than the default -3
-    oracle.load_state_dict(sd, strict=True)
-    net = SAMRoad(Config(CFG))
-    net.load_state_dict(sd, strict=True)
-    net.eval().to("cuda")
-    return oracle, net
-
-
-def oracle_pass1(oracle, img, cfg):
-    infos = oscene.get_patch_info_one_img(0, img.shape[0], cfg.SAMPLE_MARGIN, cfg.PATCH_SIZE, cfg.INFER_PATCHES_PER_EDGE)
-    bs = cfg.INFER_BATCH_SIZE
-    scores = [oracle.infer_masks_and_img_features(oscene.get_batch_img_patches(img, infos[i:i + bs]))[0]
-              for i in range(0, len(infos), bs)]
-    return infos, oscene.fuse_masks(img.shape[:2], infos, scores)
 
 
 def test_scene_pass1_masks(pair):
     oracle, net = pair
     cfg = AttrDict(CFG)
     img = synth_scene(SCENE, seed=5)
-    infos, (kp_ref, road_ref) = oracle_pass1(oracle, img, cfg)
+    infos, _, kp_ref, road_ref = oracle_scene(oracle, img, cfg.INFER_PATCHES_PER_EDGE)
     xy = torch.tensor([[p[1][0], p[1][1]] for p in infos], dtype=torch.int32)
     scene = torch.as_tensor(img).cuda()
     kp_c, road_c, emb = net.scene_pass1(scene, xy.cuda(), cfg.INFER_BATCH_SIZE)     # ragged last batch (16 = 3*5+1)
@@ -67,32 +39,14 @@ def test_infer_one_img_end_to_end(pair):
     then edge votes of pass 2 on the same point set; the product's own infer_one_img must reproduce the
     product-side stages exactly."""
     from sam_road_amd import Config
-    from sam_road_amd.graph_points import extract_graph_points
     from sam_road_amd.inferencer import infer_one_img
     oracle, net = pair
     img = synth_scene(SCENE, seed=6)
-    cfg = dict(CFG)
-    infos, feats, kp_r, road_r = oscene.infer_pass1(oracle, img, AttrDict(cfg))
-    cfg["ITSC_THRESHOLD"] = float(np.percentile(kp_r[kp_r > 0], 99.5)) / 255.0
-    cfg["ROAD_THRESHOLD"] = float(np.percentile(road_r[road_r > 0], 98.0)) / 255.0
-    nodes, edges, kp, road = infer_one_img(net, img, Config(cfg))
-    assert (np.abs(kp.astype(int) - kp_r.astype(int)) <= 2).all()
-    assert (np.abs(road.astype(int) - road_r.astype(int)) <= 2).all()
-    # points: product host stage on the product masks == oracle host stage on the same masks
-    pts = extract_graph_points(kp, road, Config(cfg))
-    np.testing.assert_array_equal(pts, oscene.extract_graph_points(kp, road, AttrDict(cfg)))
-    np.testing.assert_array_equal(nodes, pts[:, ::-1])
-    assert pts.shape[0] > 20, "synthetic scene produced too few points to be a meaningful test"
-    # pass 2 on the same points: oracle (its own fp32 features) vs HIP (its own features)
-    edges_r, sums_r, cnts_r = oscene.infer_pass2(oracle, feats, pts, infos, AttrDict(cfg))
-    got = {(int(a), int(b)) for a, b in edges.tolist()}
-    ref = {(int(a), int(b)) for a, b in edges_r.tolist()}
+    ref = oracle_scene(oracle, img, CFG["INFER_PATCHES_PER_EDGE"])
+    cfg = dict(CFG, **thresholds(ref[2], ref[3]))
     # every oracle edge decision with a margin > 0.003 from the threshold must be reproduced (measured max |HIP - oracle| mean edge
     # score over 12k edges: 6e-4, tools/scene_edge_diag.py)
-    firm = {e for e, s in sums_r.items() if abs(s / cnts_r[e] - cfg["TOPO_THRESHOLD"]) > 0.003}
-    assert {e for e in ref if e in firm} == {e for e in got if e in firm}
-    assert len(got ^ ref) <= max(2, 0.02 * len(ref))
-    assert len(sums_r) > 50
+    check_scene_parity(None, infer_one_img(net, img, Config(cfg)), ref, cfg, oracle)
 
 
 def test_infer_imgs_pipeline_equals_serial(pair):
@@ -106,8 +60,7 @@ def test_infer_imgs_pipeline_equals_serial(pair):
     # different scene sizes in one run: the staging pools grow and are re-viewed per scene
     imgs = [synth_scene(size, seed=s) for size, s in ((SCENE, 6), (384, 7), (SCENE, 8), (512, 9), (384, 10))]
     _, _, kp0, road0 = infer_one_img(net, imgs[0], Config(dict(CFG)))
-    cfg = Config(dict(CFG, ITSC_THRESHOLD=float(np.percentile(kp0[kp0 > 0], 99.5)) / 255.0,
-                      ROAD_THRESHOLD=float(np.percentile(road0[road0 > 0], 98.0)) / 255.0))
+    cfg = Config(dict(CFG, **thresholds(kp0, road0)))
     want = [infer_one_img(net, im, cfg) for im in imgs]
     print("points / edges per scene:", [(w[0].shape[0], w[1].shape[0]) for w in want])
     assert len({w[0].shape[0] for w in want}) > 1 and min(w[0].shape[0] for w in want) > 20 and max(w[1].shape[0] for w in want) > 20

@@ -12,42 +12,18 @@ import numpy as np
 import pytest
 import torch
 
-import tolerances
-
 pytestmark = pytest.mark.gpu
 
-from oracle import scene as oscene
-from oracle.samroad import AttrDict
+from scene_kit import CFG, FILL, check_scene_parity, kernel_rows, make_mask, np_pad, oracle_scene, pair, rect_grid, rect_scene  # noqa: F401
+from scene_kit import crop_pads as _crop
+from scene_kit import net_for as _net_for
+from scene_kit import same_bits as _same
+from scene_kit import shift_infos as _shift
+from scene_kit import thresholds as _thresholds
+from scene_kit import xy_of as _xy
 
-from test_gpu_valid_mask import CFG, KP_PERCENTILE, ROAD_PERCENTILE, _net_for, _same, _thresholds, make_mask, pair, rect_grid, rect_scene  # noqa: F401
-
-FILL = (124, 116, 104)
 MODES = ("reflect", "edge", "constant")
 P, MARGIN, BS = CFG["PATCH_SIZE"], CFG["SAMPLE_MARGIN"], CFG["INFER_BATCH_SIZE"]
-
-
-def np_pad(arr, pads, mode, fill=FILL):
-    """numpy.pad is the reference of the three modes; a constant colour goes channel by channel."""
-    top, bottom, left, right = pads
-    width = ((top, bottom), (left, right))
-    if mode != "constant":
-        return np.ascontiguousarray(np.pad(arr, width + ((0, 0),) * (arr.ndim - 2), mode=mode))
-    if arr.ndim == 2:
-        return np.ascontiguousarray(np.pad(arr, width, mode="constant", constant_values=arr.dtype.type(fill[0])))
-    return np.ascontiguousarray(np.stack([np.pad(arr[..., c], width, mode="constant", constant_values=fill[c]) for c in range(arr.shape[2])], -1))
-
-
-def _xy(infos):
-    return torch.tensor([[p[1][0], p[1][1]] for p in infos], dtype=torch.int32).reshape(-1, 2).cuda()
-
-
-def _shift(infos, pads):
-    top, _, left, _ = pads
-    return [(k, (x0 - left, y0 - top), (x1 - left, y1 - top)) for k, (x0, y0), (x1, y1) in infos]
-
-
-def _crop(m, pads, shape):
-    return np.ascontiguousarray(m[pads[0]:pads[0] + shape[0], pads[2]:pads[2] + shape[1]])
 
 
 # ---- 1. the kernel ---------------------------------------------------------------------------------------------------------------------
@@ -189,20 +165,13 @@ def test_border_on_the_odd_pitch_scene(pair):
     assert not bare[3][:MARGIN].any() and not bare[3][:, -MARGIN:].any() and got[3][:MARGIN].any() and got[3][:, -MARGIN:].any()
     # border 0 on a scene that is large enough: the bytes of a run without the key, and the pad kernel is not launched
     ctx = _lib.Context.get(torch.cuda.current_device())
-    ctx.profile_read()
-    ctx.profile_enable(True)
-    try:
+    with kernel_rows(ctx) as rows:
         zero = infer_one_img(net, img, Config(dict(plain, SCENE_PAD={"border": 0, "mode": "edge"})))
-        torch.cuda.synchronize()
-        rows_zero = {r["name"] for r in ctx.profile_read() if r["launches"]}
+        rows_zero = rows()
         infer_one_img(net, img, cfg)
-        torch.cuda.synchronize()
-        rows_pad = {r["name"] for r in ctx.profile_read() if r["launches"]}
+        rows_pad = rows()
         infer_one_img(net, img, plain)
-        torch.cuda.synchronize()
-        rows_plain = {r["name"] for r in ctx.profile_read() if r["launches"]}
-    finally:
-        ctx.profile_enable(False)
+        rows_plain = rows()
     for a, b in zip(zero, bare):
         _same(a, b)
     assert "scene_pad" not in rows_zero and rows_zero == rows_plain and rows_pad == rows_plain | {"scene_pad"}
@@ -315,48 +284,15 @@ def test_padded_scene_parity_with_oracle(pair):
     """The checks and bounds of test_rect_scene_parity_with_oracle (tests/tolerances.py) on the 523 x 701 scene with a reflected border of
     24 px: the oracle runs oracle.scene's pieces on the numpy-padded scene, its masks are cropped, its pass 2 takes the shifted tiles."""
     from sam_road_amd import Config
-    from sam_road_amd.graph_points import extract_graph_points
     from sam_road_amd.inferencer import infer_one_img
     oracle, net = pair
     H, W, per_edge, seed, pads = 523, 701, [4, 5], 44, (24, 24, 24, 24)
-    tag = f"pad24_{H}x{W}"
     img = rect_scene(H, W, seed)
-    padded = np_pad(img, pads, "reflect")
-    infos_v = rect_grid(H + 48, W + 48, MARGIN, P, per_edge)
-    feats, scores = [], []
-    for i in range(0, len(infos_v), BS):
-        s, f = oracle.infer_masks_and_img_features(oscene.get_batch_img_patches(padded, infos_v[i:i + BS]))
-        feats.append(f)
-        scores.append(s)
-    kp_v, road_v = oscene.fuse_masks(padded.shape[:2], infos_v, scores)
-    kp_r, road_r = _crop(kp_v, pads, (H, W)), _crop(road_v, pads, (H, W))
-    assert kp_r.shape == road_r.shape == (H, W) and kp_r.max() > 0 and road_r.max() > 0
-    cfg = dict(CFG, INFER_PATCHES_PER_EDGE=per_edge, SCENE_PAD=24,
-               ITSC_THRESHOLD=float(np.percentile(kp_r[kp_r > 0], KP_PERCENTILE)) / 255.0,
-               ROAD_THRESHOLD=float(np.percentile(road_r[road_r > 0], ROAD_PERCENTILE)) / 255.0)
-    nodes, edges, kp, road = infer_one_img(net, img, Config(cfg))
-    assert kp.shape == road.shape == (H, W) and kp.dtype == road.dtype == np.uint8
-    for name, got, ref in (("kp", kp, kp_r), ("road", road, road_r)):
-        d = np.abs(got.astype(int) - ref.astype(int))
-        print(f"[parity] {tag}_{name}_u8_max_diff: {d.max()} levels (bound <= 2)")
-        tolerances.check(f"{tag}_{name}_u8_within1", (d <= 1).mean(), tolerances.U8_WITHIN1, at_least=True)
-        tolerances.check(f"{tag}_{name}_u8_max_diff", d.max(), 3)                 # integers: < 3 is <= 2 levels
-        assert d.max() <= 2
+    ref = oracle_scene(oracle, img, per_edge, pads=pads)
+    assert ref[2].shape == ref[3].shape == (H, W) and ref[0] == _shift(rect_grid(H + 48, W + 48, MARGIN, P, per_edge), pads)
+    cfg = dict(CFG, INFER_PATCHES_PER_EDGE=per_edge, SCENE_PAD=24, **_thresholds(ref[2], ref[3]))
+    got = infer_one_img(net, img, Config(cfg))
+    check_scene_parity(f"pad24_{H}x{W}", got, ref, cfg, oracle)
+    for mask in got[2:]:
         # the border of 24 px closes the 16-px frame no tile covered: every pixel of the real scene is covered now
-        assert (got[:MARGIN] > 0).any() and (got[-MARGIN:] > 0).any() and (got[:, :MARGIN] > 0).any() and (got[:, -MARGIN:] > 0).any()
-    pts = extract_graph_points(kp, road, Config(cfg))
-    np.testing.assert_array_equal(pts, oscene.extract_graph_points(kp, road, AttrDict(cfg)))
-    np.testing.assert_array_equal(nodes, pts[:, ::-1])
-    assert pts.shape[0] > 20, "scene produced too few points to be a meaningful test"
-    assert pts[:, 0].max() < W and pts[:, 1].max() < H and pts.min() >= 0           # (x, y)
-    edges_r, sums_r, cnts_r = oscene.infer_pass2(oracle, feats, pts, _shift(infos_v, pads), AttrDict(cfg))
-    got = {(int(a), int(b)) for a, b in edges.tolist()}
-    ref = {(int(a), int(b)) for a, b in edges_r.tolist()}
-    firm = {e for e, s in sums_r.items() if abs(s / cnts_r[e] - cfg["TOPO_THRESHOLD"]) > tolerances.TOPO_SCORE}
-    assert len(sums_r) > 50
-    left_out = 1.0 - len(firm) / len(sums_r)
-    print(f"[parity] {tag}: {pts.shape[0]} points, {len(sums_r)} voted edges, {len(ref)} oracle edges, firm filter leaves out {left_out:.4f}")
-    assert left_out <= 0.05
-    assert {e for e in ref if e in firm} == {e for e in got if e in firm}
-    tolerances.check(f"{tag}_edge_symdiff", len(got ^ ref), int(max(2, 0.02 * len(ref))) + 1)    # integers: < floor(b) + 1 is <= b
-    assert len(got ^ ref) <= max(2, 0.02 * len(ref))
+        assert (mask[:MARGIN] > 0).any() and (mask[-MARGIN:] > 0).any() and (mask[:, :MARGIN] > 0).any() and (mask[:, -MARGIN:] > 0).any()

@@ -9,7 +9,6 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
-from oracle import scene as oscene
 from oracle.samroad import AttrDict, SAMRoadOracle
 from oracle.synth import synth_queries, synth_scene, synth_state_dict, synth_tiles
 
@@ -269,25 +268,9 @@ def test_unsupported_k_from_c_abi(K):
 
 
 # ---- the scene pipeline ------------------------------------------------------------------------------------------------------------
-SCENE_CFG = dict(SAM_VERSION="vit_b", PATCH_SIZE=256, TOPONET_VERSION="normal", SAM_CKPT_PATH="",
-                 ENCODER_DEPTH=2, ENCODER_GLOBAL_ATTN_INDEXES=[1],
-                 INFER_BATCH_SIZE=5, SAMPLE_MARGIN=16, INFER_PATCHES_PER_EDGE=4,
-                 ITSC_THRESHOLD=0.5, ROAD_THRESHOLD=0.5, TOPO_THRESHOLD=0.5,
-                 ITSC_NMS_RADIUS=8, ROAD_NMS_RADIUS=16, NEIGHBOR_RADIUS=64, MAX_NEIGHBOR_QUERIES=16)
-
-
-@pytest.fixture(scope="module")
-def scene_pair():
-    from sam_road_amd import Config, SAMRoad
-    warnings.simplefilter("ignore")
-    oracle = SAMRoadOracle(AttrDict(SCENE_CFG)).eval()
-    sd = synth_state_dict(oracle, 77)
-    sd["map_decoder.7.bias"] = torch.tensor([-0.3, 0.2])   # denser masks than the default -3
-    oracle.load_state_dict(sd, strict=True)
-    net = SAMRoad(Config(SCENE_CFG))
-    net.load_state_dict(sd, strict=True)
-    net.eval().to("cuda")
-    return oracle, net
+from scene_kit import CFG as SCENE_CFG
+from scene_kit import check_scene_parity, oracle_scene, thresholds
+from scene_kit import pair as scene_pair  # noqa: F401  (a fixture)
 
 
 @pytest.mark.parametrize("K", [8, 32])
@@ -295,28 +278,13 @@ def test_infer_one_img_end_to_end_at_k(scene_pair, K):
     """infer_one_img at MAX_NEIGHBOR_QUERIES = K on the 448-px synthetic scene, stage-wise against oracle.scene (as
     test_gpu_scene.py::test_infer_one_img_end_to_end does at K = 16)."""
     from sam_road_amd import Config
-    from sam_road_amd.graph_points import extract_graph_points
     from sam_road_amd.inferencer import infer_one_img
     oracle, net = scene_pair
     img = synth_scene(448, seed=6)
     cfg = dict(SCENE_CFG, MAX_NEIGHBOR_QUERIES=K)
-    infos, feats, kp_r, road_r = oscene.infer_pass1(oracle, img, AttrDict(cfg))
-    cfg["ITSC_THRESHOLD"] = float(np.percentile(kp_r[kp_r > 0], 99.5)) / 255.0
-    cfg["ROAD_THRESHOLD"] = float(np.percentile(road_r[road_r > 0], 98.0)) / 255.0
-    nodes, edges, kp, road = infer_one_img(net, img, Config(cfg))
-    assert (np.abs(kp.astype(int) - kp_r.astype(int)) <= 2).all()
-    assert (np.abs(road.astype(int) - road_r.astype(int)) <= 2).all()
-    pts = extract_graph_points(kp, road, Config(cfg))
-    np.testing.assert_array_equal(pts, oscene.extract_graph_points(kp, road, AttrDict(cfg)))
-    np.testing.assert_array_equal(nodes, pts[:, ::-1])
-    assert pts.shape[0] > 20
-    edges_r, sums_r, cnts_r = oscene.infer_pass2(oracle, feats, pts, infos, AttrDict(cfg))
-    got = {(int(a), int(b)) for a, b in edges.tolist()}
-    ref = {(int(a), int(b)) for a, b in edges_r.tolist()}
-    firm = {e for e, s in sums_r.items() if abs(s / cnts_r[e] - cfg["TOPO_THRESHOLD"]) > 0.003}
-    assert {e for e in ref if e in firm} == {e for e in got if e in firm}
-    assert len(got ^ ref) <= max(2, 0.02 * len(ref))
-    assert len(sums_r) > 50
+    ref = oracle_scene(oracle, img, cfg["INFER_PATCHES_PER_EDGE"], cfg=cfg)
+    cfg.update(thresholds(ref[2], ref[3]))
+    check_scene_parity(None, infer_one_img(net, img, Config(cfg)), ref, cfg, oracle)
 
 
 def test_infer_imgs_pipeline_equals_serial_at_k32(scene_pair):
@@ -325,8 +293,7 @@ def test_infer_imgs_pipeline_equals_serial_at_k32(scene_pair):
     _, net = scene_pair
     imgs = [synth_scene(size, seed=s) for size, s in ((448, 6), (384, 7), (448, 8))]
     _, _, kp0, road0 = infer_one_img(net, imgs[0], Config(dict(SCENE_CFG, MAX_NEIGHBOR_QUERIES=32)))
-    cfg = Config(dict(SCENE_CFG, MAX_NEIGHBOR_QUERIES=32, ITSC_THRESHOLD=float(np.percentile(kp0[kp0 > 0], 99.5)) / 255.0,
-                      ROAD_THRESHOLD=float(np.percentile(road0[road0 > 0], 98.0)) / 255.0))
+    cfg = Config(dict(SCENE_CFG, MAX_NEIGHBOR_QUERIES=32, **thresholds(kp0, road0)))
     want = [infer_one_img(net, im, cfg) for im in imgs]
     assert max(w[1].shape[0] for w in want) > 20
     got = list(infer_imgs(net, iter(imgs), cfg, tile_sharded=False))

@@ -15,21 +15,18 @@ import numpy as np
 import pytest
 import torch
 
-import tolerances
-
 pytestmark = pytest.mark.gpu
 
 from oracle import scene as oscene
 from oracle.samroad import AttrDict
 
-from test_gpu_valid_mask import (CFG, FILL, PARITY_SCENES, SCENES, _net_for, _same, _thresholds, _xy, make_mask, np_kept, pair,  # noqa: F401
-                                 rect_grid, rect_scene)
-
-NAMES = ("id", "flip_h", "flip_v", "rot180", "transpose", "rot90", "rot270", "anti_transpose")      # index = code
-
-
-def _dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
+from scene_kit import (CFG, FILL, NAMES, PARITY_SCENES, SCENES, check_scene_parity, kernel_rows, make_mask, np_kept, oracle_scene, pair,  # noqa: F401
+                       rect_grid, rect_scene)
+from scene_kit import dev as _dev
+from scene_kit import net_for as _net_for
+from scene_kit import same_bits as _same
+from scene_kit import thresholds as _thresholds
+from scene_kit import xy_of as _xy
 
 
 def _helpers():
@@ -233,11 +230,6 @@ def test_infer_imgs_with_tta_equals_serial(pair):
 
 
 # ---- 5. profile rows ------------------------------------------------------------------------------------------------------------------
-def _rows(ctx):
-    torch.cuda.synchronize()
-    return {r["name"] for r in ctx.profile_read() if r["launches"]}
-
-
 def test_profile_rows_and_abi_rejections(pair):
     from sam_road_amd import Config, _lib
     from sam_road_amd.inferencer import infer_one_img
@@ -247,15 +239,13 @@ def test_profile_rows_and_abi_rejections(pair):
     img = rect_scene(H, W, seed)
     base = dict(CFG, INFER_PATCHES_PER_EDGE=per_edge)
     ctx = _lib.Context.get(torch.cuda.current_device())
-    ctx.profile_read()
-    ctx.profile_enable(True)
     new = {"patch_im2col_oriented", "scores_unorient"}
-    try:
+    with kernel_rows(ctx) as rows:
         infer_one_img(net, img, Config(base))
         infer_one_img(net, img, Config(dict(base, TTA=["id"])))
-        plain = _rows(ctx)
+        plain = rows()
         infer_one_img(net, img, Config(dict(base, TTA=["id", "flip_v", "rot270"])))
-        tta = _rows(ctx)
+        tta = rows()
         print("kernel classes, plain:", sorted(plain), "| TTA:", sorted(tta))
         assert not (new & plain) and {"patch_im2col", "scene_add", "scene_count", "scene_normalise"} <= plain
         assert new <= tta and plain <= tta                                      # id's batches take today's path
@@ -274,13 +264,11 @@ def test_profile_rows_and_abi_rejections(pair):
         for codes, k in (([1, 0], None), ([5], None), ([0, 8], None), ([0, 3, 3], None), ([0, 0], None), ([0], 0), (list(range(8)) + [0], 9), ([0], -1)):
             assert call(codes, k) == -1, (codes, k)
         assert call([0], orients=None) == -1
-        assert not _rows(ctx) and not kp.any() and not road.any()               # SRH_ERR_BAD_ARG before anything is launched
+        assert not rows() and not kp.any() and not road.any()               # SRH_ERR_BAD_ARG before anything is launched
         assert call([0, 5]) == 0                                                # the same arguments with a good list run
-        assert new <= _rows(ctx) and kp.any()
+        assert new <= rows() and kp.any()
         with pytest.raises(ValueError, match="tta"):
             net.scene_pass1(scene, xy, 5, tta=[])
-    finally:
-        ctx.profile_enable(False)
 
 
 # ---- 7. against the oracle ------------------------------------------------------------------------------------------------------------
@@ -291,59 +279,15 @@ ORACLE_TTA = ["id", "rot90", "flip_h"]        # three orientations keep the CPU 
 ORACLE_SCENE = "384x640"
 
 
-def oracle_tta(oracle, img, per_edge, names):
-    """The expectation from the oracle's per-tile scores on orient_tile-d tiles, un-oriented and fused by oscene.fuse_masks over the k-fold
-    info list: (infos, id feats, kp u8, road u8).  Uses nothing of sam_road_amd but the two host helpers that are the table."""
-    orient_tile, unorient_tile = _helpers()
-    H, W = img.shape[:2]
-    P, bs = CFG["PATCH_SIZE"], CFG["INFER_BATCH_SIZE"]
-    infos = rect_grid(H, W, CFG["SAMPLE_MARGIN"], P, per_edge)
-    feats, scores = [], []
-    for name in names:
-        for i in range(0, len(infos), bs):
-            batch = torch.stack([torch.tensor(np.ascontiguousarray(orient_tile(img[y0:y1, x0:x1, :], name)), dtype=torch.float32)
-                                 for _, (x0, y0), (x1, y1) in infos[i:i + bs]], 0).contiguous()
-            s, f = oracle.infer_masks_and_img_features(batch)
-            scores.append(torch.from_numpy(np.stack([np.ascontiguousarray(unorient_tile(t, name)) for t in s.detach().numpy()])))
-            if name == "id":
-                feats.append(f)
-    kp, road = oscene.fuse_masks((H, W), infos * len(names), scores)
-    return infos, feats, kp, road
-
-
 def test_tta_scene_parity_with_oracle(pair):
-    """The assertions and bounds of test_rect_scene_parity_with_oracle (tests/tolerances.py) on a TTA-fused scene."""
+    """The assertions and bounds of test_rect_scene_parity_with_oracle (tests/tolerances.py) on a TTA-fused scene: the oracle's per-tile
+    scores on oriented tiles, un-oriented and fused by oscene.fuse_masks over the k-fold info list."""
     from sam_road_amd import Config
-    from sam_road_amd.graph_points import extract_graph_points
     from sam_road_amd.inferencer import infer_one_img
     oracle, net = pair
     H, W, per_edge, seed = PARITY_SCENES[ORACLE_SCENE]
-    tag = f"tta_{ORACLE_SCENE}"
     img = rect_scene(H, W, seed)
-    infos, feats, kp_r, road_r = oracle_tta(oracle, img, per_edge, ORACLE_TTA)
-    assert kp_r.max() > 0 and road_r.max() > 0
-    cfg = dict(CFG, INFER_PATCHES_PER_EDGE=per_edge, TTA=ORACLE_TTA, **_thresholds(kp_r, road_r))
-    nodes, edges, kp, road = infer_one_img(net, img, Config(cfg))
-    for name, got, ref in (("kp", kp, kp_r), ("road", road, road_r)):
-        d = np.abs(got.astype(int) - ref.astype(int))
-        print(f"[parity] {tag}_{name}_u8_max_diff: {d.max()} levels (bound <= 2)")
-        tolerances.check(f"{tag}_{name}_u8_within1", (d <= 1).mean(), tolerances.U8_WITHIN1, at_least=True)
-        tolerances.check(f"{tag}_{name}_u8_max_diff", d.max(), 3)                 # integers: < 3 is <= 2 levels
-        assert d.max() <= 2
-    pts = extract_graph_points(kp, road, Config(cfg))
-    np.testing.assert_array_equal(pts, oscene.extract_graph_points(kp, road, AttrDict(cfg)))
-    np.testing.assert_array_equal(nodes, pts[:, ::-1])
-    assert pts.shape[0] > 20
-    assert oscene.extract_graph_points(kp_r, road_r, AttrDict(cfg)).shape[0] > 20      # and on the oracle's own masks
-    edges_r, sums_r, cnts_r = oscene.infer_pass2(oracle, feats, pts, infos, AttrDict(cfg))
-    got = {(int(a), int(b)) for a, b in edges.tolist()}
-    ref = {(int(a), int(b)) for a, b in edges_r.tolist()}
-    firm = {e for e, s in sums_r.items() if abs(s / cnts_r[e] - cfg["TOPO_THRESHOLD"]) > tolerances.TOPO_SCORE}
-    left_out = 1.0 - len(firm) / len(sums_r)
-    print(f"[parity] {tag}: {len(infos)} tiles, {pts.shape[0]} points, {len(sums_r)} voted edges, {len(ref)} oracle edges, "
-          f"firm filter leaves out {left_out:.4f}, symmetric difference {len(got ^ ref)}")
-    assert len(sums_r) > 50
-    assert left_out <= 0.05
-    assert {e for e in ref if e in firm} == {e for e in got if e in firm}
-    tolerances.check(f"{tag}_edge_symdiff", len(got ^ ref), int(max(2, 0.02 * len(ref))) + 1)    # integers: < floor(b) + 1 is <= b
-    assert len(got ^ ref) <= max(2, 0.02 * len(ref))
+    ref = oracle_scene(oracle, img, per_edge, orientations=ORACLE_TTA)
+    cfg = dict(CFG, INFER_PATCHES_PER_EDGE=per_edge, TTA=ORACLE_TTA, **_thresholds(ref[2], ref[3]))
+    assert oscene.extract_graph_points(ref[2], ref[3], AttrDict(cfg)).shape[0] > 20      # and on the oracle's own masks
+    check_scene_parity(f"tta_{ORACLE_SCENE}", infer_one_img(net, img, Config(cfg)), ref, cfg, oracle)

@@ -8,117 +8,20 @@ from oracle.scene's pieces on the same filled scene and kept tiles and reuse the
 Masks: (a) all true, (b) a diagonal band of about half the scene, (c) a rectangle of nodata strictly inside the scene, (d) all
 false, (e) a single valid pixel, (f) only the left part valid, so that whole tile columns drop out.
 """
-import warnings
-
 import numpy as np
 import pytest
 import torch
 
-import tolerances
-
 pytestmark = pytest.mark.gpu
 
-from oracle import scene as oscene
-from oracle.samroad import AttrDict, SAMRoadOracle
-from oracle.synth import synth_scene, synth_state_dict
+from scene_kit import (CFG, FILL, PARITY_SCENES, SCENES, check_scene_parity, kernel_rows, make_mask, np_counts, np_kept, oracle_scene, pair,  # noqa: F401
+                       rect_grid, rect_scene)
+from scene_kit import net_for as _net_for
+from scene_kit import same_bits as _same
+from scene_kit import thresholds as _thresholds
+from scene_kit import xy_of as _xy
 
-# the configuration of tests/test_gpu_scene.py and tests/test_gpu_rect_scene.py
-CFG = dict(SAM_VERSION="vit_b", PATCH_SIZE=256, TOPONET_VERSION="normal", SAM_CKPT_PATH="",
-           ENCODER_DEPTH=2, ENCODER_GLOBAL_ATTN_INDEXES=[1],
-           INFER_BATCH_SIZE=5, SAMPLE_MARGIN=16, INFER_PATCHES_PER_EDGE=4,
-           ITSC_THRESHOLD=0.5, ROAD_THRESHOLD=0.5, TOPO_THRESHOLD=0.5,
-           ITSC_NMS_RADIUS=8, ROAD_NMS_RADIUS=16, NEIGHBOR_RADIUS=64, MAX_NEIGHBOR_QUERIES=16)
-FILL = (124, 116, 104)
-# (H, W, INFER_PATCHES_PER_EDGE, scene seed): two of tests/test_gpu_rect_scene.py's scenes — 15 tiles in 5 columns, and the odd row
-# pitch whose rows are not aligned against each other (tile origins 16, 94, 173, 251 / 16, 54, 91, 129: none divisible by 16)
-SCENES = {"384x640": (384, 640, [3, 5], 41), "401x523": (401, 523, 4, 43)}
-PARITY_SCENES = dict(SCENES, **{"523x701": (523, 701, [4, 5], 44)})      # a larger odd pitch: half of 401 x 523 is too small a graph
-KP_PERCENTILE, ROAD_PERCENTILE = 99.5, 98.0
 MASKS = ("all", "band", "hole", "none", "pixel", "left")
-
-
-def rect_scene(H, W, seed):
-    return np.ascontiguousarray(synth_scene(max(H, W), seed=seed)[:H, :W])
-
-
-def rect_grid(H, W, margin, P, per_edge):
-    """The reference's tile rule (dataset.py:56-67) per axis, restated: x outer / y inner.  per_edge: int or [n_y, n_x]."""
-    n_y, n_x = (per_edge, per_edge) if isinstance(per_edge, int) else per_edge
-    xs = [round(v) for v in np.linspace(start=margin, stop=W - (P + margin), num=n_x)]
-    ys = [round(v) for v in np.linspace(start=margin, stop=H - (P + margin), num=n_y)]
-    return [(0, (x, y), (x + P, y + P)) for x in xs for y in ys]
-
-
-def make_mask(kind, H, W):
-    """bool [H, W]."""
-    yy, xx = np.mgrid[0:H, 0:W]
-    if kind == "all":
-        return np.ones((H, W), bool)
-    if kind == "none":
-        return np.zeros((H, W), bool)
-    if kind == "band":                                    # |distance from the main diagonal| below a quarter: about half the pixels
-        return np.abs(yy / H - xx / W) < 0.29
-    if kind == "hole":                                    # nodata strictly inside: kept tiles straddle its edge
-        m = np.ones((H, W), bool)
-        m[H // 3:H // 3 + 130, W // 3:W // 3 + 150] = False
-        return m
-    if kind == "pixel":
-        m = np.zeros((H, W), bool)
-        m[H // 2 + 3, 21] = True                          # near the left edge: only the first tile column holds it
-        return m
-    if kind == "left":
-        return xx < 300
-    raise KeyError(kind)
-
-
-def np_counts(valid, infos):
-    return np.array([int(valid[y0:y1, x0:x1].sum()) for _, (x0, y0), (x1, y1) in infos], dtype=np.int64)
-
-
-def np_kept(valid, infos, P, frac=0.0):
-    c = np_counts(valid, infos)
-    return np.flatnonzero((c > 0) & (c >= frac * P * P))
-
-
-@pytest.fixture(scope="module")
-def pair():
-    from sam_road_amd import Config, SAMRoad
-    warnings.simplefilter("ignore")
-    oracle = SAMRoadOracle(AttrDict(CFG)).eval()
-    sd = synth_state_dict(oracle, 77)
-    sd["map_decoder.7.bias"] = torch.tensor([-0.3, 0.2])   # denser masks than the default -3
-    oracle.load_state_dict(sd, strict=True)
-    net = SAMRoad(Config(CFG))
-    net.load_state_dict(sd, strict=True)
-    net.eval().to("cuda")
-    return oracle, net
-
-
-def _xy(infos):
-    return torch.tensor([[p[1][0], p[1][1]] for p in infos], dtype=torch.int32).reshape(-1, 2).cuda()
-
-
-def _same(a, b):
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)      # (embeddings arrive as a permuted view)
-    assert a.dtype == b.dtype and a.shape == b.shape, (a.dtype, b.dtype, a.shape, b.shape)
-    np.testing.assert_array_equal(a.view(np.uint8) if a.dtype.kind == "f" else a, b.view(np.uint8) if b.dtype.kind == "f" else b)
-
-
-def _thresholds(kp_m, road_m):
-    return dict(ITSC_THRESHOLD=float(np.percentile(kp_m[kp_m > 0], KP_PERCENTILE)) / 255.0,
-                ROAD_THRESHOLD=float(np.percentile(road_m[road_m > 0], ROAD_PERCENTILE)) / 255.0)
-
-
-_NETS = {}
-
-
-def _net_for(P):
-    """A model object per PATCH_SIZE (the shim reads the tile size from it); one encoder block keeps the weight packing short."""
-    from sam_road_amd import Config, SAMRoad
-    if P not in _NETS:
-        warnings.simplefilter("ignore")
-        _NETS[P] = SAMRoad(Config(dict(CFG, PATCH_SIZE=P, ENCODER_DEPTH=1, ENCODER_GLOBAL_ATTN_INDEXES=[]))).eval().to("cuda")
-    return _NETS[P]
 
 
 # ---- 1. the count kernel -------------------------------------------------------------------------------------------------------
@@ -283,19 +186,11 @@ def test_all_false_mask_launches_no_encoder(pair):
     cfg = Config(dict(CFG, INFER_PATCHES_PER_EDGE=per_edge))
     infer_one_img(net, img, cfg)                         # weights packed, workspaces allocated
     ctx = _lib.Context.get(torch.cuda.current_device())
-    ctx.profile_read()                                   # reading clears the rows
-    ctx.profile_enable(True)
-    try:
+    with kernel_rows(ctx) as rows:
         out = infer_one_img(net, img, cfg, valid=np.zeros((H, W), bool))
-        torch.cuda.synchronize()
-        rows = [r for r in ctx.profile_read() if r["launches"]]
         # the single valid pixel lies in one or more tiles; with MIN_VALID_FRACTION above 1 / P^2 none is kept
         out2 = infer_one_img(net, img, Config(dict(cfg, MIN_VALID_FRACTION=0.5)), valid=make_mask("pixel", H, W))
-        torch.cuda.synchronize()
-        rows += [r for r in ctx.profile_read() if r["launches"]]
-    finally:
-        ctx.profile_enable(False)
-    names = sorted({r["name"] for r in rows})
+        names = sorted(rows())
     print("kernel classes of the two calls:", names)
     assert names == ["tile_valid_count"], names
     for o in (out, out2, list(infer_imgs(net, [img], cfg, valids=[np.zeros((H, W), np.uint8)]))[0]):
@@ -316,17 +211,11 @@ def test_profile_rows_of_a_masked_call(pair):
     cfg = Config(dict(CFG, INFER_PATCHES_PER_EDGE=per_edge))
     infer_one_img(net, img, cfg)
     ctx = _lib.Context.get(torch.cuda.current_device())
-    ctx.profile_read()
-    ctx.profile_enable(True)
-    try:
+    with kernel_rows(ctx) as rows:
         infer_one_img(net, img, cfg)
-        torch.cuda.synchronize()
-        plain = {r["name"] for r in ctx.profile_read() if r["launches"]}
+        plain = rows()
         infer_one_img(net, img, cfg, valid=make_mask("band", H, W))
-        torch.cuda.synchronize()
-        masked = {r["name"] for r in ctx.profile_read() if r["launches"]}
-    finally:
-        ctx.profile_enable(False)
+        masked = rows()
     new = {"tile_valid_count", "scene_fill_invalid", "scene_norm_valid"}
     assert not (plain & new) and "scene_normalise" in plain
     assert new <= masked and "scene_normalise" not in masked
@@ -412,26 +301,6 @@ def test_abi_rejects_bad_arguments(pair):
 
 
 # ---- against the oracle -----------------------------------------------------------------------------------------------------------
-def oracle_masked(oracle, img, valid, per_edge):
-    """The oracle's masked pass 1 from oracle.scene's public pieces: (filled scene, kept infos, feats, kp u8, road u8) with the masks
-    zeroed on nodata.  Uses nothing of sam_road_amd."""
-    H, W = valid.shape
-    P, bs = CFG["PATCH_SIZE"], CFG["INFER_BATCH_SIZE"]
-    infos = rect_grid(H, W, CFG["SAMPLE_MARGIN"], P, per_edge)
-    infos = [infos[i] for i in np_kept(valid, infos, P)]
-    filled = np.ascontiguousarray(np.where(valid[..., None], img, np.array(FILL, np.uint8)))
-    feats, scores = [], []
-    for i in range(0, len(infos), bs):
-        s, f = oracle.infer_masks_and_img_features(oscene.get_batch_img_patches(filled, infos[i:i + bs]))
-        feats.append(f)
-        scores.append(s)
-    kp_r, road_r = oscene.fuse_masks((H, W), infos, scores)
-    kp_r, road_r = kp_r.copy(), road_r.copy()
-    kp_r[~valid] = 0
-    road_r[~valid] = 0
-    return filled, infos, feats, kp_r, road_r
-
-
 # Scenes and seeds were chosen WITH THE ORACLE ALONE on the CPU (points from the oracle's own masks), so that the oracle yields well
 # over 200 edges inside the valid area — the symmetric-difference cap max(2, 2 %) is then a condition, not a measurement:
 #   (valid share, tiles kept, points, voted edges, oracle edges, share within TOPO_SCORE of the threshold)
@@ -445,36 +314,12 @@ PARITY_CASES = [("384x640", "band"), ("384x640", "hole"), ("523x701", "band"), (
 def test_masked_scene_parity_with_oracle(pair, scene, kind):
     """The checks and bounds of test_rect_scene_parity_with_oracle (tests/tolerances.py) on a masked scene."""
     from sam_road_amd import Config
-    from sam_road_amd.graph_points import extract_graph_points
     from sam_road_amd.inferencer import infer_one_img
     oracle, net = pair
     H, W, per_edge, seed = PARITY_SCENES[scene]
-    tag = f"valid_{kind}_{scene}"
     img, valid = rect_scene(H, W, seed), make_mask(kind, H, W)
-    _, infos, feats, kp_r, road_r = oracle_masked(oracle, img, valid, per_edge)
-    assert kp_r.max() > 0 and road_r.max() > 0
-    cfg = dict(CFG, INFER_PATCHES_PER_EDGE=per_edge, **_thresholds(kp_r, road_r))
-    nodes, edges, kp, road = infer_one_img(net, img, Config(cfg), valid=valid)
-    for name, got, ref in (("kp", kp, kp_r), ("road", road, road_r)):
-        d = np.abs(got.astype(int) - ref.astype(int))
-        print(f"[parity] {tag}_{name}_u8_max_diff: {d.max()} levels (bound <= 2)")
-        tolerances.check(f"{tag}_{name}_u8_within1", (d <= 1).mean(), tolerances.U8_WITHIN1, at_least=True)
-        tolerances.check(f"{tag}_{name}_u8_max_diff", d.max(), 3)                 # integers: < 3 is <= 2 levels
-        assert d.max() <= 2
-        assert not got[~valid].any() and got[valid].any()
-    pts = extract_graph_points(kp, road, Config(cfg))
-    np.testing.assert_array_equal(pts, oscene.extract_graph_points(kp, road, AttrDict(cfg)))
-    np.testing.assert_array_equal(nodes, pts[:, ::-1])
-    assert pts.shape[0] > 20 and valid[pts[:, 1], pts[:, 0]].all()
-    edges_r, sums_r, cnts_r = oscene.infer_pass2(oracle, feats, pts, infos, AttrDict(cfg))
-    got = {(int(a), int(b)) for a, b in edges.tolist()}
-    ref = {(int(a), int(b)) for a, b in edges_r.tolist()}
-    firm = {e for e, s in sums_r.items() if abs(s / cnts_r[e] - cfg["TOPO_THRESHOLD"]) > tolerances.TOPO_SCORE}
-    left_out = 1.0 - len(firm) / len(sums_r)
-    print(f"[parity] {tag}: {len(infos)} tiles kept, {pts.shape[0]} points, {len(sums_r)} voted edges, {len(ref)} oracle edges, "
-          f"firm filter leaves out {left_out:.4f}, symmetric difference {len(got ^ ref)}")
-    assert len(ref) >= 200, "the scene must give the oracle at least 200 edges for the 2 % cap to be a condition"
-    assert left_out <= 0.05
-    assert {e for e in ref if e in firm} == {e for e in got if e in firm}
-    tolerances.check(f"{tag}_edge_symdiff", len(got ^ ref), int(max(2, 0.02 * len(ref))) + 1)    # integers: < floor(b) + 1 is <= b
-    assert len(got ^ ref) <= max(2, 0.02 * len(ref))
+    ref = oracle_scene(oracle, img, per_edge, valid=valid)
+    cfg = dict(CFG, INFER_PATCHES_PER_EDGE=per_edge, **_thresholds(ref[2], ref[3]))
+    got = infer_one_img(net, img, Config(cfg), valid=valid)
+    # the scene must give the oracle at least 200 edges for the 2 % cap to be a condition
+    check_scene_parity(f"valid_{kind}_{scene}", got, ref, cfg, oracle, valid=valid, min_oracle_edges=200)

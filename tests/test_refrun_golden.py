@@ -255,27 +255,13 @@ def test_cli_plumbing_matches_reference_run(tmp_path, monkeypatch):
 
 
 def _make_fake_dataset(mg, work, dataset, g, with_ckpt=False):
-    import json
-    import yaml
-    from PIL import Image
-    os.makedirs(work)
-    size = 400 if dataset == "spacenet" else 288
+    from scene_kit import make_fake_dataset
     cfg = dict(mg.SCENE_CFG, DATASET=dataset, SAM_CKPT_PATH="", INFER_PATCHES_PER_EDGE=2,
                SAMPLE_MARGIN=16 if dataset == "cityscale" else 0, INFER_BATCH_SIZE=3)
-    with open(work / "cfg.yaml", "w") as f:
-        yaml.safe_dump(cfg, f)
     ids = g[f"{dataset}_ids"].tolist()
-    if dataset == "spacenet":
-        os.makedirs(work / "spacenet" / "RGB_1.0_meter")
-        with open(work / "spacenet" / "data_split.json", "w") as f:
-            json.dump({"train": ["x"], "validation": ["y"], "test": ids}, f)
-        pat = "spacenet/RGB_1.0_meter/{}__rgb.png"
-    else:
-        os.makedirs(work / "cityscale" / "20cities")
+    if dataset != "spacenet":
         ids = [int(i) for i in ids]
-        pat = "cityscale/20cities/region_{}_sat.png"
-    for j, i in enumerate(ids):
-        Image.fromarray(synth_scene(size, seed=100 + j)).save(work / pat.format(i))
+    make_fake_dataset(work, dataset, ids, cfg, 400 if dataset == "spacenet" else 288)
     if with_ckpt:
         net = SAMRoadOracle(AttrDict(cfg))
         torch.save({"state_dict": mg.scene_state_dict(net, mg.CLI_WSEED)}, work / "ckpt.ckpt")

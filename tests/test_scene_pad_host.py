@@ -1,9 +1,8 @@
 """SCENE_PAD (scenes padded at their borders on the device), the GPU-free part: the key and its errors, the geometry, the
 fold against numpy.pad, the kernel's addressing run item by item on the CPU, the C-ABI surface, the CLI, scene_tiles, and the orchestration
-of the scene loops through a numpy scene_pad on top of the CPU stand-in of tests/test_distributed_cpu.py.  The feature is pinned by
+of the scene loops through the numpy scene_pad of the CPU stand-in of tests/scene_kit.py.  The feature is pinned by
 COMPOSITION: a run with the key equals the existing pipeline on the numpy-padded scene, cropped."""
 import os
-import pickle
 import re
 import shutil
 import subprocess
@@ -12,31 +11,19 @@ import warnings
 import numpy as np
 import pytest
 import torch
-import torch.distributed as dist
-import torch.multiprocessing as mp
 
 from sam_road_amd import Config, _lib
 from sam_road_amd import inferencer as inf
 from sam_road_amd.graph_points import extract_graph_points
 from sam_road_amd.inferencer import edge_votes, infer_imgs, infer_one_img, scene_pad_key, scene_pad_plan, scene_tiles, votes_to_edges
 
-from test_distributed_cpu import _E2E_CFG, _E2E_SCENE, _CpuStandIn, _free_port
+from scene_kit import E2E_CFG as _E2E_CFG
+from scene_kit import E2E_SCENE as _E2E_SCENE
+from scene_kit import FILL, SceneStandIn, assert_abi_11, np_pad, run_cli, run_worlds
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-FILL = (124, 116, 104)
 MODES = ("reflect", "edge", "constant")
 GEO = dict(PATCH_SIZE=256, SAMPLE_MARGIN=16, INFER_PATCHES_PER_EDGE=2, MAX_NEIGHBOR_QUERIES=16)      # need = 288
-
-
-def np_pad(arr, pads, mode, fill=FILL):
-    """numpy.pad is the reference of the three modes; a constant colour goes channel by channel."""
-    top, bottom, left, right = pads
-    width = ((top, bottom), (left, right))
-    if mode != "constant":
-        return np.ascontiguousarray(np.pad(arr, width + ((0, 0),) * (arr.ndim - 2), mode=mode))
-    if arr.ndim == 2:
-        return np.ascontiguousarray(np.pad(arr, width, mode="constant", constant_values=arr.dtype.type(fill[0])))
-    return np.ascontiguousarray(np.stack([np.pad(arr[..., c], width, mode="constant", constant_values=fill[c]) for c in range(arr.shape[2])], -1))
 
 
 # ---- the definition on the host -----------------------------------------------------------------------------------------------------
@@ -242,12 +229,7 @@ def test_kernel_compiles_for_gfx950_without_a_gpu():
 
 # ---- C ABI surface ------------------------------------------------------------------------------------------------------------------
 def test_abi_has_the_entry_and_stays_11():
-    header = open(os.path.join(ROOT, "include", "samroad_hip.h")).read()
-    lib = _lib.load()
-    assert lib.srh_abi_version() == _lib.ABI_VERSION == int(re.search(r"#define SRH_ABI_VERSION (\d+)", header).group(1)) == 11
-    assert hasattr(lib, "srh_scene_pad") and len(_lib.SYMBOLS["srh_scene_pad"][1]) == 13
-    decl = re.search(r"\bint srh_scene_pad\(([^;]*)\);", header).group(1)
-    assert len(decl.split(",")) == 13
+    header, lib = assert_abi_11((("srh_scene_pad", 13),))
     for name, code in _lib.SRH_PAD_MODES.items():
         assert int(re.search(r"#define SRH_PAD_%s (\d+)" % name.upper(), header).group(1)) == code
     assert tuple(_lib.SRH_PAD_MODES) == MODES
@@ -256,20 +238,11 @@ def test_abi_has_the_entry_and_stays_11():
 
 
 # ---- the whole loop on the CPU stand-in ------------------------------------------------------------------------------------------------
-class _PadStandIn(_CpuStandIn):
-    """The stand-in of tests/test_distributed_cpu.py (square canvases) with SAMRoad.scene_pad from numpy.pad."""
-    pad_calls = 0
-
-    def scene_pad(self, t, pads, mode="reflect", fill=(0, 0, 0)):
-        _PadStandIn.pad_calls += 1
-        return torch.from_numpy(np_pad(t.numpy(), pads, mode, fill))
-
-
 @pytest.fixture(scope="module")
 def standin():
     warnings.simplefilter("ignore")
     torch.set_num_threads(4)
-    return _PadStandIn(dict(_E2E_CFG))
+    return SceneStandIn(dict(_E2E_CFG), ("pad",))
 
 
 def _hand_composition(net, cfg, img, pads, mode="reflect"):
@@ -340,9 +313,9 @@ def test_whole_loop_square_scene_with_a_border(standin, square_run):
     plain = infer_one_img(standin, img, Config(_E2E_CFG), device="cpu")
     assert not plain[3][:16].any() and got[3][:16].any()
     # border 0 on a scene that is large enough: the run without the key, and scene_pad is not called
-    calls = _PadStandIn.pad_calls
+    standin.calls.clear()
     _same_tuple(infer_one_img(standin, img, Config(dict(_E2E_CFG, SCENE_PAD={"border": 0, "mode": "edge"})), device="cpu"), plain)
-    assert _PadStandIn.pad_calls == calls
+    assert not [c for c in standin.calls if c[0] == "pad"]
 
 
 def test_whole_loop_scene_smaller_than_a_tile(standin):
@@ -382,39 +355,12 @@ def test_the_scene_loops_inherit_the_feature(standin, square_run):
 
 
 # ---- world 2 on gloo -------------------------------------------------------------------------------------------------------------------
-def _world_rank(world, rank, port, out):
-    warnings.simplefilter("ignore")
-    os.environ["MASTER_ADDR"] = "127.0.0.1"
-    os.environ["MASTER_PORT"] = str(port)
-    dist.init_process_group("gloo", rank=rank, world_size=world)
-    try:
-        torch.set_num_threads(2)
-        img, cfg, _ = _square_case()
-        res = infer_one_img(_PadStandIn(dict(_E2E_CFG)), img, Config(cfg), device="cpu")
-        out.put((rank, None if res is None else [np.asarray(r) for r in res]))
-    except Exception:  # pragma: no cover
-        import traceback
-        out.put((rank, "ERR " + traceback.format_exc()))
-    finally:
-        dist.destroy_process_group()
-
-
 def test_tile_sharded_world2_matches_single_process(square_run):
     """The serial tile-sharded loop on gloo at world 2: the canvases of the virtual scene are reduced in column bands, rank 0 crops.  The
     f32 sums associate differently across ranks, so the masks may differ by one level (as tests/test_distributed_cpu.py allows at world 3)."""
     one = square_run[5]
-    ctx = mp.get_context("spawn")
-    q, port = ctx.Queue(), _free_port()
-    procs = [ctx.Process(target=_world_rank, args=(2, r, port, q)) for r in range(2)]
-    for p in procs:
-        p.start()
-    got = dict(q.get(timeout=600) for _ in range(2))
-    for p in procs:
-        p.join(timeout=60)
-    for r, v in got.items():
-        assert not isinstance(v, str), v
-        assert (v is None) == (r != 0)
-    n2, e2, k2, r2 = got[0]
+    spec = dict(base="e2e", features=("pad",), overrides=dict(SCENE_PAD=24), shapes=[(_E2E_SCENE, _E2E_SCENE)], seeds=[6], mode="serial")
+    n2, e2, k2, r2 = run_worlds((2,), spec)[2][0]
     n1, e1, k1, r1 = one
     assert k2.shape == k1.shape == (_E2E_SCENE, _E2E_SCENE)
     assert np.abs(k1.astype(int) - k2.astype(int)).max() <= 1 and np.abs(r1.astype(int) - r2.astype(int)).max() <= 1
@@ -427,41 +373,32 @@ def test_tile_sharded_world2_matches_single_process(square_run):
 
 # ---- CLI -----------------------------------------------------------------------------------------------------------------------------
 def test_cli_takes_the_key_and_the_flags(tmp_path, monkeypatch, standin, square_run):
-    import yaml
     from PIL import Image
     from sam_road_amd.formats import convert_to_sat2graph_format
     img, cfg, _, _, _, with_border = square_run
-    base = dict(_E2E_CFG, DATASET="cityscale")
     monkeypatch.chdir(tmp_path)
-    for name, extra in (("plain", {}), ("pad", dict(SCENE_PAD={"border": 24})), ("edge", dict(SCENE_PAD={"border": 8, "mode": "edge"}))):
-        with open(f"{name}.yaml", "w") as f:
-            yaml.safe_dump(dict(base, **extra), f)
     Image.fromarray(img).save("rgb.png")
-    monkeypatch.setattr(inf, "_build_net", lambda config, checkpoint, device: standin)
+    plain, pad, edge = _E2E_CFG, dict(_E2E_CFG, SCENE_PAD={"border": 24}), dict(_E2E_CFG, SCENE_PAD={"border": 8, "mode": "edge"})
 
     def run(name, config, *argv):
-        inf.main(["--config", config, "--checkpoint", "none", "--device", "cpu", "--output_dir", name, "--images", "rgb.png", *argv])
-        with open(f"save/{name}/graph/rgb.p", "rb") as f:
-            g = pickle.load(f)
-        saved = yaml.safe_load(open(f"save/{name}/config.yaml"))
-        return np.array(Image.open(f"save/{name}/mask/rgb_itsc.png")), np.array(Image.open(f"save/{name}/mask/rgb_road.png")), g, saved
+        return run_cli(inf, standin, tmp_path, monkeypatch, name, config, ["rgb.png"], *argv)["rgb"]
 
     def check(got, want):
         np.testing.assert_array_equal(got[0], want[2])
         np.testing.assert_array_equal(got[1], want[3])
         assert got[2] == convert_to_sat2graph_format(want[0], want[1])
 
-    check(run("a", "pad.yaml"), with_border)                                     # the key comes from the YAML
-    got = run("b", "plain.yaml", "--scene-pad", "24")                            # the flag sets it
+    check(run("a", pad), with_border)                                     # the key comes from the YAML
+    got = run("b", plain, "--scene-pad", "24")                            # the flag sets it
     check(got, with_border)
     assert got[3]["SCENE_PAD"] == {"border": 24, "mode": "reflect"}
-    got = run("c", "edge.yaml", "--scene-pad", "24", "--scene-pad-mode", "reflect")      # both flags override the YAML
+    got = run("c", edge, "--scene-pad", "24", "--scene-pad-mode", "reflect")      # both flags override the YAML
     check(got, with_border)
-    got = run("d", "edge.yaml", "--scene-pad-mode", "constant")                  # one flag keeps the other field of the YAML
+    got = run("d", edge, "--scene-pad-mode", "constant")                  # one flag keeps the other field of the YAML
     assert got[3]["SCENE_PAD"] == {"border": [8, 8], "mode": "constant"}
     check(got, infer_one_img(standin, img, Config(dict(_E2E_CFG, SCENE_PAD={"border": 8, "mode": "constant"})), device="cpu"))
     monkeypatch.setattr(inf, "_build_net", lambda *a: (_ for _ in ()).throw(AssertionError("the model was built")))
     with pytest.raises(ValueError, match="border"):
-        inf.main(["--config", "plain.yaml", "--checkpoint", "none", "--device", "cpu", "--output_dir", "e", "--images", "rgb.png", "--scene-pad", "-4"])
+        inf.main(["--config", "b.yaml", "--checkpoint", "none", "--device", "cpu", "--output_dir", "e", "--images", "rgb.png", "--scene-pad", "-4"])
     with pytest.raises(SystemExit):
-        inf.main(["--config", "plain.yaml", "--checkpoint", "none", "--device", "cpu", "--output_dir", "e", "--images", "rgb.png", "--scene-pad-mode", "wrap"])
+        inf.main(["--config", "b.yaml", "--checkpoint", "none", "--device", "cpu", "--output_dir", "e", "--images", "rgb.png", "--scene-pad-mode", "wrap"])

@@ -1,7 +1,5 @@
 """Host side of MAX_NEIGHBOR_QUERIES (K) != 16: pass-2 query building, packing and vote sums at other K, the tile-sharded merge at
 K = 8, and the inferencer's up-front check of K (1..64, ABI 10).  CPU only."""
-import multiprocessing as mp
-
 import numpy as np
 import pytest
 
@@ -75,22 +73,10 @@ def test_pack_ragged_and_vote_sums_at_k(K):
 def test_tile_sharded_merge_at_k8():
     """infer_one_img split over 2 gloo ranks (CPU oracle stand-in for the model) == one process, at MAX_NEIGHBOR_QUERIES = 8, on
     disjoint tiles (every canvas pixel has one addend, so the results are identical)."""
-    import test_distributed_cpu as tdc
-    ctx = mp.get_context("spawn")
+    from scene_kit import run_worlds
     overrides = dict(SAMPLE_MARGIN=0, INFER_PATCHES_PER_EDGE=2, MAX_NEIGHBOR_QUERIES=8)
-    results = {}
-    for world in (1, 2):
-        port = tdc._free_port()
-        q = ctx.Queue()
-        procs = [ctx.Process(target=tdc._e2e_run, args=(world, r, port, q, 512, overrides)) for r in range(world)]
-        for p in procs:
-            p.start()
-        got = dict(q.get(timeout=600) for _ in range(world))
-        for p in procs:
-            p.join(timeout=60)
-        for v in got.values():
-            assert not isinstance(v, str), v
-        results[world] = got[0]
+    res = run_worlds((1, 2), dict(base="e2e", overrides=overrides, shapes=[(512, 512)], seeds=[6], mode="serial"))
+    results = {1: res[1][0], 2: res[2][0]}
     assert results[1][0].shape[0] > 30 and results[1][1].shape[0] > 50
     for a, b in zip(results[1], results[2]):
         np.testing.assert_array_equal(a, b)

@@ -1,8 +1,7 @@
 """TTA (test-time augmentation over the 8 tile orientations), the GPU-free part: the plan and its errors, the host
 orientation helpers against the numpy table, the C-ABI surface, the CLI, scene_tiles, and the orchestration of the three scene loops
-through a numpy stand-in of scene_pass1(tta=) on top of the CPU stand-in of tests/test_fuse_window_host.py."""
+through scene_pass1(tta=) of the CPU stand-in of tests/scene_kit.py (features "valid", "window", "tta")."""
 import os
-import pickle
 import re
 import shutil
 import subprocess
@@ -16,24 +15,11 @@ from sam_road_amd import Config, _lib
 from sam_road_amd import inferencer as inf
 from sam_road_amd.inferencer import infer_imgs, infer_one_img, orient_tile, tta_plan, unorient_tile
 
-from test_fuse_window_host import _WindowStandIn
-from test_rect_scene_host import _CFG, _rect_scene
-from test_valid_mask_host import _same_tuple, make_mask
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NAMES = ("id", "flip_h", "flip_v", "rot180", "transpose", "rot90", "rot270", "anti_transpose")
-
-# the table of the issue / DESIGN.md §6f, restated: these expressions ARE the definition
-TABLE = {
-    "id": lambda T: T,
-    "flip_h": lambda T: T[:, ::-1],
-    "flip_v": lambda T: T[::-1, :],
-    "rot180": lambda T: T[::-1, ::-1],
-    "transpose": lambda T: T.swapaxes(0, 1),
-    "rot90": lambda T: np.rot90(T, 1, axes=(0, 1)),
-    "rot270": lambda T: np.rot90(T, 3, axes=(0, 1)),
-    "anti_transpose": lambda T: T[::-1, ::-1].swapaxes(0, 1),
-}
+from scene_kit import HOST_CFG as _CFG
+from scene_kit import NAMES, SceneStandIn, assert_abi_11, make_mask, run_cli
+from scene_kit import ORIENT as TABLE      # the table of DESIGN.md §6f, restated: those expressions ARE the definition
+from scene_kit import rect_scene as _rect_scene
+from scene_kit import same_tuple as _same_tuple
 
 
 # ---- the plan ---------------------------------------------------------------------------------------------------------------------
@@ -130,13 +116,7 @@ def test_scene_tiles_lists_the_orientations():
 
 # ---- C ABI surface ----------------------------------------------------------------------------------------------------------------
 def test_abi_has_the_tta_entries_and_stays_11():
-    header = open(os.path.join(ROOT, "include", "samroad_hip.h")).read()
-    lib = _lib.load()
-    assert lib.srh_abi_version() == _lib.ABI_VERSION == int(re.search(r"#define SRH_ABI_VERSION (\d+)", header).group(1)) == 11
-    for name, n_args in (("srh_scene_pass1_tta_hw", 15), ("srh_op_patch_im2col", 10), ("srh_op_scores_unorient", 7)):
-        assert hasattr(lib, name) and len(_lib.SYMBOLS[name][1]) == n_args
-        decl = re.search(r"\bint %s\(([^;]*)\);" % name, header).group(1)
-        assert len(decl.split(",")) == n_args
+    assert_abi_11((("srh_scene_pass1_tta_hw", 15), ("srh_op_patch_im2col", 10), ("srh_op_scores_unorient", 7)))
     assert len(_lib.SYMBOLS["srh_scene_pass1_tta_hw"][1]) == len(_lib.SYMBOLS["srh_scene_pass1_window_hw"][1]) + 2
 
 
@@ -159,43 +139,11 @@ def test_tta_kernels_compile_for_gfx950_without_a_gpu():
 
 
 # ---- the pipeline on a stand-in ---------------------------------------------------------------------------------------------------
-class _TtaStandIn(_WindowStandIn):
-    """_WindowStandIn + tta= on scene_pass1 in CPU torch, the rule of DESIGN.md §6f: for every orientation the whole list, the crop
-    oriented, the scores brought back, then the (weighted) add.  scene_normalise is inherited: TTA only hands it the k-fold list.
-    Without tta the inherited scene_pass1 runs — it does not know the argument, so passing it for ['id'] is an error."""
-
-    def scene_pass1(self, scene, tile_xy, bs, window=None, tta=None):
-        if tta is None:
-            return super().scene_pass1(scene, tile_xy, bs) if window is None else super().scene_pass1(scene, tile_xy, bs, window=window)
-        self.calls.append(("pass1_tta", int(tile_xy.shape[0]), tuple(tta), window is not None))
-        assert tta[0] == 0 and len(set(tta)) == len(tta) > 1
-        (H, W), P = scene.shape[:2], self.P
-        w2 = torch.ones((P, P)) if window is None else window[:, None] * window[None, :]
-        kp, road = torch.zeros((H, W)), torch.zeros((H, W))
-        embs = []
-        for code in tta:
-            name = NAMES[code]
-            for x0, y0 in tile_xy.tolist():
-                crop = np.ascontiguousarray(orient_tile(scene[y0:y0 + P, x0:x0 + P].numpy(), name))
-                s, e = self.oracle.infer_masks_and_img_features(torch.from_numpy(crop).float()[None])
-                s = torch.from_numpy(np.ascontiguousarray(unorient_tile(s[0].detach().numpy(), name)))
-                kp[y0:y0 + P, x0:x0 + P] += w2 * s[:, :, 0]
-                road[y0:y0 + P, x0:x0 + P] += w2 * s[:, :, 1]
-                if code == 0:
-                    embs.append(e)
-        emb = torch.cat(embs) if embs else torch.zeros((0, 256, P // 16, P // 16))
-        return kp, road, emb
-
-    def scene_normalise(self, kp, road, tile_xy, valid=None, window=None):
-        self.calls.append(("normalise", int(tile_xy.shape[0])))
-        return super().scene_normalise(kp, road, tile_xy, valid=valid, window=window)
-
-
 @pytest.fixture(scope="module")
 def standin():
     warnings.simplefilter("ignore")
     cfg = dict(_CFG, INFER_PATCHES_PER_EDGE=[3, 5])
-    return _TtaStandIn(cfg), cfg
+    return SceneStandIn(cfg, ("valid", "window", "tta")), cfg
 
 
 def _mean_levels(net, img, infos, names):
@@ -297,24 +245,16 @@ def test_the_four_entry_paths_make_the_same_calls(standin):
 
 # ---- CLI --------------------------------------------------------------------------------------------------------------------------
 def test_cli_takes_the_key_and_the_flag(tmp_path, monkeypatch, standin):
-    import yaml
     from PIL import Image
     from sam_road_amd.formats import convert_to_sat2graph_format
     net, cfg = standin
     img = _rect_scene(384, 640, 60)
     monkeypatch.chdir(tmp_path)
-    for name, extra in (("plain", {}), ("two", dict(TTA=["id", "flip_v"]))):
-        with open(f"{name}.yaml", "w") as f:
-            yaml.safe_dump(dict(cfg, DATASET="cityscale", **extra), f)
     Image.fromarray(img).save("rgb.png")
-    monkeypatch.setattr(inf, "_build_net", lambda config, checkpoint, device: net)
+    plain, two = cfg, dict(cfg, TTA=["id", "flip_v"])
 
     def run(name, config, *argv):
-        inf.main(["--config", config, "--checkpoint", "none", "--device", "cpu", "--output_dir", name, "--images", "rgb.png", *argv])
-        with open(f"save/{name}/graph/rgb.p", "rb") as f:
-            g = pickle.load(f)
-        saved = yaml.safe_load(open(f"save/{name}/config.yaml"))
-        return np.array(Image.open(f"save/{name}/mask/rgb_itsc.png")), np.array(Image.open(f"save/{name}/mask/rgb_road.png")), g, saved
+        return run_cli(inf, net, tmp_path, monkeypatch, name, config, ["rgb.png"], *argv)["rgb"]
 
     want = {k: infer_one_img(net, img, Config(dict(cfg, **({} if k == "plain" else dict(TTA=k.split(","))))), device="cpu")
             for k in ("plain", "id,flip_v", "id,rot270")}
@@ -325,13 +265,13 @@ def test_cli_takes_the_key_and_the_flag(tmp_path, monkeypatch, standin):
         np.testing.assert_array_equal(got[1], want[key][3])
         assert got[2] == convert_to_sat2graph_format(want[key][0], want[key][1])
 
-    check(run("a", "plain.yaml"), "plain")
-    check(run("b", "two.yaml"), "id,flip_v")                                    # the key comes from the YAML
-    got = run("c", "plain.yaml", "--tta", "id,rot270")                          # the flag sets it
+    check(run("a", plain), "plain")
+    check(run("b", two), "id,flip_v")                                    # the key comes from the YAML
+    got = run("c", plain, "--tta", "id,rot270")                          # the flag sets it
     check(got, "id,rot270")
     assert got[3]["TTA"] == ["id", "rot270"]
-    check(run("d", "two.yaml", "--tta", "id"), "plain")                         # and overrides the YAML
+    check(run("d", two, "--tta", "id"), "plain")                         # and overrides the YAML
     monkeypatch.setattr(inf, "_build_net", lambda *a: (_ for _ in ()).throw(AssertionError("the model was built")))
     for bad, what in (("flip_h,id", "first"), ("id,spin", "one of"), ("id,id", "twice")):
         with pytest.raises(ValueError, match=what):
-            inf.main(["--config", "plain.yaml", "--checkpoint", "none", "--device", "cpu", "--output_dir", "e", "--images", "rgb.png", "--tta", bad])
+            inf.main(["--config", "a.yaml", "--checkpoint", "none", "--device", "cpu", "--output_dir", "e", "--images", "rgb.png", "--tta", bad])

@@ -1,87 +1,20 @@
 """Scenes with a per-pixel validity mask (nodata), the GPU-free part: the selection rule and the argument errors against numpy, the
 C-ABI surface, the tile-sharded loops on gloo / CPU, and the CLI plumbing — all through a numpy stand-in of the three shim methods
-(scene_tile_valid, scene_fill_invalid, scene_normalise(valid=)) on top of the CPU stand-in model of tests/test_rect_scene_host.py."""
-import os
-import pickle
-import re
+(scene_tile_valid, scene_fill_invalid, scene_normalise(valid=)) of the CPU stand-in model of tests/scene_kit.py (feature "valid")."""
 import warnings
 
 import numpy as np
 import pytest
 import torch
-import torch.distributed as dist
-import torch.multiprocessing as mp
 
 from sam_road_amd import Config, _lib
-from sam_road_amd import distributed as D
 from sam_road_amd.inferencer import infer_imgs, infer_one_img, scene_tiles, select_tiles
 from sam_road_amd.tiling import get_patch_info_hw
 
-from test_rect_scene_host import _CFG, _CpuStandIn, _free_port, _rect_scene
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-FILL = (124, 116, 104)
-
-
-class _MaskStandIn(_CpuStandIn):
-    """_CpuStandIn (H x W canvases) + the three mask methods of SAMRoad in numpy / CPU torch, counting its calls."""
-
-    def __init__(self, cfg):
-        super().__init__(cfg)
-        self.calls = []
-
-    def scene_pass1(self, scene, tile_xy, bs):
-        self.calls.append(("pass1", int(tile_xy.shape[0])))
-        return super().scene_pass1(scene, tile_xy, bs)
-
-    def scene_tile_valid(self, valid, tile_xy):
-        self.calls.append(("tile_valid", int(tile_xy.shape[0])))
-        v = valid.numpy() != 0
-        return torch.tensor([int(v[y0:y0 + self.P, x0:x0 + self.P].sum()) for x0, y0 in tile_xy.tolist()], dtype=torch.int32)
-
-    def scene_fill_invalid(self, scene, valid, fill):
-        self.calls.append(("fill", tuple(fill)))
-        scene[valid == 0] = torch.tensor(fill, dtype=torch.uint8)
-        return scene
-
-    def scene_normalise(self, kp, road, tile_xy, valid=None):
-        kp_u8, road_u8 = super().scene_normalise(kp, road, tile_xy)
-        if valid is not None:
-            kp_u8[valid == 0] = 0
-            road_u8[valid == 0] = 0
-        return kp_u8, road_u8
-
-
-class _CountOnly(torch.nn.Module):
-    """A model object that can count and nothing else: whatever else is called raises AttributeError."""
-
-    def __init__(self, P):
-        super().__init__()
-        self.P, self.w = P, torch.nn.Parameter(torch.zeros(1))
-
-    scene_tile_valid = _MaskStandIn.scene_tile_valid
-    calls = []
-
-
-def make_mask(kind, H, W):
-    yy, xx = np.mgrid[0:H, 0:W]
-    if kind == "all":
-        return np.ones((H, W), bool)
-    if kind == "none":
-        return np.zeros((H, W), bool)
-    if kind == "band":
-        return np.abs(yy / H - xx / W) < 0.29
-    if kind == "hole":
-        m = np.ones((H, W), bool)
-        m[H // 3:H // 3 + 130, W // 3:W // 3 + 150] = False
-        return m
-    if kind == "pixel":
-        m = np.zeros((H, W), bool)
-        m[H // 2 + 3, W // 2 + 5] = True
-        return m
-    if kind == "left":
-        return xx < 300
-    raise KeyError(kind)
+from scene_kit import HOST_CFG as _CFG
+from scene_kit import SceneStandIn, _CountOnly, assert_abi_11, compare_worlds, make_mask, run_cli, run_worlds
+from scene_kit import rect_scene as _rect_scene
+from scene_kit import same_tuple as _same_tuple
 
 
 # ---- selection rule ---------------------------------------------------------------------------------------------------------------
@@ -94,7 +27,7 @@ def test_selection_rule_against_numpy(H, W, per_edge, P):
         infos = get_patch_info_hw(0, H, W, 16, P, per_edge)
         assert scene_tiles((H, W), Config(cfg)) == infos == scene_tiles((H, W, 3), Config(cfg))
         dropped_some = False
-        for kind in ("all", "band", "hole", "none", "pixel", "left"):
+        for kind in ("all", "band", "hole", "none", "pixel_mid", "left"):
             m = make_mask(kind, H, W)
             counts = np.array([m[y0:y1, x0:x1].sum() for _, (x0, y0), (x1, y1) in infos])
             for frac in (None, 0, 0.25, 0.5, 1.0, 1):
@@ -108,7 +41,7 @@ def test_selection_rule_against_numpy(H, W, per_edge, P):
                     assert want == infos
                 if kind == "none":
                     assert want == []
-                if kind == "pixel":
+                if kind == "pixel_mid":
                     assert len(want) == (0 if f > 0 else int((counts > 0).sum())) and (f > 0 or len(want) >= 1)
         assert dropped_some
     np.testing.assert_array_equal(select_tiles([0, 1, 16384, 4096, 4095], 128, 0.25), [2, 3])
@@ -161,13 +94,7 @@ def test_arguments_are_refused_before_the_model_is_touched():
 def standin():
     warnings.simplefilter("ignore")
     cfg = dict(_CFG, SAMPLE_MARGIN=0, INFER_PATCHES_PER_EDGE=[3, 5])
-    return _MaskStandIn(cfg), cfg
-
-
-def _same_tuple(a, b):
-    for x, y in zip(a, b):
-        assert np.asarray(x).dtype == np.asarray(y).dtype
-        np.testing.assert_array_equal(np.asarray(x), np.asarray(y))
+    return SceneStandIn(cfg, ("valid",)), cfg
 
 
 def test_masked_scene_on_the_standin(standin):
@@ -180,7 +107,7 @@ def test_masked_scene_on_the_standin(standin):
     net.calls.clear()
     plain = infer_one_img(net, img, Config(cfg), device="cpu")
     assert net.calls == [("pass1", 15)]
-    base = _CpuStandIn(cfg)                                   # the stand-in of the existing tests: scene_normalise has no `valid`
+    base = SceneStandIn(cfg)                                  # the stand-in without the feature: scene_normalise has no `valid`
     _same_tuple(infer_one_img(base, img, Config(cfg), device="cpu"), plain)
     _same_tuple(infer_one_img(net, img, Config(cfg), device="cpu", valid=np.ones((H, W), bool)), plain)
     band = make_mask("band", H, W)
@@ -214,96 +141,14 @@ def test_masked_scene_on_the_standin(standin):
 
 # ---- C ABI surface ------------------------------------------------------------------------------------------------------------------
 def test_abi_symbol_tables_agree_and_number_is_11():
-    header = open(os.path.join(ROOT, "include", "samroad_hip.h")).read()
-    declared = set(re.findall(r"^[A-Za-z_][\w \*]*?\b(srh_\w+)\(", header, flags=re.M))
-    assert declared == set(_lib.SYMBOLS), (declared ^ set(_lib.SYMBOLS))
-    lib = _lib.load()
-    assert lib.srh_abi_version() == _lib.ABI_VERSION == int(re.search(r"#define SRH_ABI_VERSION (\d+)", header).group(1)) == 11
-    for name, n_args in (("srh_scene_tile_valid", 9), ("srh_scene_fill_invalid", 9), ("srh_scene_normalise_valid_hw", 12)):
-        assert re.search(r"\bint %s\(" % name, header)
-        assert hasattr(lib, name) and len(_lib.SYMBOLS[name][1]) == n_args
-        decl = re.search(r"\bint %s\(([^;]*)\);" % name, header).group(1)
-        assert len(decl.split(",")) == n_args
+    assert_abi_11((("srh_scene_tile_valid", 9), ("srh_scene_fill_invalid", 9), ("srh_scene_normalise_valid_hw", 12)))
     assert len(_lib.SYMBOLS["srh_scene_normalise_valid_hw"][1]) == len(_lib.SYMBOLS["srh_scene_normalise_hw"][1]) + 1
 
 
 # ---- tile-sharded loops on gloo -------------------------------------------------------------------------------------------------------
-def _rank(world, rank, port, out, shapes, kinds, overrides, mode):
-    warnings.simplefilter("ignore")
-    if world > 1:
-        os.environ["MASTER_ADDR"] = "127.0.0.1"
-        os.environ["MASTER_PORT"] = str(port)
-        dist.init_process_group("gloo", rank=rank, world_size=world)
-    try:
-        torch.set_num_threads(2)
-        D._CHECK_BANDS[0] = True
-        cfg = dict(_CFG, **(overrides or {}))
-        net = _MaskStandIn(cfg)
-        imgs = [_rect_scene(h, w, 60 + i) for i, (h, w) in enumerate(shapes)]
-        valids = [None if k is None else make_mask(k, h, w) for k, (h, w) in zip(kinds, shapes)]
-        serial = [infer_one_img(net, im, Config(cfg), device="cpu", valid=v) for im, v in zip(imgs, valids)]
-        if mode == "pipelined" and world > 1:
-            got = list(infer_imgs(net, iter(imgs), Config(dict(cfg, TILE_SHARD_PIPELINE=True)), device="cpu", valids=valids))
-            for a, b in zip(got, serial):             # same world size: same summation orders, so the two loops agree exactly
-                assert (a is None) == (b is None) == (rank != 0)
-                if a is not None:
-                    _same_tuple(a, b)
-            via_loop = list(infer_imgs(net, iter(imgs), Config(cfg), device="cpu", valids=iter(valids)))    # the serial tile-sharded loop
-            for a, b in zip(via_loop, serial):
-                assert (a is None) == (b is None)
-                if a is not None:
-                    _same_tuple(a, b)
-        else:
-            got = serial
-        out.put((rank, [None if r is None else [np.asarray(a) for a in r] for r in got]))
-    except Exception:  # pragma: no cover
-        import traceback
-        out.put((rank, "ERR " + traceback.format_exc()))
-    finally:
-        if world > 1:
-            dist.destroy_process_group()
-
-
-def _run_worlds(worlds, shapes, kinds, overrides, mode):
-    ctx = mp.get_context("spawn")
-    results = {}
-    for world in worlds:
-        port, q = _free_port(), ctx.Queue()
-        procs = [ctx.Process(target=_rank, args=(world, r, port, q, shapes, kinds, overrides, mode)) for r in range(world)]
-        for p in procs:
-            p.start()
-        got = dict(q.get(timeout=900) for _ in range(world))
-        for p in procs:
-            p.join(timeout=60)
-        for r, v in got.items():
-            assert not isinstance(v, str), v
-            assert all((x is None) == (r != 0) for x in v)                     # only rank 0 returns the graphs
-        results[world] = got[0]
-    return results
-
-
-def _compare(one, many, shapes, kinds, must_be_identical):
-    """The identity conditions of tests/test_rect_scene_host.py: a disjoint tiling gives every canvas pixel one addend, so the
-    multi-rank result is IDENTICAL; with overlapping tiles the u8 masks may differ by one level on a few pixels."""
-    assert len(one) == len(many) == len(shapes)
-    for (n1, e1, k1, r1), (nw, ew, kw, rw), hw, kind in zip(one, many, shapes, kinds):
-        assert k1.shape == r1.shape == kw.shape == rw.shape == tuple(hw)
-        valid = make_mask(kind, *hw) if kind is not None else np.ones(hw, bool)
-        if kind == "none":
-            assert n1.shape == nw.shape == (0, 2) and e1.shape == ew.shape == (0, 2) and not k1.any() and not kw.any() and not rw.any()
-            continue
-        assert n1.shape[0] > 30 and e1.shape[0] > 100
-        assert valid[n1[:, 0], n1[:, 1]].all() and valid[nw[:, 0], nw[:, 1]].all()
-        assert not kw[~valid].any() and not rw[~valid].any()
-        assert np.abs(k1.astype(int) - kw.astype(int)).max() <= 1 and np.abs(r1.astype(int) - rw.astype(int)).max() <= 1
-        same_masks = np.array_equal(k1, kw) and np.array_equal(r1, rw)
-        print(hw, kind, "masks identical to single process:", same_masks, "| nodes", n1.shape[0], "edges", e1.shape[0])
-        assert same_masks or not must_be_identical
-        if same_masks:
-            np.testing.assert_array_equal(n1, nw)
-            np.testing.assert_array_equal(e1, ew)
-        else:
-            assert abs(n1.shape[0] - nw.shape[0]) <= 2
+def _spec(shapes, kinds, overrides, mode):
+    """The masked stand-in; in the pipelined runs the serial tile-sharded loop of infer_imgs is checked against infer_one_img too."""
+    return dict(features=("valid",), shapes=shapes, kinds=kinds, overrides=overrides, mode=mode, checks=("serial_loop",))
 
 
 @pytest.mark.parametrize("overrides,must_be_identical", [
@@ -312,8 +157,8 @@ def _compare(one, many, shapes, kinds, must_be_identical):
 ])
 def test_serial_tile_sharded_world3_masked(overrides, must_be_identical):
     shapes, kinds = [(384, 640), (384, 640), (384, 640)], ["band", "none", "left"]
-    res = _run_worlds((1, 3), shapes, kinds, overrides, "serial")
-    _compare(res[1], res[3], shapes, kinds, must_be_identical)
+    res = run_worlds((1, 3), _spec(shapes, kinds, overrides, "serial"))
+    compare_worlds(res[1], res[3], shapes, kinds, must_be_identical)
 
 
 def test_pipelined_tile_sharded_world2_masked():
@@ -321,13 +166,12 @@ def test_pipelined_tile_sharded_world2_masked():
     tile-sharded loop of the same world exactly (checked inside the ranks), and to the single-process run."""
     shapes = [(384, 640), (640, 384), (401, 523), (384, 640), (448, 448)]
     kinds = ["band", None, "none", "left", "hole"]
-    res = _run_worlds((1, 2), shapes, kinds, None, "pipelined")
-    _compare(res[1], res[2], shapes, kinds, False)
+    res = run_worlds((1, 2), _spec(shapes, kinds, None, "pipelined"))
+    compare_worlds(res[1], res[2], shapes, kinds, False)
 
 
 # ---- CLI ----------------------------------------------------------------------------------------------------------------------------
 def test_cli_valid_masks_and_rgba(tmp_path, monkeypatch, standin):
-    import yaml
     from PIL import Image
     import sam_road_amd.inferencer as inf
     net, cfg = standin
@@ -335,14 +179,11 @@ def test_cli_valid_masks_and_rgba(tmp_path, monkeypatch, standin):
     img = _rect_scene(H, W, 60)
     band, left = make_mask("band", H, W), make_mask("left", H, W)
     monkeypatch.chdir(tmp_path)
-    with open("cfg.yaml", "w") as f:
-        yaml.safe_dump(dict(cfg, DATASET="cityscale"), f)
     Image.fromarray(img).save("rgb.png")
     np.save("scene.npy", img)
     Image.fromarray(np.dstack([img, band.astype(np.uint8) * 255])).save("rgba.png")
     Image.fromarray(left.astype(np.uint8) * 255).save("left.png")
     np.save("band.npy", band)
-    monkeypatch.setattr(inf, "_build_net", lambda config, checkpoint, device: net)
     np.testing.assert_array_equal(inf.read_rgb_img("rgba.png"), img)             # read_rgb_img still drops alpha
     np.testing.assert_array_equal(inf.read_alpha_valid("rgba.png"), band)
     assert inf.read_alpha_valid("rgb.png") is None
@@ -353,38 +194,30 @@ def test_cli_valid_masks_and_rgba(tmp_path, monkeypatch, standin):
     assert inf.has_alpha("pal.png") and inf.has_alpha("rgba.png") and not inf.has_alpha("rgb.png") and not inf.has_alpha("scene.npy")
     np.testing.assert_array_equal(inf.read_alpha_valid("pal.png"), left)
 
-    def run(name, *argv):
-        inf.main(["--config", "cfg.yaml", "--checkpoint", "none", "--device", "cpu", "--output_dir", name, *argv])
-        out = {}
-        for stem in [os.path.splitext(os.path.basename(p))[0] for p in argv[argv.index("--images") + 1:] if not p.startswith("--")
-                     and p.endswith((".png", ".npy")) and "left" not in p and "band" not in p]:
-            road = np.array(Image.open(f"save/{name}/mask/{stem}_road.png"))
-            itsc = np.array(Image.open(f"save/{name}/mask/{stem}_itsc.png"))
-            with open(f"save/{name}/graph/{stem}.p", "rb") as f:
-                out[stem] = (itsc, road, pickle.load(f))
-        return out
+    def run(name, images, *argv):
+        return run_cli(inf, net, tmp_path, monkeypatch, name, cfg, images, *argv)
 
     want = {k: infer_one_img(net, img, Config(cfg), device="cpu", valid=v) for k, v in (("plain", None), ("band", band), ("left", left))}
     from sam_road_amd.formats import convert_to_sat2graph_format
     graph = lambda r: convert_to_sat2graph_format(r[0], r[1])
 
     def check(got, key):
-        itsc, road, g = got
+        itsc, road, g, _ = got
         np.testing.assert_array_equal(itsc, want[key][2])
         np.testing.assert_array_equal(road, want[key][3])
         assert g == graph(want[key])
 
     # explicit mask files, parallel to --images; '-' = no mask
-    out = run("a", "--valid-masks", "left.png", "band.npy", "-", "--images", "rgb.png", "scene.npy", "rgba.png")
+    out = run("a", ["rgb.png", "scene.npy", "rgba.png"], "--valid-masks", "left.png", "band.npy", "-")
     check(out["rgb"], "left")
     check(out["scene"], "band")
     check(out["rgba"], "plain")                               # mask files were given: the alpha channel is not consulted
     # no mask files: an RGBA file uses alpha > 0, an RGB file has no mask
-    out = run("b", "--images", "rgba.png", "rgb.png")
+    out = run("b", ["rgba.png", "rgb.png"])
     check(out["rgba"], "band")
     check(out["rgb"], "plain")
     assert not out["rgba"][0][~band].any() and not out["rgba"][1][~band].any()
     with pytest.raises(SystemExit):
-        inf.main(["--config", "cfg.yaml", "--checkpoint", "none", "--device", "cpu", "--output_dir", "c", "--images", "rgb.png", "--valid-masks"])
+        inf.main(["--config", "a.yaml", "--checkpoint", "none", "--device", "cpu", "--output_dir", "c", "--images", "rgb.png", "--valid-masks"])
     with pytest.raises(SystemExit):
-        inf.main(["--config", "cfg.yaml", "--checkpoint", "none", "--device", "cpu", "--output_dir", "d", "--valid-masks", "left.png"])
+        inf.main(["--config", "a.yaml", "--checkpoint", "none", "--device", "cpu", "--output_dir", "d", "--valid-masks", "left.png"])
