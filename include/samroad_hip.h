@@ -251,6 +251,31 @@ int srh_op_scores_unorient(srh_ctx* ctx, const float* scores_in, int n, int P, i
 int srh_scene_pad(srh_ctx* ctx, const uint8_t* src, int H, int W, int C, int top, int bottom, int left, int right, int mode,
                   const int32_t* fill_rgb, uint8_t* dst, void* stream);
 
+/* Scene groups (config key SCENE_GROUP; an extension): the tiles of several small scenes run as one pass 1 over a vertical
+ * stack of their (padded) images.  Two additive entries; the ABI number stays 11 because nothing existing changes, and a run without
+ * the key calls neither.
+ *
+ * The table has one row of eight int64 per scene k: { off, H, W, top, left, Hv, Wv, row0 }.  H x W is the real scene, Hv x Wv >= (H + top)
+ * x (W + left) its virtual (padded) size, row0 the stack row it starts at: row0[0] = 0, row0[k + 1] = row0[k] + Hv[k], sum Hv = Ha, every
+ * Wv <= Wa.  off is the byte offset of the scene's block in the ragged buffer of THAT call.  The table is passed twice: table_host is read
+ * and validated by the entry before anything is launched, table_dev — the same n * 8 values on the device, uploaded by the caller — is
+ * what the kernel reads.  The entry cannot compare the two; a table_dev that differs from table_host is undefined behaviour.
+ *
+ * srh_scene_group_pack: dst u8 [Ha, Wa, C] on the device, every byte written exactly once and nothing else: stack pixel (row0 + Y, X)
+ *   with X < Wv holds pixel (f(Y - top, H), f(X - left, W)) of the scene's block src + off (u8 [H, W, C], dense rows, any byte address) by
+ *   the rule and the modes of srh_scene_pad; columns X >= Wv hold 0.  src_bytes: the size of the ragged buffer; every block must lie
+ *   inside it (blocks may repeat or leave gaps).  fill_rgb as for srh_scene_pad.
+ * srh_scene_group_crop: for every scene the window [row0 + top : row0 + top + H, left : left + W] of the two u8 [Ha, Wa] masks kp and
+ *   road -> the dense H x W blocks out_kp + off and out_road + off.  The blocks must tile [0, out_bytes) in table order with no gap
+ *   (off[0] = 0, off[k + 1] = off[k] + H W, the last one ending at out_bytes), so every output byte is written exactly once.
+ * Both: SRH_ERR_BAD_ARG, and nothing is launched, unless the pointers are non-null, n >= 1, C is 1 or 3, mode one of the three, every
+ *   row of table_host is consistent as above with H, W >= 1 and pads >= 0, the blocks lie inside src_bytes / tile out_bytes, and Ha * Wa
+ *   <= 2^31 - 1.  Neither touches a workspace of the context.  Profiler rows: scene_group_pack, scene_group_crop. */
+int srh_scene_group_pack(srh_ctx* ctx, const uint8_t* src, int64_t src_bytes, const int64_t* table_host, const int64_t* table_dev, int n,
+                         int C, int Ha, int Wa, int mode, const int32_t* fill_rgb, uint8_t* dst, void* stream);
+int srh_scene_group_crop(srh_ctx* ctx, const uint8_t* kp, const uint8_t* road, int Ha, int Wa, const int64_t* table_host,
+                         const int64_t* table_dev, int n, uint8_t* out_kp, uint8_t* out_road, int64_t out_bytes, void* stream);
+
 /* op level (used by the parity tests to localise a failure; same kernels as above) ----------------- */
 
 /* out = act(A[M,K] W[N,K]^T + bias) (+resid); A,W fp16; N%128==0, K%64==0. act: 0/1 GELU/2 ReLU. */

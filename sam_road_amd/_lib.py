@@ -73,6 +73,8 @@ SYMBOLS = {
     "srh_op_scene_fuse_window": (_I, [_P, _P, _I, _I, _P, _P, _P, _P, _I, _I, _P]),
     "srh_scene_pass1_tta_hw": (_I, [_P, _P, _P, _I, _I, _P, _I, _I, _P, _I, _P, _P, _P, _P, _P]),
     "srh_scene_pad": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P]),
+    "srh_scene_group_pack": (_I, [_P, _P, C.c_int64, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P]),
+    "srh_scene_group_crop": (_I, [_P, _P, _P, _I, _I, _P, _P, _I, _P, _P, C.c_int64, _P]),
     "srh_op_patch_im2col": (_I, [_P, _P, _I, _I, _P, _I, _I, _I, _P, _P]),
     "srh_op_scores_unorient": (_I, [_P, _P, _I, _I, _I, _P, _P]),
     "srh_op_gemm": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P]),

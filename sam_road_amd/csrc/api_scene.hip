@@ -182,3 +182,36 @@ extern "C" int srh_scene_pad(srh_ctx* c, const uint8_t* src, int H, int W, int C
     TRYK(c, "scene_pad", 0, ((double)H * W + (double)Hv * Wv) * C, s, launch_scene_pad(p, s));
     return 0;
 }
+
+// ---- scene level, groups of small scenes (kernels in scene_group.hip, behaviour in DESIGN.md §6h) ---------------------------------------
+extern "C" int srh_scene_group_pack(srh_ctx* c, const uint8_t* src, int64_t src_bytes, const int64_t* table_host, const int64_t* table_dev,
+                                    int n, int C, int Ha, int Wa, int mode, const int32_t* fill_rgb, uint8_t* dst, void* stream) {
+    if (!c || !src || !table_host || !table_dev || !dst || (mode == SRH_PAD_CONSTANT && !fill_rgb))
+        return fail(c, SRH_ERR_BAD_ARG, "srh_scene_group_pack: null argument");
+    if ((C != 1 && C != 3) || mode < SRH_PAD_REFLECT || mode > SRH_PAD_CONSTANT)
+        return fail(c, SRH_ERR_BAD_ARG, "srh_scene_group_pack: bad channel count or mode");
+    if (fill_rgb && ((fill_rgb[0] | fill_rgb[1] | fill_rgb[2]) & ~255)) return fail(c, SRH_ERR_BAD_ARG, "srh_scene_group_pack: bad fill colour");
+    if (n < 1 || !scene_dims_ok(Ha, Wa) || !group_table_ok(table_host, n, C, Ha, Wa, src_bytes, false))
+        return fail(c, SRH_ERR_BAD_ARG, "srh_scene_group_pack: bad sizes or an inconsistent table");
+    hipSetDevice(c->device);
+    hipStream_t s = (hipStream_t)stream;
+    SceneGroupParams p;
+    p.src = src; p.dst = dst; p.table = table_dev; p.n = n; p.Ha = Ha; p.Wa = Wa; p.C = C; p.mode = mode;
+    if (fill_rgb) p.fill = (uint32_t)fill_rgb[0] | ((uint32_t)fill_rgb[1] << 8) | ((uint32_t)fill_rgb[2] << 16);
+    TRYK(c, "scene_group_pack", 0, ((double)src_bytes + (double)Ha * Wa * C), s, launch_scene_group_pack(p, s));
+    return 0;
+}
+
+extern "C" int srh_scene_group_crop(srh_ctx* c, const uint8_t* kp, const uint8_t* road, int Ha, int Wa, const int64_t* table_host,
+                                    const int64_t* table_dev, int n, uint8_t* out_kp, uint8_t* out_road, int64_t out_bytes, void* stream) {
+    if (!c || !kp || !road || !table_host || !table_dev || !out_kp || !out_road) return fail(c, SRH_ERR_BAD_ARG, "srh_scene_group_crop: null argument");
+    if (n < 1 || !scene_dims_ok(Ha, Wa) || !group_table_ok(table_host, n, 1, Ha, Wa, out_bytes, true))
+        return fail(c, SRH_ERR_BAD_ARG, "srh_scene_group_crop: bad sizes or an inconsistent table");
+    hipSetDevice(c->device);
+    hipStream_t s = (hipStream_t)stream;
+    SceneGroupParams a, b;
+    a.src = kp; a.dst = out_kp; a.table = table_dev; a.n = n; a.Ha = Ha; a.Wa = Wa; a.C = 1; a.mode = PAD_EDGE;
+    b = a; b.src = road; b.dst = out_road;
+    TRYK(c, "scene_group_crop", 0, 4.0 * (double)out_bytes, s, launch_scene_group_crop(a, b, s));
+    return 0;
+}

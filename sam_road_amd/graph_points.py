@@ -80,8 +80,8 @@ def _pool():
     return _POOL
 
 
-def _mask_points(mask, threshold, radius):
-    cand, sc = points_and_scores_from_mask(mask, threshold)
+def _mask_points(mask, threshold, radius, n_threads=None):
+    cand, sc = points_and_scores_from_mask(mask, threshold, n_threads)
     return nms_points(cand, sc, radius)
 
 
@@ -92,13 +92,16 @@ def _mask_candidates_ordered(mask, threshold, n_threads):
     return cand, np.ascontiguousarray(np.argsort(sc)[::-1], dtype=np.int64)
 
 
-def extract_graph_points(keypoint_mask, road_mask, config):
+def extract_graph_points(keypoint_mask, road_mask, config, n_threads=None):
     """graph_extraction.py:130-139.  The two masks are independent until the final merge: the road mask is processed on a worker
     thread while this thread does the keypoint mask (the library calls and numpy's argsort release the GIL).
     With u8 masks, thresholds >= 1 and integer radii (every shipped config) each mask's own nms_points call keeps all its
     candidates — their scores exceed 1.0, graph_utils.py:586 — and only orders them; then the whole step is: two threaded mask
     scans, numpy's two argsorts (kept for their tie order), numpy's argsort of the priorities, and ONE library call that gathers
-    the candidates in visiting order, suppresses and compacts (srh_nms_merge_points).  Everything else takes the general path."""
+    the candidates in visiting order, suppresses and compacts (srh_nms_merge_points).  Everything else takes the general path.
+    n_threads (None: the behaviour above): the whole call stays on the calling thread, the road mask after the keypoint mask, with that
+    many threads inside each mask scan — for callers that run many small scenes side by side (a scene group), where the
+    fan-out inside one call costs more than it saves.  The result does not depend on it."""
     u8 = all(m.dtype == np.uint8 and m.ndim == 2 and m.flags.c_contiguous for m in (keypoint_mask, road_mask))
     thr_k, thr_r = config.ITSC_THRESHOLD * 255, config.ROAD_THRESHOLD * 255
     if u8 and thr_k >= 1.0 and thr_r >= 1.0 and float(config.ROAD_NMS_RADIUS) == int(config.ROAD_NMS_RADIUS) \
@@ -112,12 +115,13 @@ def extract_graph_points(keypoint_mask, road_mask, config):
             if prof:
                 t_sec.append(time.perf_counter())
                 print(f"[points] {name}: {(t_sec[-1] - t_sec[-2]) * 1e3:.2f} ms", flush=True)
-        nt = max(1, worker_threads() // 2)
-        fut = _pool().submit(_mask_candidates_ordered, road_mask, thr_r, nt)
+        nt = max(1, worker_threads() // 2) if n_threads is None else max(1, int(n_threads))
+        if n_threads is None:
+            fut = _pool().submit(_mask_candidates_ordered, road_mask, thr_r, nt)
         xy_a, ord_a = _mask_candidates_ordered(keypoint_mask, thr_k, nt)
         na = xy_a.shape[0]
         lap("keypoint mask: scan + argsort")
-        xy_b, ord_b = fut.result()
+        xy_b, ord_b = fut.result() if n_threads is None else _mask_candidates_ordered(road_mask, thr_r, nt)
         nb = xy_b.shape[0]
         lap("wait for the road mask's")
         prio = np.concatenate([np.ones(na), np.zeros(nb)], axis=0)       # intersections first
@@ -133,9 +137,13 @@ def extract_graph_points(keypoint_mask, road_mask, config):
             raise _lib.SrhError(f"srh_nms_merge_points failed ({rc})")
         lap("gather + suppress + compact (library)")
         return out[:n.value].copy()
-    fut = _pool().submit(_mask_points, road_mask, thr_r, config.ROAD_NMS_RADIUS)
-    kp0 = _mask_points(keypoint_mask, thr_k, config.ITSC_NMS_RADIUS)
-    kp1 = fut.result()
+    if n_threads is not None:
+        kp0 = _mask_points(keypoint_mask, thr_k, config.ITSC_NMS_RADIUS, n_threads)
+        kp1 = _mask_points(road_mask, thr_r, config.ROAD_NMS_RADIUS, n_threads)
+    else:
+        fut = _pool().submit(_mask_points, road_mask, thr_r, config.ROAD_NMS_RADIUS)
+        kp0 = _mask_points(keypoint_mask, thr_k, config.ITSC_NMS_RADIUS)
+        kp1 = fut.result()
     cand = np.concatenate([kp0, kp1], axis=0)
     prio = np.concatenate([np.ones(kp0.shape[0]), np.zeros(kp1.shape[0])], axis=0)  # intersections first
     return nms_points(cand, prio, config.ROAD_NMS_RADIUS)

@@ -122,13 +122,14 @@ def _kdtree_selfcheck():
     return ok
 
 
-def build_all_patch_queries(graph_points, infos, lo, hi, config, flat=False):
+def build_all_patch_queries(graph_points, infos, lo, hi, config, flat=False, n_threads=None):
     """build_patch_queries for tiles [lo, hi) in ONE call into the library's host code (srh_pass2_count / srh_pass2_fill,
     csrc/host_geom.hip: closed-box filter + exact integer kNN per tile, worker threads).  Source points whose scipy result is
     not determined by distances alone (tie at the k-th neighbour, coincident points) are answered by the library's restatement
     of scipy's kd-tree on their tile's points (ids ascending; csrc/kdtree_emul.hpp), so those rows equal the reference's call
     element for element; elsewhere the order inside a group of equidistant neighbours is (distance, index) where scipy's is
-    heap-internal.  Returns a list of per-tile tuples, or the flat form."""
+    heap-internal.  Returns a list of per-tile tuples, or the flat form.  n_threads: worker threads of the fill (None: fill_threads());
+    the result does not depend on it."""
     k, r = int(config.MAX_NEIGHBOR_QUERIES), config.NEIGHBOR_RADIUS
     n_tiles = hi - lo
     if n_tiles <= 0:
@@ -152,7 +153,7 @@ def build_all_patch_queries(graph_points, infos, lo, hi, config, flat=False):
     amb = np.empty(total, dtype=np.uint8)
     local = np.empty((total, 2), dtype=np.int64)
     if lib.srh_pass2_fill(_vp(pts), pts.shape[0], _vp(boxes), n_tiles, k, int(r), _vp(offsets), _vp(ids), _vp(knn), _vp(amb), _vp(local),
-                          fill_threads()) != 0:
+                          fill_threads() if n_threads is None else max(1, int(n_threads))) != 0:
         raise _lib.SrhError("srh_pass2_fill failed")
     lap("count + fill (library)")
     # (source points whose answer is not determined by distances alone — a tie at the K-th neighbour, a coincident point — were
@@ -352,7 +353,7 @@ def _votes_from_scores(fq, lo, batches, n_pts, K):
     return k[:cnt_c.value], s[:cnt_c.value]
 
 
-def _vote_sums(fq, lo, batches, n_pts, K):
+def _vote_sums(fq, lo, batches, n_pts, K, n_threads=None):
     """_votes_from_scores + _accumulate_votes without the ~700k intermediate votes of a CityScale scene: the library groups the
     query rows by source point and adds every point's votes into a table of its few dozen targets (srh_pass2_vote_sums,
     csrc/host_geom.hip; visiting order per key kept, so the float64 sums, counts and first-vote positions are the same, bit for
@@ -369,7 +370,8 @@ def _vote_sums(fq, lo, batches, n_pts, K):
     uk, sums, cnts, first = np.empty(cap, np.int64), np.empty(cap, np.float64), np.empty(cap, np.float64), np.empty(cap, np.int64)
     nu = C.c_int64(0)
     rc = lib.srh_pass2_vote_sums(ptrs, _vp(tile0), _vp(cnt), _vp(n_max), nb, K, _vp(fq.offsets), fq.n_tiles, _vp(fq.ids), _vp(fq.knn),
-                                 n_pts, _vp(uk), _vp(sums), _vp(cnts), _vp(first), cap, C.byref(nu), worker_threads())
+                                 n_pts, _vp(uk), _vp(sums), _vp(cnts), _vp(first), cap, C.byref(nu),
+                                 worker_threads() if n_threads is None else max(1, int(n_threads)))
     del keep
     if rc != 0:
         raise AssertionError("edge score outside [0, 1] (reference inferencer.py:219) or inconsistent query arrays")
@@ -415,11 +417,13 @@ def _queue_pass2(net, emb, fq, bs, K, ragged, io):
     return plan, scores
 
 
-def _collect_pass2(fq, plan, scores, n_pts, K, raw=False):
+def _collect_pass2(fq, plan, scores, n_pts, K, raw=False, n_threads=None):
     """The votes of a pass 2 that _queue_pass2 launched, from its scores on the host (numpy, in the order returned): the unique keys with
     their sums, counts and first-vote positions (_vote_sums), or for raw=True the votes themselves in visiting order."""
     batches = _ragged_batches(fq, scores[0]) if plan == "ragged" else [(tiles, sc) for (tiles, _, _), sc in zip(plan, scores)]
-    return (_votes_from_scores if raw else _vote_sums)(fq, 0, batches, n_pts, K)
+    if raw:
+        return _votes_from_scores(fq, 0, batches, n_pts, K)
+    return _vote_sums(fq, 0, batches, n_pts, K, n_threads)
 
 
 def edge_votes(net, emb, graph_points, infos, lo, hi, config, device, raw=False):
@@ -867,6 +871,129 @@ def tta_plan(config):
     return names, [TTA_NAMES.index(n) for n in names]
 
 
+# ---- several small scenes as one pass 1 (SCENE_GROUP) --------------------------------------------------------------------------------
+def scene_group_key(config, group=None):
+    """config.SCENE_GROUP (extension key), or `group` where it is given (infer_imgs' argument), as the number of
+    consecutive scenes that run as one: 1 for a missing key, None or 1 — nothing changes anywhere.  ValueError — before the device is
+    touched — for anything but None and an int >= 1."""
+    v = config.SCENE_GROUP if group is None else group
+    if _absent(v):
+        return 1
+    if not _is_int(v) or v < 1:
+        raise ValueError(f"SCENE_GROUP must be an int >= 1 (the number of consecutive scenes that run as one), got {v!r}")
+    return int(v)
+
+
+@dataclasses.dataclass
+class _GroupScene:
+    """One scene of a group, planned: everything _pass1_front fixes for a scene before the device is touched."""
+    img: np.ndarray                   # u8 [H,W,3]
+    valid: np.ndarray                 # u8 [H,W], or None
+    shape: tuple                      # (H, W)
+    pads: tuple                       # (top, bottom, left, right): zeros without SCENE_PAD
+    infos: list                       # the candidate tiles and their origins in the scene's VIRTUAL frame
+    all_xy: np.ndarray
+    row0: int = 0                     # the stack row the virtual scene starts at
+
+    @property
+    def virtual(self):
+        return self.shape[0] + self.pads[0] + self.pads[1], self.shape[1] + self.pads[2] + self.pads[3]
+
+
+def _plan_group_scene(img, valid, config):
+    """_pass1_front's planning step for one scene of a group: the same checks in the same order, so a scene that would raise alone
+    raises the same error here."""
+    img, infos, all_xy = _scene_plan(img, config)
+    pad = scene_pad_plan(img.shape, config)
+    shape = tuple(int(v) for v in img.shape[:2])
+    if valid is not None:
+        valid = _valid_plan(valid, shape, config)[0]
+    return _GroupScene(np.ascontiguousarray(img), valid, shape, tuple(pad[:4]) if pad is not None else (0, 0, 0, 0), infos, all_xy)
+
+
+def group_fits(sizes, n_max):
+    """Whether scenes of the virtual sizes `sizes` = [(H', W'), ...] may share one stack: at most n_max of them, and the stack (sum H') x
+    (max W') within the 2^31 - 1 pixels a scene may have.  (The existing entries have no tile limit of their own below that of an int.)"""
+    return len(sizes) <= n_max and sum(h for h, _ in sizes) * max(w for _, w in sizes) <= 2 ** 31 - 1
+
+
+def _scene_groups(imgs, valids, config, n):
+    """The scenes of a stream as planned groups, lazily: lists of up to n consecutive _GroupScene.  A group closes at n scenes and before
+    a scene that would take the stack past group_fits; `valids` is read in step with `imgs`.  Every scene is planned (and refused) as it
+    is read."""
+    group = []
+    for img in imgs:
+        sc = _plan_group_scene(img, next(valids), config)
+        if group and not group_fits([g.virtual for g in group] + [sc.virtual], n):
+            yield group
+            group = []
+        group.append(sc)
+        if len(group) == n:
+            yield group
+            group = []
+    if group:
+        yield group
+
+
+def group_geometry(scenes, any_mask=None):
+    """The stack of a group: (Ha, Wa, tables int64 [T,n,8], tile origins int32 [N,2] on the stack, first tile of every
+    scene [n+1]); sets every scene's row0.  Table rows are {byte offset, H, W, top, left, H', W', row0} (include/samroad_hip.h).  tables[0]
+    packs the scenes (offsets into the ragged u8 [sum H W 3] buffer), tables[1] crops the masks (offsets into the ragged [sum H W]
+    outputs) and, if any scene has a mask, tables[2] packs the masks: a masked scene's block is its H x W mask, an unmasked scene's is H' x
+    W' ones with no pads — its whole rectangle is valid, whatever the pad mode."""
+    if any_mask is None:
+        any_mask = any(sc.valid is not None for sc in scenes)
+    n = len(scenes)
+    tables = np.zeros((3 if any_mask else 2, n, 8), dtype=np.int64)
+    row0 = off = moff = 0
+    xy, first = [], [0]
+    for k, sc in enumerate(scenes):
+        (H, W), (Hv, Wv), (top, _, left, _) = sc.shape, sc.virtual, sc.pads
+        sc.row0 = row0
+        tables[0, k] = (3 * off, H, W, top, left, Hv, Wv, row0)
+        tables[1, k] = (off, H, W, top, left, Hv, Wv, row0)
+        if any_mask:
+            tables[2, k] = (moff, H, W, top, left, Hv, Wv, row0) if sc.valid is not None else (moff, Hv, Wv, 0, 0, Hv, Wv, row0)
+            moff += H * W if sc.valid is not None else Hv * Wv
+        xy.append(sc.all_xy + np.array([[0, row0]], dtype=np.int32))
+        first.append(first[-1] + len(sc.infos))
+        off += H * W
+        row0 += Hv
+    Wa = max(sc.virtual[1] for sc in scenes)
+    return row0, Wa, tables, np.ascontiguousarray(np.concatenate(xy), dtype=np.int32), np.array(first, dtype=np.int64)
+
+
+def _group_stack(ctx, io, scenes):
+    """The device side of a group's front end up to where a single scene stands after its pad step: one staged ragged upload of the real
+    scenes (and one of the masks, if any scene has one), the tables, the pack launches.  Returns (stack u8 [Ha,Wa,3], mask stack u8
+    [Ha,Wa] or None, tile origins on the stack, first tile per scene, crop table (host), crop table (device))."""
+    net, config = ctx.net, ctx.config
+    pad = scene_pad_plan(scenes[0].shape, config)
+    mode, fill = (pad[4], pad[5]) if pad is not None else ("reflect", (0, 0, 0))
+    any_mask = any(sc.valid is not None for sc in scenes)
+    Ha, Wa, tables, all_xy, first = group_geometry(scenes, any_mask)
+
+    def stage(name, n):
+        return io.alloc(name, (n,), np.uint8) if io.alloc is not None else np.empty(n, np.uint8)
+
+    src = stage("group_scene", int(tables[1, -1, 0] + tables[1, -1, 1] * tables[1, -1, 2]) * 3)
+    for sc, off in zip(scenes, tables[0, :, 0]):
+        src[off:off + sc.img.size] = sc.img.reshape(-1)
+    ragged = io.upload_packed("group_scene", src)
+    tables_d = io.upload("group_tables", tables)
+    if any_mask:
+        msrc = stage("group_mask", int(tables[2, -1, 0] + tables[2, -1, 1] * tables[2, -1, 2]))
+        for sc, (off, h, w) in zip(scenes, tables[2, :, :3]):
+            msrc[off:off + h * w] = 1 if sc.valid is None else sc.valid.reshape(-1)
+        mragged = io.upload_packed("group_mask", msrc)
+    io.step("upload")
+    host = torch.from_numpy(tables)
+    scene = net.scene_group_pack(ragged, host[0], 3, Ha, Wa, mode, fill, table_dev=tables_d[0])
+    valid_d = net.scene_group_pack(mragged, host[2], 1, Ha, Wa, mode, (0, 0, 0), table_dev=tables_d[2]) if any_mask else None
+    io.step("pack")
+    return scene, valid_d, all_xy, first, host[1], tables_d[1]
+
+
 class TilePlan(list):
     """What scene_tiles returns: the list of tiles, in `orientations` the names every one of them is run in, and in `pads` the (top, bottom,
     left, right) of SCENE_PAD (zeros without it)."""
@@ -904,6 +1031,9 @@ class _Lane:
     event, downloads are asynchronous copies into page-locked buffers followed by an event — no call blocks the host until the
     results are actually needed.  (A pageable-memory hipMemcpyAsync is stream-ordered AND host-blocking: issued behind a scene's
     pass 1 it would park the host for the whole pass.)  Degenerates to synchronous copies on a CPU device."""
+
+    times = None       # tools set a list here (tools/scene_bench.py; no environment switch): every unit of infer_imgs that ran a pass 2 then
+                       # appends (scenes in the unit, device ms of pass 1, device ms of pass 2), from the events of the profile
 
     def __init__(self, device):
         self.device = device
@@ -962,7 +1092,7 @@ class _Lane:
 class _BlockingIO:
     """How infer_one_img and the tile-sharded loops move a scene's arrays: one blocking copy each way, pageable memory.  The other
     implementation of the same four operations is _LaneIO.  `lap` (a _Laps) names the steps of pass 1 for the profile."""
-    STEPS = {"upload": "scene upload", "pad": "scene pad", "select": "tile selection (count kernel + counts D2H)", "fill": "nodata fill",
+    STEPS = {"upload": "scene upload", "pad": "scene pad", "pack": "group pack", "select": "tile selection (count kernel + counts D2H)", "fill": "nodata fill",
              "pass 1": "pass 1 (GPU)"}
     alloc = None                                       # the pass-2 collate fills plain numpy arrays
 
@@ -988,12 +1118,12 @@ class _LaneIO:
     """The operations of _BlockingIO on infer_imgs' lane, for ONE scene in flight (`pool`: its page-locked staging): uploads are staged
     and stream-ordered, the counts come back over the copy stream, the pass-2 collate writes straight into the staging buffers.  With the
     profile on, five device events time the scene's pass 1, pass 2 and score download."""
-    STEPS = {"upload": "stage + queue scene upload", "pad": "queue scene pad", "select": "tile selection (upload lane)", "pass 1": "queue pass 1"}
+    STEPS = {"upload": "stage + queue scene upload", "pad": "queue scene pad", "pack": "queue group pack", "select": "tile selection (upload lane)", "pass 1": "queue pass 1"}
     EVENTS = {"launch pass 1": 0, "normalised": 1, "pass 2 uploaded": 2, "pass 2 launched": 3, "pass 2 on its way back": 4}
 
     def __init__(self, lane, pool, lap):
         self.lane, self.pool, self.lap, self.stage = lane, pool, lap, {}
-        self.t = [torch.cuda.Event(enable_timing=True) for _ in self.EVENTS] if lap.on and lane.cuda else None
+        self.t = [torch.cuda.Event(enable_timing=True) for _ in self.EVENTS] if (lap.on or lane.times is not None) and lane.cuda else None
 
     def upload(self, name, arr):
         return self.lane.upload(self.pool, name, arr)
@@ -1070,42 +1200,66 @@ class _SceneJob:
     scores: list = None
     e2: object = None
     votes: tuple = None
+    # a scene group (SCENE_GROUP): this job is the stack — shape (Ha, Wa), infos / all_xy the kept tiles on the stack, emb all of them,
+    # kp_u8 the u8 [2, sum H W] tensor of every scene's cropped masks — and `group` holds one child job per scene: its tiles in its
+    # own real frame, [lo, hi) its rows of the stack's emb (empty: it kept no tile), mask_off the byte offset of its masks
+    group: list = None
+    mask_off: int = 0
+    row0: int = 0                     # first query row of a child in the group's one ragged pass 2
 
 
-def _pass1_front(ctx, io, img, valid=None):
+def _pass1_front(ctx, io, img, valid=None, group=None):
     """Pass 1 of one scene, queued (GPU): plan, upload, [border padding,] [tile selection, nodata fill,] crop -> encoder -> decoder ->
     fused canvases, [canvas reduce,] normalise[, masks cropped back].  `io` decides how arrays travel and when the host waits
     (_BlockingIO / _LaneIO); everything else is the same for every loop.  Returns the _SceneJob: embeddings resident, the u8 masks on the
     device of rank 0 — fetching them is the caller's.  SCENE_PAD lives here and nowhere else: the real scene (and mask)
     is uploaded and padded on the device, everything up to the normalise runs on that virtual scene through the same calls, the u8 masks
-    are cropped to the real scene before they travel, and the job carries the tiles in the real scene's frame for pass 2."""
+    are cropped to the real scene before they travel, and the job carries the tiles in the real scene's frame for pass 2.
+    group (SCENE_GROUP; img and valid are None then): a planned group, a list of _GroupScene, takes the place of the one
+    scene — one ragged upload and one pack launch build the vertical stack of the scenes (each padded by its own pads) and of their masks,
+    then the stack IS the scene of the code below, and one crop launch cuts every scene's window out of the stack's masks; the job
+    is the stack's, its `group` the scenes' (see _SceneJob).  Without a group none of its branches is taken."""
     net, config = ctx.net, ctx.config
-    img, infos, all_xy = _scene_plan(img, config)
-    pad = scene_pad_plan(img.shape, config)
-    shape = tuple(int(v) for v in img.shape[:2])
-    pads = pad[:4] if pad is not None and any(pad[:4]) else None     # all four 0: the launches of a run without the key
-    if valid is not None:
-        valid, min_frac, fill = _valid_plan(valid, shape, config)
-    pass1_kw, norm_kw, n_orient = ctx.features
-    scene = io.upload("scene", img)                    # the u8 scene, ONCE; tiles are cropped on the device
-    xy_dev = io.upload("xy", all_xy)
-    if valid is not None:
-        valid_d = io.upload("valid_mask", valid)       # a key of its own: "valid" stages pass 2's pair flags
-    io.step("upload")
-    if pads is not None:
-        scene = net.scene_pad(scene, pads, pad[4], pad[5])
-        if valid is not None:                          # the mask by the same rule: reflect / edge mirror its validity, constant padding is nodata
-            valid_d = net.scene_pad(valid_d, pads, pad[4], (0, 0, 0))
-        io.step("pad")
-    job_pads = pads or (0, 0, 0, 0)
+    if group is not None:
+        masked = [sc for sc in group if sc.valid is not None]
+        if masked:
+            valid, min_frac, fill = _valid_plan(masked[0].valid, masked[0].shape, config)
+        pass1_kw, norm_kw, n_orient = ctx.features
+        scene, valid_d, all_xy, first, crop_table, crop_table_d = _group_stack(ctx, io, group)
+        infos = list(range(all_xy.shape[0]))           # on the stack a tile is known by its index alone
+        xy_dev = io.upload("xy", all_xy)
+        shape, pads, job_pads = tuple(int(v) for v in scene.shape[:2]), None, (0, 0, 0, 0)
+    else:
+        img, infos, all_xy = _scene_plan(img, config)
+        pad = scene_pad_plan(img.shape, config)
+        shape = tuple(int(v) for v in img.shape[:2])
+        pads = pad[:4] if pad is not None and any(pad[:4]) else None     # all four 0: the launches of a run without the key
+        if valid is not None:
+            valid, min_frac, fill = _valid_plan(valid, shape, config)
+        pass1_kw, norm_kw, n_orient = ctx.features
+        scene = io.upload("scene", img)                    # the u8 scene, ONCE; tiles are cropped on the device
+        xy_dev = io.upload("xy", all_xy)
+        if valid is not None:
+            valid_d = io.upload("valid_mask", valid)       # a key of its own: "valid" stages pass 2's pair flags
+        io.step("upload")
+        if pads is not None:
+            scene = net.scene_pad(scene, pads, pad[4], pad[5])
+            if valid is not None:                          # the mask by the same rule: reflect / edge mirror its validity, constant padding is nodata
+                valid_d = net.scene_pad(valid_d, pads, pad[4], (0, 0, 0))
+            io.step("pad")
+        job_pads = pads or (0, 0, 0, 0)
     if valid is not None:
         # every rank holds the scene and the mask, computes the same integer counts and therefore the same kept list: from here
         # on infos / all_xy / xy_dev ARE the kept tiles (a subsequence of an x-outer list is x-outer, so the banded reduce stays valid)
-        kept = select_tiles(io.counts(lambda: net.scene_tile_valid(valid_d, xy_dev), after_compute=pads is not None), config.PATCH_SIZE, min_frac)
+        kept = select_tiles(io.counts(lambda: net.scene_tile_valid(valid_d, xy_dev), after_compute=pads is not None or group is not None),
+                            config.PATCH_SIZE, min_frac)
         io.step("select")
         infos, all_xy = [infos[i] for i in kept], np.ascontiguousarray(all_xy[kept])
         if len(kept) == 0:                             # nothing to run: the encoder is not launched and no exchange step is entered
-            return _SceneJob(shape, _shift_infos(infos, job_pads), all_xy, job_pads, empty=True)
+            job = _SceneJob(shape, _shift_infos(infos, job_pads), all_xy, job_pads, empty=True)
+            if group is not None:
+                job.group = _group_children(group, first, infos)
+            return job
         xy_dev = io.upload("xy_kept", all_xy)
         if scene.device.type != "cuda":                # a CPU tensor (the stand-in models of the gloo tests) may share the caller's memory
             scene = scene.clone()
@@ -1130,8 +1284,27 @@ def _pass1_front(ctx, io, img, valid=None):
         if pads is not None:                           # the real scene's window of the virtual masks, cut out on the device: H * W bytes travel
             (top, _, left, _), (H, W) = pads, shape
             job.kp_u8, job.road_u8 = (m[top:top + H, left:left + W].contiguous() for m in (job.kp_u8, job.road_u8))
+        if group is not None:                          # every scene's window of the stack's masks, one launch, one allocation
+            job.group = _group_children(group, first, infos)
+            job.kp_u8, job.road_u8 = net.scene_group_crop(job.kp_u8, job.road_u8, crop_table, table_dev=crop_table_d), None
     io.step("normalised")
     return job
+
+
+def _group_children(group, first, kept):
+    """One child job per scene of a group: `kept`, ascending indices into the group's candidate tile list (scene k's candidates are
+    first[k] .. first[k + 1]), mapped back to the scenes.  A child's tiles are its own, in its own real frame; [lo, hi) are its rows of
+    the stack's embeddings; a scene that kept no tile is empty."""
+    kept = np.asarray(kept, dtype=np.int64)
+    cut = np.searchsorted(kept, first)
+    children, off = [], 0
+    for k, sc in enumerate(group):
+        mine = kept[cut[k]:cut[k + 1]] - first[k]
+        child = _SceneJob(sc.shape, _shift_infos([sc.infos[i] for i in mine], sc.pads), np.ascontiguousarray(sc.all_xy[mine]), sc.pads,
+                          empty=len(mine) == 0, lo=int(cut[k]), hi=int(cut[k + 1]), mask_off=off)
+        children.append(child)
+        off += sc.shape[0] * sc.shape[1]
+    return children
 
 
 def _pass2_sharded(ctx, job, kp_mask, road_mask, stats=None, lap=None):
@@ -1201,7 +1374,7 @@ def _valid_iter(valids):
     return itertools.repeat(None) if valids is None else itertools.chain(iter(valids), itertools.repeat(None))
 
 
-def infer_imgs(net, imgs, config, device=None, tile_sharded=None, pipelined=None, valids=None):
+def infer_imgs(net, imgs, config, device=None, tile_sharded=None, pipelined=None, valids=None, group=None):
     """infer_one_img over a sequence of scenes, as a generator of the same tuples in the same order — software-pipelined on
     one GPU: while the device runs pass 1 of scene i+1, the host does scene i's mask -> points -> pass-2 queries; scene i's
     TopoNet batches are queued behind that pass 1 and its edge vote runs while scene i+2 is on the device.  One compute stream
@@ -1217,13 +1390,23 @@ def infer_imgs(net, imgs, config, device=None, tile_sharded=None, pipelined=None
     DESIGN.md §6), so it stays opt-in until an RCCL run exists; both give the same results (tests/test_distributed_cpu.py).
     valids: validity masks parallel to imgs (a list or any iterable, read in step with imgs; entries may be None), see infer_one_img.
     A masked scene's tile selection — mask upload, count kernel, n int32 back, one host wait — is issued on the upload lane; like every
-    upload there it starts after the work the compute stream holds at that moment (the previous scene's pass 2)."""
+    upload there it starts after the work the compute stream holds at that moment (the previous scene's pass 2).
+    group (None: config.SCENE_GROUP): an int n >= 2 runs up to n consecutive scenes as ONE unit of this pipeline — one
+    upload, one pass 1 over all their tiles in full batches, one normalise, one mask download, one ragged TopoNet launch sequence; the
+    host stages run one scene per worker thread.  The tuples and their order do not change; a group's results are yielded once the group
+    is finished, the last, shorter group when the input ends, and a group of one scene takes the single-scene path.  The tile batches
+    are composed differently from a scene's own, so on the GPU the masks agree with infer_one_img's within a level (tests/tolerances.py,
+    BATCH_INDEP_SCORE), not bit for bit.  Only this one-process loop groups: with a tile-sharded mode the key is a ValueError."""
     neighbor_queries(config)                          # fail before any scene touches the device
     fuse_window(config)
     tta_plan(config)
     scene_pad_key(config)
+    n_group = scene_group_key(config, group)
     valids = _valid_iter(valids)
     if D.is_distributed() if tile_sharded is None else tile_sharded:
+        if n_group > 1:
+            raise ValueError(f"SCENE_GROUP = {n_group} applies to the one-process scene loop (tile_sharded=False, CLI --shard scenes); a "
+                             f"tile-sharded mode runs its scenes one by one: drop the key or the mode")
         if pipelined is None:
             pipelined = _cfg_switch(config.TILE_SHARD_PIPELINE, False)
         if pipelined:
@@ -1238,14 +1421,14 @@ def infer_imgs(net, imgs, config, device=None, tile_sharded=None, pipelined=None
     pools = [_StagingPool(device), _StagingPool(device)]
     lap = _Laps("infer_imgs")                          # tuning aid: host wall time of each step (no device synchronisation)
 
-    def launch_pass1(img, pool, valid=None):           # G1: upload, pass 1, normalise, masks on their way to the host
+    def launch_pass1(img, pool, valid=None, group=None):           # G1: upload, pass 1, normalise, masks on their way to the host
         io = _LaneIO(lane, pool, lap)
-        job = _pass1_front(ctx, io, img, valid)
+        job = _pass1_front(ctx, io, img, valid, group)
         job.io = io
-        if job.empty:                                  # zero masks, no nodes
-            job.masks = [torch.zeros(job.shape, dtype=torch.uint8) for _ in range(2)]
+        if job.empty:                                  # zero masks, no nodes (a group: every child is empty)
+            job.masks = [torch.zeros(job.shape, dtype=torch.uint8) for _ in range(2)] if group is None else None
             return job
-        job.masks, job.e1 = lane.download(pool, "mask", [job.kp_u8, job.road_u8])
+        job.masks, job.e1 = lane.download(pool, "mask", [job.kp_u8, job.road_u8] if group is None else [job.kp_u8])
         lap("queue normalise + mask download")
         return job
 
@@ -1285,13 +1468,19 @@ def infer_imgs(net, imgs, config, device=None, tile_sharded=None, pipelined=None
             lap("wait for pass-2 scores")
             if job.io.t is not None:
                 t = job.io.t
-                print(f"[infer_imgs] device: pass 1 {t[0].elapsed_time(t[1]):.1f} ms, mask download -> pass 2 start {t[1].elapsed_time(t[2]):.1f} ms, "
-                      f"pass 2 {t[2].elapsed_time(t[3]):.1f} ms, score download {t[3].elapsed_time(t[4]):.1f} ms", flush=True)
+                if lap.on:
+                    print(f"[infer_imgs] device: pass 1 {t[0].elapsed_time(t[1]):.1f} ms, mask download -> pass 2 start {t[1].elapsed_time(t[2]):.1f} ms, "
+                          f"pass 2 {t[2].elapsed_time(t[3]):.1f} ms, score download {t[3].elapsed_time(t[4]):.1f} ms", flush=True)
+                if lane.times is not None:
+                    lane.times.append((1, t[0].elapsed_time(t[1]), t[2].elapsed_time(t[3])))
             job.votes = _collect_pass2(job.fq, job.plan, [sc.numpy() for sc in job.scores], n_pts, K)
         edges = votes_to_edges(*job.votes, n_pts, config.TOPO_THRESHOLD)
         lap("votes -> edges")
         return nodes, edges, job.kp_mask, job.road_mask
 
+    if n_group > 1:
+        yield from _infer_imgs_grouped(ctx, lane, pools, lap, imgs, valids, n_group, launch_pass1, points_and_pass2, finish)
+        return
     it = iter(imgs)
     img = next(it, None)
     if img is None:
@@ -1317,6 +1506,152 @@ def infer_imgs(net, imgs, config, device=None, tile_sharded=None, pipelined=None
     with _host_quiet():
         res = finish(prev)
     yield res
+
+
+class _ChildIO:
+    """A group's _LaneIO / _BlockingIO for ONE of its scenes in the padded pass 2 (PASS2_RAGGED off): the scenes' collates must not share
+    staging buffers, since an upload is still on its way when the next scene is collated."""
+
+    def __init__(self, io, k):
+        self.io, self.k = io, k
+        self.alloc = None if io.alloc is None else (lambda name, shape, dtype: io.alloc(f"{name}#{k}", shape, dtype))
+
+    def upload_packed(self, name, arr):
+        return self.io.upload_packed(f"{name}#{self.k}", arr)
+
+    def step(self, name):
+        pass
+
+
+def _group_pool_threads(n):
+    """Threads of the pool that runs a group's host stages, one scene per thread with ONE thread inside each call."""
+    return max(1, min(int(n), worker_threads()))
+
+
+def _concat_queries(job, live):
+    """The flat queries of a group's scenes as ONE _FlatQueries over the tiles of the group's embedding tensor: a scene's tile t is tile lo
+    + t there, its rows keep their order, and child.row0 is set to its first row.  (ids stay per scene: the votes read them there.)"""
+    counts = np.zeros(int(job.emb.shape[0]), dtype=np.int64)
+    for c in live:
+        counts[c.lo:c.hi] = np.diff(c.fq.offsets)
+    offsets = np.zeros(counts.shape[0] + 1, dtype=np.int64)
+    np.cumsum(counts, out=offsets[1:])
+    for c in live:
+        c.row0 = int(offsets[c.lo])
+    cat = lambda name: np.ascontiguousarray(np.concatenate([getattr(c.fq, name) for c in live], axis=0))
+    return _FlatQueries(offsets, cat("ids"), cat("local"), cat("knn"))
+
+
+def _infer_imgs_grouped(ctx, lane, pools, lap, imgs, valids, n_group, launch_pass1, points_and_pass2, finish):
+    """infer_imgs' pipeline with a GROUP of scenes as its unit (SCENE_GROUP): while the device runs pass 1 of group i+1,
+    the host does group i's points and queries, scene-parallel; group i's ONE ragged TopoNet launch sequence is queued behind that pass 1
+    and its votes are read while group i+2 is on the device.  A group of one scene is a unit of the single-scene functions, untouched."""
+    from concurrent.futures import ThreadPoolExecutor
+    net, config, device, K = ctx.net, ctx.config, ctx.device, ctx.K
+    no_edges = np.zeros((0, 2), dtype=np.int32)
+    host_pool = ThreadPoolExecutor(_group_pool_threads(n_group), thread_name_prefix="srh-group")
+
+    def launch(unit, pool):
+        return launch_pass1(unit[0].img, pool, unit[0].valid) if len(unit) == 1 else launch_pass1(None, pool, None, unit)
+
+    def group_points_and_pass2(job):                   # H1 + G2 of every scene: points and queries side by side, ONE pass 2
+        if job.empty:
+            return
+        if job.e1 is not None:
+            job.e1.synchronize()
+        both = job.masks[0].numpy()                    # u8 [2, sum H W]: every scene's keypoint masks, then every scene's road masks
+        _kdtree_selfcheck()                            # once, before the threads need its answer
+
+        def one(c):
+            (H, W), a = c.shape, c.mask_off
+            c.kp_mask, c.road_mask = (both[j, a:a + H * W].reshape(H, W).copy() for j in (0, 1))
+            c.graph_points = extract_graph_points(c.kp_mask, c.road_mask, config, n_threads=1)
+            if c.graph_points.shape[0]:
+                c.fq = build_all_patch_queries(c.graph_points, c.infos, 0, len(c.infos), config, flat=True, n_threads=1)
+
+        list(host_pool.map(one, [c for c in job.group if not c.empty]))
+        lap("group: points + queries")
+        live = [c for c in job.group if not c.empty and c.graph_points.shape[0]]
+        if not live:
+            return
+        if any(c.fq is None for c in live):            # non-integer radius: the serial per-tile path, scene by scene
+            for c in live:
+                c.votes = edge_votes(net, job.emb[c.lo:c.hi], c.graph_points, c.infos, 0, len(c.infos), config, device)
+        elif _ragged_pass2(net, config):               # the rows of all scenes in ONE launch sequence: tile indices count through the group
+            job.plan, scores = _queue_pass2(net, job.emb, _concat_queries(job, live), ctx.bs, K, True, job.io)
+            if job.plan:
+                job.scores, job.e2 = lane.download(job.io.pool, "score", scores)
+                job.io.step("pass 2 on its way back")
+        else:                                          # padded batches never mix scenes: per scene, as alone
+            for k, c in enumerate(live):
+                c.plan, scores = _queue_pass2(net, job.emb[c.lo:c.hi], c.fq, ctx.bs, K, False, _ChildIO(job.io, k))
+                if c.plan:
+                    c.scores, c.e2 = lane.download(job.io.pool, f"score#{k}_", scores)
+        job.emb = None
+        lap("group: pack + queue pass 2")
+
+    def group_finish(job):                             # H2 of every scene, side by side
+        rows = None
+        if job.plan:
+            if job.e2 is not None:
+                job.e2.synchronize()
+            rows = job.scores[0].numpy()
+            if job.io.t is not None and lane.times is not None:
+                t = job.io.t
+                lane.times.append((len(job.group), t[0].elapsed_time(t[1]), t[2].elapsed_time(t[3])))
+        for c in job.group:
+            if c.e2 is not None:
+                c.e2.synchronize()
+        lap("group: wait for pass-2 scores")
+
+        def one(c):
+            if c.empty:
+                return _empty_result(*c.shape)
+            if c.graph_points.shape[0] == 0:
+                return c.graph_points, no_edges, c.kp_mask, c.road_mask
+            nodes, n_pts = c.graph_points[:, ::-1], c.graph_points.shape[0]
+            if c.votes is None:
+                R = int(c.fq.offsets[-1] - c.fq.offsets[0])
+                if rows is not None and R:
+                    c.votes = _collect_pass2(c.fq, "ragged", [rows[c.row0:c.row0 + R]], n_pts, K, n_threads=1)
+                elif c.plan:
+                    c.votes = _collect_pass2(c.fq, c.plan, [sc.numpy() for sc in c.scores], n_pts, K, n_threads=1)
+                else:
+                    return nodes, no_edges.astype(np.int64), c.kp_mask, c.road_mask
+            return nodes, votes_to_edges(*c.votes, n_pts, config.TOPO_THRESHOLD), c.kp_mask, c.road_mask
+
+        res = list(host_pool.map(one, job.group))
+        lap("group: votes -> edges")
+        return res
+
+    try:
+        units = _scene_groups(iter(imgs), valids, config, n_group)
+        unit = next(units, None)
+        if unit is None:
+            return
+        with _host_quiet():
+            cur = launch(unit, pools[0])
+        prev, i = None, 0
+        while cur is not None:
+            with _host_quiet():
+                lap("(consumer)")
+                if cur.e1 is not None:
+                    cur.e1.synchronize()               # group i's masks are on the host: the device is free for group i+1
+                    _poll_finite(net, device)
+                lap("wait for pass-1 masks")
+                unit = next(units, None)
+                nxt = launch(unit, pools[(i + 1) % 2]) if unit is not None else None
+                res = None if prev is None else [finish(prev)] if prev.group is None else group_finish(prev)
+            if prev is not None:
+                yield from res
+            with _host_quiet():
+                (points_and_pass2 if cur.group is None else group_points_and_pass2)(cur)
+            prev, cur, i = cur, nxt, i + 1
+        with _host_quiet():
+            res = [finish(prev)] if prev.group is None else group_finish(prev)
+        yield from res
+    finally:
+        host_pool.shutdown(wait=False)
 
 
 def _infer_imgs_tile_sharded(net, imgs, config, device=None, stats=None, valids=None):
@@ -1509,8 +1844,14 @@ def main(argv=None):
     ap.add_argument("--scene-pad-mode", default=None, metavar="MODE", choices=SCENE_PAD_MODES,
                     help="(extension) how the padding is filled, overriding the mode of the config's SCENE_PAD: reflect (default), edge "
                          "or constant (the colour NODATA_FILL)")
+    ap.add_argument("--scene-group", default=None, type=int, metavar="N",
+                    help="(extension) run up to N consecutive scenes as one — one upload, one pass 1 over all their tiles in full batches, "
+                         "one TopoNet launch sequence — overriding the config's SCENE_GROUP; for streams of small scenes (chips).  1: scene "
+                         "by scene.  Not with --shard tiles / tiles-pipelined")
     args = ap.parse_args(argv)
     config = load_config(args.config)
+    if args.scene_group is not None:
+        config.SCENE_GROUP = args.scene_group
     if args.scene_pad is not None or args.scene_pad_mode is not None:
         config.SCENE_PAD = scene_pad_override(config, args.scene_pad, args.scene_pad_mode)
     if args.fuse_window is not None:
@@ -1521,6 +1862,8 @@ def main(argv=None):
     fuse_window(config)                          # and so does a FUSE_WINDOW that cannot be used
     tta_plan(config)                             # and a TTA list that cannot be run
     scene_pad_plan((1, 1), config)               # and a SCENE_PAD (or the NODATA_FILL it uses) that cannot be used
+    if scene_group_key(config) > 1 and args.shard != "scenes" and int(os.environ.get("WORLD_SIZE", "1")) > 1:      # and a SCENE_GROUP
+        raise ValueError("SCENE_GROUP applies to --shard scenes (every rank runs whole scenes); a tile-sharded mode runs its scenes one by one")
     device = torch.device("cuda") if args.device == "cuda" else torch.device(args.device)
     torch.set_num_threads(max(1, min(torch.get_num_threads(), usable_cpus() // max(1, int(os.environ.get("WORLD_SIZE", "1"))))))   # this rank's share of the container's CPU quota (hostcpu.py)
     _numpy_hugepages(False)                      # for the whole run: image decoding and output encoding allocate beside the GPU too (_host_quiet)

@@ -701,3 +701,67 @@ class SAMRoad(nn.Module):
             ctx.check(ctx.lib.srh_scene_pad(ctx.handle, t_u8.data_ptr(), H, W, ch, top, bottom, left, right, _lib.SRH_PAD_MODES[mode], rgb,
                                             out.data_ptr(), self._stream(dev)), "srh_scene_pad")
         return out
+
+    # ---- scene level, groups of small scenes (SCENE_GROUP) -------------------------------------------------------------
+    @staticmethod
+    def _group_table(table, table_dev, dev):
+        """(table on the host as a contiguous int64 [n,8] CPU tensor, the same on the device): the library validates the host copy and
+        the kernel reads the device copy (include/samroad_hip.h); without table_dev the table is uploaded here."""
+        t = torch.as_tensor(table)
+        if t.device.type != "cpu" or t.dtype != torch.int64 or t.dim() != 2 or t.shape[1] != 8 or t.shape[0] < 1:
+            raise ValueError(f"a scene-group table is an int64 [n, 8] array on the host with n >= 1, got {t.dtype} {tuple(t.shape)} on {t.device}")
+        t = t.contiguous()
+        if table_dev is None:
+            table_dev = t.to(dev)
+        if table_dev.device != dev or table_dev.dtype != torch.int64 or tuple(table_dev.shape) != tuple(t.shape) or not table_dev.is_contiguous():
+            raise ValueError(f"table_dev must be the table as a contiguous int64 {tuple(t.shape)} tensor on {dev}")
+        return t, table_dev
+
+    @torch.no_grad()
+    def scene_group_pack(self, ragged_u8, table, C, Ha, Wa, mode="reflect", fill=(0, 0, 0), table_dev=None):
+        """The stack of a group's scenes (srh_scene_group_pack): ragged_u8, a flat uint8 / bool tensor on the GPU that holds the real scenes
+        back to back (any byte address), table int64 [n,8] on the HOST with one row {byte offset in ragged_u8, H, W, top, left, H', W', row0}
+        per scene -> a NEW tensor [Ha, Wa, 3] (C = 3) or [Ha, Wa] (C = 1) of ragged_u8's dtype: rows row0 .. row0 + H' hold the scene padded
+        as scene_pad pads it, with its own pads, in columns 0 .. W', and 0 beyond.  table_dev: the table on the GPU if the caller has
+        uploaded it already."""
+        import ctypes
+        dev = ragged_u8.device
+        ctx, _ = self._weights(dev)
+        if ragged_u8.dtype not in (torch.uint8, torch.bool) or ragged_u8.dim() != 1 or not ragged_u8.is_contiguous() or ragged_u8.numel() < 1:
+            raise ValueError(f"scene_group_pack takes a flat contiguous uint8 / bool tensor, got {ragged_u8.dtype} {tuple(ragged_u8.shape)}")
+        if mode not in _lib.SRH_PAD_MODES:
+            raise ValueError(f"mode must be one of {tuple(_lib.SRH_PAD_MODES)}, got {mode!r}")
+        if C not in (1, 3):
+            raise ValueError(f"C must be 1 or 3, got {C!r}")
+        t, t_dev = self._group_table(table, table_dev, dev)
+        Ha, Wa = int(Ha), int(Wa)
+        if Ha < 1 or Wa < 1 or Ha * Wa > 2 ** 31 - 1:
+            raise ValueError(f"a stack has 1 to 2^31 - 1 pixels, got {Ha} x {Wa}")
+        rgb = (ctypes.c_int32 * 3)(*(int(v) for v in fill))
+        out = torch.empty((Ha, Wa, 3) if C == 3 else (Ha, Wa), dtype=ragged_u8.dtype, device=dev)
+        with torch.cuda.device(dev):
+            ctx.check(ctx.lib.srh_scene_group_pack(ctx.handle, ragged_u8.data_ptr(), ragged_u8.numel(), t.data_ptr(), t_dev.data_ptr(), int(t.shape[0]),
+                                                   int(C), Ha, Wa, _lib.SRH_PAD_MODES[mode], rgb, out.data_ptr(), self._stream(dev)),
+                      "srh_scene_group_pack")
+        return out
+
+    @torch.no_grad()
+    def scene_group_crop(self, kp_u8, road_u8, table, table_dev=None):
+        """Every scene's window of the stack's two uint8 [Ha,Wa] masks, in ONE allocation (srh_scene_group_crop): table int64 [n,8] on the
+        HOST as for scene_group_pack, column 0 being the byte offset of the scene's H x W block in each output (0, H0 W0, H0 W0 + H1 W1, ...).
+        Returns a uint8 [2, sum H W] tensor: row 0 the keypoint masks, row 1 the road masks, the scenes back to back."""
+        dev = kp_u8.device
+        ctx, _ = self._weights(dev)
+        for m in (kp_u8, road_u8):
+            if m.device != dev or m.dtype != torch.uint8 or m.dim() != 2 or tuple(m.shape) != tuple(kp_u8.shape) or not m.is_contiguous():
+                raise ValueError(f"scene_group_crop takes two contiguous uint8 [Ha,Wa] masks on one GPU, got {m.dtype} {tuple(m.shape)} on {m.device}")
+        t, t_dev = self._group_table(table, table_dev, dev)
+        total = int((t[:, 1] * t[:, 2]).sum())
+        if total < 1:
+            raise ValueError("scene_group_crop: the table describes no pixel")
+        out = torch.empty((2, total), dtype=torch.uint8, device=dev)
+        with torch.cuda.device(dev):
+            ctx.check(ctx.lib.srh_scene_group_crop(ctx.handle, kp_u8.data_ptr(), road_u8.data_ptr(), int(kp_u8.shape[0]), int(kp_u8.shape[1]),
+                                                   t.data_ptr(), t_dev.data_ptr(), int(t.shape[0]), out[0].data_ptr(), out[1].data_ptr(), total,
+                                                   self._stream(dev)), "srh_scene_group_crop")
+        return out

@@ -15,6 +15,10 @@ The final map_decoder bias is lowered so that the random network yields sparse m
     python tools/scene_bench.py --tta id,flip_h,rot90               # test-time augmentation (TTA): every tile runs once per orientation
     python tools/scene_bench.py --scene-pad 64 [--scene-pad-mode edge]    # SCENE_PAD: the scene is padded by 64 px on every side on the device
                                                                     # (reflect by default), the masks and the graph are those of the real scene
+    python tools/scene_bench.py --scene 400 --tiles 1 --scene-pad 0 --scenes 256 --group 16    # a STREAM of 256 small scenes (chips) through
+                                                                    # infer_imgs with SCENE_GROUP 16: scenes/s, tiles/s, device ms of pass 1 and
+                                                                    # pass 2 per group, host ms per scene; --group 1 is the loop without the key
+    python tools/scene_bench.py --patch 256 --margin 0 --scene 400 --tiles 4 --scenes 256 --group 16     # the spacenet_4x4 geometry: 16 tiles of 256 px
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 tools/scene_bench.py    # N GPUs:
         tiles sharded over the ranks (RCCL: packed-weight broadcast, banded canvas reduce, point broadcast, vote gather);
         rank 0 prints ms/scene (max over ranks) and the per-rank stage times
@@ -39,6 +43,49 @@ def parse_scene(words):
     return int(parts[0]), int(parts[-1])
 
 
+def stream(args, net, cfg, H, W):
+    """--scenes M [--group N]: M scenes of H x W (eight different ones, in turn) through infer_imgs, three timed runs after a warm-up run.
+    Prints one JSON line: scenes/s and tiles/s (median run), the device time of pass 1 and pass 2 per unit of the loop (a group, or a
+    scene) from events, and the host time of one scene's points + queries on ONE thread, measured apart on the masks of the run."""
+    import sam_road_amd.inferencer as inf
+    from sam_road_amd.graph_points import extract_graph_points
+    rng = np.random.default_rng(0)
+    imgs = [np.kron(rng.integers(0, 256, size=(H // 8, W // 8, 3)).astype(np.float32), np.ones((8, 8, 1), np.float32)).astype(np.uint8) for _ in range(8)]
+    n_tiles = len(inf.scene_tiles((H, W), cfg))
+    group = {} if args.group == 1 else dict(group=args.group)
+    scenes = lambda m: (imgs[i % 8] for i in range(m))
+    outs = list(inf.infer_imgs(net, scenes(min(args.scenes, 2 * max(args.group, 8))), cfg, **group))       # warm-up: staging, workspaces
+    runs = []
+    inf._Lane.times = []
+    for _ in range(3):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        n_out = sum(1 for _ in inf.infer_imgs(net, scenes(args.scenes), cfg, **group))
+        torch.cuda.synchronize()
+        runs.append(time.perf_counter() - t0)
+        assert n_out == args.scenes
+    times, inf._Lane.times = inf._Lane.times, None
+    full = [t for t in times if t[0] == max(u[0] for u in times)] if times else []
+    host = []
+    for nodes, _, kp, road in outs[:8]:
+        t0 = time.perf_counter()
+        pts = extract_graph_points(kp, road, cfg, n_threads=1)
+        if pts.shape[0]:
+            inf.build_all_patch_queries(pts, inf.scene_tiles((H, W), cfg), 0, n_tiles, cfg, flat=True, n_threads=1)
+        host.append(1e3 * (time.perf_counter() - t0))
+    sec = float(np.median(runs))
+    med = lambda j: None if not full else round(float(np.median([t[j] for t in full])), 3)
+    print(json.dumps({"stream": f"{args.scenes} synthetic {H}x{W} u8 scenes, {n_tiles} tiles of {args.patch}^2 each (margin {args.margin})",
+                      "scene_group": args.group, "scene_pad": None if inf.scene_pad_key(cfg) is None else list(inf.scene_pad_plan((H, W), cfg)[:4]),
+                      "infer_batch_size": args.batch, "scenes_per_s": round(args.scenes / sec, 1), "tiles_per_s": round(args.scenes * n_tiles / sec, 1),
+                      "runs_scenes_per_s": [round(args.scenes / r, 1) for r in runs], "scenes_per_unit": full[0][0] if full else None,
+                      "device_ms_pass1_per_unit": med(1), "device_ms_pass2_per_unit": med(2),
+                      "host_ms_points_and_queries_per_scene_one_thread": round(float(np.median(host)), 3),
+                      "host_pool_threads": inf._group_pool_threads(args.group) if args.group > 1 else None,
+                      "graph_points_per_scene": round(float(np.mean([o[0].shape[0] for o in outs])), 1),
+                      "edges_per_scene": round(float(np.mean([o[1].shape[0] for o in outs])), 1)}))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--bias", type=float, default=-2.2)
@@ -58,6 +105,11 @@ def main():
     ap.add_argument("--scene-pad-mode", default=None, metavar="MODE", choices=("reflect", "edge", "constant"),
                     help="SCENE_PAD's mode (default reflect)")
     ap.add_argument("--no-pipelined", action="store_true", help="skip the infer_imgs runs (12- and 48-scene streams)")
+    ap.add_argument("--patch", type=int, default=512, metavar="P", help="PATCH_SIZE (default 512)")
+    ap.add_argument("--margin", type=int, default=64, metavar="M", help="SAMPLE_MARGIN (default 64)")
+    ap.add_argument("--scenes", type=int, default=None, metavar="M",
+                    help="time a STREAM of M scenes of the given size through infer_imgs instead of one scene (one GPU)")
+    ap.add_argument("--group", type=int, default=1, metavar="N", help="with --scenes: SCENE_GROUP, N consecutive scenes run as one (default 1: the key is absent)")
     args = ap.parse_args()
     H, W = parse_scene(args.scene)
     if len(args.tiles) not in (1, 2) or H % 8 or W % 8:
@@ -77,8 +129,8 @@ def main():
     torch.cuda.set_device(dev)
     from sam_road_amd.hostcpu import usable_cpus
     torch.set_num_threads(max(1, min(torch.get_num_threads(), usable_cpus() // world)))      # as the CLI does: respect the container's CPU quota
-    cfg = Config(SAM_VERSION="vit_b", PATCH_SIZE=512, TOPONET_VERSION="normal", SAM_CKPT_PATH="", DATASET="cityscale",
-                 INFER_BATCH_SIZE=args.batch, SAMPLE_MARGIN=64, INFER_PATCHES_PER_EDGE=per_edge, ITSC_THRESHOLD=0.248,
+    cfg = Config(SAM_VERSION="vit_b", PATCH_SIZE=args.patch, TOPONET_VERSION="normal", SAM_CKPT_PATH="", DATASET="cityscale",
+                 INFER_BATCH_SIZE=args.batch, SAMPLE_MARGIN=args.margin, INFER_PATCHES_PER_EDGE=per_edge, ITSC_THRESHOLD=0.248,
                  ROAD_THRESHOLD=0.364, TOPO_THRESHOLD=0.499, ITSC_NMS_RADIUS=8, ROAD_NMS_RADIUS=16, NEIGHBOR_RADIUS=64,
                  MAX_NEIGHBOR_QUERIES=16)
     if args.fuse_window is not None:
@@ -113,6 +165,10 @@ def main():
     coarse = rng.integers(0, 256, size=(H // 8, W // 8, 3)).astype(np.float32)
     img = np.kron(coarse, np.ones((8, 8, 1), np.float32)).astype(np.uint8)
 
+    if args.scenes is not None:
+        if world > 1 or args.scenes < 1 or args.group < 1:
+            ap.error("--scenes M --group N take M, N >= 1 and one GPU")
+        return stream(args, net, cfg, H, W)
     img, infos, all_xy = _scene_plan(img, cfg)         # the product's own validation and tile list (SCENE_PAD: of the padded scene)
     n_all = len(infos)
     valid = None
@@ -219,7 +275,7 @@ def main():
             dist.destroy_process_group()
         return
     nodes, edges, kp, road = res
-    print(json.dumps({"scene": f"synthetic {H}x{W} u8, {n_all} tiles of 512^2 ({per_edge} per edge, margin 64)", "n_gpus": world,
+    print(json.dumps({"scene": f"synthetic {H}x{W} u8, {n_all} tiles of {args.patch}^2 ({per_edge} per edge, margin {args.margin})", "n_gpus": world,
                       "fuse_window": args.fuse_window or "uniform",
                       "tta": tta_names,
                       "scene_pad": None if pad is None else {"pads": list(pad[:4]), "mode": pad[4]},
