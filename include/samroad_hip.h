@@ -40,7 +40,7 @@ typedef enum {
     /* ABI 9: an earlier srh_toponet_ragged call's pair outside its row's tile is reported the same lazy way, as SRH_ERR_BAD_ARG */
 } srh_status;
 
-typedef enum { SRH_F32 = 0, SRH_F16 = 1, SRH_U8 = 2, SRH_I32 = 3, SRH_I64 = 4 } srh_dtype;
+typedef enum { SRH_F32 = 0, SRH_F16 = 1, SRH_U8 = 2, SRH_I32 = 3, SRH_I64 = 4, SRH_U16 = 5 /* scene bands only */ } srh_dtype;
 
 typedef struct srh_ctx srh_ctx;          /* per (process, device): workspace + error state */
 typedef struct srh_weights srh_weights;  /* packed, device-resident, immutable model weights */
@@ -275,6 +275,28 @@ int srh_scene_group_pack(srh_ctx* ctx, const uint8_t* src, int64_t src_bytes, co
                          int C, int Ha, int Wa, int mode, const int32_t* fill_rgb, uint8_t* dst, void* stream);
 int srh_scene_group_crop(srh_ctx* ctx, const uint8_t* kp, const uint8_t* road, int Ha, int Wa, const int64_t* table_host,
                          const int64_t* table_dev, int n, uint8_t* out_kp, uint8_t* out_road, int64_t out_bytes, void* stream);
+
+/* 16-bit and multi-band scenes (config key SCENE_BANDS; an extension): band selection and a radiometric lookup table on
+ * the device, in front of everything above.  Two additive entries and one dtype code (SRH_U16); the ABI number stays 11 because nothing
+ * existing changes, and a run without the key calls neither.
+ *
+ * Both see the source as n_pixels pixels of C elements, dense, on the device: src_dtype SRH_U8 (levels = 256; any byte address) or
+ * SRH_U16 (levels = 65536; any 2-byte-aligned address), 1 <= C <= 16, 1 <= n_pixels <= 2^31 - 1.  They know nothing of rows: a scene
+ * and the ragged buffer of a scene group are the same to them.  select: HOST array of three ints in 0 .. C - 1 (repeats allowed), the
+ * source band of output channel 0, 1, 2.  The source is not written.
+ *
+ *   hist: u32 [3, levels] on the device, zeroed by the call itself; on return hist[b][v] is the exact number of counted pixels whose
+ *     band select[b] holds v.  valid: u8 [n_pixels] on the device, 0 = the pixel is not counted, or NULL = every pixel is.  Integer
+ *     adds: the result does not depend on scheduling.
+ *   apply: dst u8 [n_pixels, 3] on the device (any byte address, not overlapping src), byte 3 i + b = lut[b][src[i][select[b]]] with
+ *     lut u8 [3, levels] on the device.  Every byte of dst is written exactly once and nothing else is.
+ * SRH_ERR_BAD_ARG, and nothing is launched, for a null pointer (valid excepted), another dtype, C or n_pixels outside their range, a
+ * select entry outside 0 .. C - 1 or a misaligned u16 source.  Neither touches a workspace of the context.  Profiler rows:
+ * scene_bands_hist, scene_bands_apply. */
+int srh_scene_bands_hist(srh_ctx* ctx, const void* src, int src_dtype, int64_t n_pixels, int C, const int32_t* select,
+                         const uint8_t* valid, uint32_t* hist, void* stream);
+int srh_scene_bands_apply(srh_ctx* ctx, const void* src, int src_dtype, int64_t n_pixels, int C, const int32_t* select,
+                          const uint8_t* lut, uint8_t* dst, void* stream);
 
 /* op level (used by the parity tests to localise a failure; same kernels as above) ----------------- */
 

@@ -10,7 +10,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # SRH_LIB_PATH: load another build of the same library (A/B measurements of kernel changes); still no CPU fallback
 LIB_PATH = os.environ.get("SRH_LIB_PATH") or os.path.join(_HERE, "libsamroad_hip.so")
 
-SRH_F32, SRH_F16, SRH_U8, SRH_I32, SRH_I64 = 0, 1, 2, 3, 4
+SRH_F32, SRH_F16, SRH_U8, SRH_I32, SRH_I64, SRH_U16 = 0, 1, 2, 3, 4, 5
 ABI_VERSION = 11
 SRH_GEMM_A_BLOCKED16, SRH_GEMM_OUT_BLOCKED16 = 1, 2       # srh_op_gemm_ex flags (include/samroad_hip.h)
 SRH_PAD_MODES = {"reflect": 0, "edge": 1, "constant": 2}  # srh_scene_pad modes (SRH_PAD_*)
@@ -75,6 +75,8 @@ SYMBOLS = {
     "srh_scene_pad": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P]),
     "srh_scene_group_pack": (_I, [_P, _P, C.c_int64, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P]),
     "srh_scene_group_crop": (_I, [_P, _P, _P, _I, _I, _P, _P, _I, _P, _P, C.c_int64, _P]),
+    "srh_scene_bands_hist": (_I, [_P, _P, _I, C.c_int64, _I, _P, _P, _P, _P]),
+    "srh_scene_bands_apply": (_I, [_P, _P, _I, C.c_int64, _I, _P, _P, _P, _P]),
     "srh_op_patch_im2col": (_I, [_P, _P, _I, _I, _P, _I, _I, _I, _P, _P]),
     "srh_op_scores_unorient": (_I, [_P, _P, _I, _I, _I, _P, _P]),
     "srh_op_gemm": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P]),

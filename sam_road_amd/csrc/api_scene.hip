@@ -215,3 +215,42 @@ extern "C" int srh_scene_group_crop(srh_ctx* c, const uint8_t* kp, const uint8_t
     TRYK(c, "scene_group_crop", 0, 4.0 * (double)out_bytes, s, launch_scene_group_crop(a, b, s));
     return 0;
 }
+
+// ---- scene level, 16-bit and multi-band scenes (kernels in scene_bands.hip, behaviour in DESIGN.md §6i) -----------------------------------
+static int scene_bands_params(srh_ctx* c, const char* who, const void* src, int src_dtype, int64_t n_pixels, int C, const int32_t* select,
+                              SceneBandsParams& p) {
+    if (!c || !src || !select) return fail(c, SRH_ERR_BAD_ARG, std::string(who) + ": null argument");
+    if (src_dtype != SRH_U8 && src_dtype != SRH_U16) return fail(c, SRH_ERR_BAD_ARG, std::string(who) + ": the source is SRH_U8 or SRH_U16");
+    if (C < 1 || C > BANDS_MAX_C || n_pixels < 1 || n_pixels > BANDS_MAX_PIXELS)
+        return fail(c, SRH_ERR_BAD_ARG, std::string(who) + ": 1 to 16 bands and 1 to 2^31 - 1 pixels");
+    for (int b = 0; b < 3; ++b)
+        if (select[b] < 0 || select[b] >= C) return fail(c, SRH_ERR_BAD_ARG, std::string(who) + ": a selected band is 0 to C - 1");
+    if (src_dtype == SRH_U16 && (reinterpret_cast<uintptr_t>(src) & 1)) return fail(c, SRH_ERR_BAD_ARG, std::string(who) + ": a u16 source is 2-byte aligned");
+    p.src = src; p.n = (long)n_pixels; p.C = C; p.wide = src_dtype == SRH_U16;
+    for (int b = 0; b < 3; ++b) p.sel[b] = select[b];
+    return 0;
+}
+
+extern "C" int srh_scene_bands_hist(srh_ctx* c, const void* src, int src_dtype, int64_t n_pixels, int C, const int32_t* select,
+                                    const uint8_t* valid, uint32_t* hist, void* stream) {
+    SceneBandsParams p;
+    TRY(scene_bands_params(c, "srh_scene_bands_hist", src, src_dtype, n_pixels, C, select, p));
+    if (!hist || (reinterpret_cast<uintptr_t>(hist) & 3)) return fail(c, SRH_ERR_BAD_ARG, "srh_scene_bands_hist: null or misaligned hist");
+    hipSetDevice(c->device);
+    hipStream_t s = (hipStream_t)stream;
+    p.valid = valid; p.hist = hist;
+    TRYK(c, "scene_bands_hist", 0, (double)n_pixels * (3 * (p.wide ? 2 : 1) + (valid ? 1 : 0)), s, launch_scene_bands_hist(p, s));
+    return 0;
+}
+
+extern "C" int srh_scene_bands_apply(srh_ctx* c, const void* src, int src_dtype, int64_t n_pixels, int C, const int32_t* select,
+                                     const uint8_t* lut, uint8_t* dst, void* stream) {
+    SceneBandsParams p;
+    TRY(scene_bands_params(c, "srh_scene_bands_apply", src, src_dtype, n_pixels, C, select, p));
+    if (!lut || !dst) return fail(c, SRH_ERR_BAD_ARG, "srh_scene_bands_apply: null argument");
+    hipSetDevice(c->device);
+    hipStream_t s = (hipStream_t)stream;
+    p.lut = lut; p.dst = dst;
+    TRYK(c, "scene_bands_apply", 0, (double)n_pixels * (3 * (p.wide ? 2 : 1) + 3), s, launch_scene_bands_apply(p, s));
+    return 0;
+}

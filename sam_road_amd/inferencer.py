@@ -28,6 +28,7 @@ from . import _lib
 from . import distributed as D
 from .graph_points import extract_graph_points
 from .hostcpu import fill_threads, usable_cpus, worker_threads
+from .radiometry import band_luts, fixed_ranges, scene_bands_check, scene_bands_key, scene_bands_override, stretch_from_hist
 from .tiling import get_patch_info_hw, get_patch_info_one_img, patches_per_axis, shard_tiles
 
 
@@ -578,7 +579,8 @@ def neighbor_queries(config):
 
 def _scene_plan(img, config):
     """Validated scene + its tile list (inferencer.py:63-76): (img u8 [H,W,3], infos, tile origins int32 [n,2] (x0, y0)) — under
-    SCENE_PAD infos and origins are those of the padded scene (scene_pad_plan(img.shape, config) says how it is padded).
+    SCENE_PAD infos and origins are those of the padded scene (scene_pad_plan(img.shape, config) says how it is padded); under
+    SCENE_BANDS img is the raw scene, u8 / u16 [H,W,C], checked against the key.
     H and W are independent; the reference's tile rule is applied per axis (tiling.get_patch_info_hw), and
     INFER_PATCHES_PER_EDGE may be an int or [n_y, n_x].  Everything that can be refused is refused here, before the device is
     touched."""
@@ -586,7 +588,10 @@ def _scene_plan(img, config):
     img = np.asarray(img)
     # the reference uses img.shape[0] for both axes (inferencer.py:63,67) and casts whatever it gets to f32: it would mis-stride a
     # non-square scene and silently convert a non-u8 one.  Here H and W are separate all the way down; non-u8 is refused
-    if img.ndim != 3 or img.shape[2] != 3 or img.dtype != np.uint8:
+    bands = scene_bands_key(config)
+    if bands is not None:                                  # SCENE_BANDS: a raw u8 / u16 scene of 1 to 16 bands
+        scene_bands_check(img, bands)
+    elif img.ndim != 3 or img.shape[2] != 3 or img.dtype != np.uint8:
         raise ValueError(f"infer_one_img expects an HxWx3 uint8 scene, got {img.dtype} {tuple(img.shape)}")
     if img.shape[0] < 1 or img.shape[1] < 1:
         raise ValueError(f"infer_one_img expects a scene of at least 1 x 1 pixels, got {tuple(img.shape)}")
@@ -887,7 +892,7 @@ def scene_group_key(config, group=None):
 @dataclasses.dataclass
 class _GroupScene:
     """One scene of a group, planned: everything _pass1_front fixes for a scene before the device is touched."""
-    img: np.ndarray                   # u8 [H,W,3]
+    img: np.ndarray                   # u8 [H,W,3]; under SCENE_BANDS the raw scene, u8 / u16 [H,W,C]
     valid: np.ndarray                 # u8 [H,W], or None
     shape: tuple                      # (H, W)
     pads: tuple                       # (top, bottom, left, right): zeros without SCENE_PAD
@@ -919,12 +924,12 @@ def group_fits(sizes, n_max):
 
 def _scene_groups(imgs, valids, config, n):
     """The scenes of a stream as planned groups, lazily: lists of up to n consecutive _GroupScene.  A group closes at n scenes and before
-    a scene that would take the stack past group_fits; `valids` is read in step with `imgs`.  Every scene is planned (and refused) as it
-    is read."""
+    a scene that would take the stack past group_fits or, under SCENE_BANDS, whose dtype or band count differs (one apply launch serves the
+    group's ragged buffer); `valids` is read in step with `imgs`.  Every scene is planned (and refused) as it is read."""
     group = []
     for img in imgs:
         sc = _plan_group_scene(img, next(valids), config)
-        if group and not group_fits([g.virtual for g in group] + [sc.virtual], n):
+        if group and (not group_fits([g.virtual for g in group] + [sc.virtual], n) or (sc.img.dtype, sc.img.shape[2]) != (group[0].img.dtype, group[0].img.shape[2])):
             yield group
             group = []
         group.append(sc)
@@ -976,9 +981,16 @@ def _group_stack(ctx, io, scenes):
     def stage(name, n):
         return io.alloc(name, (n,), np.uint8) if io.alloc is not None else np.empty(n, np.uint8)
 
-    src = stage("group_scene", int(tables[1, -1, 0] + tables[1, -1, 1] * tables[1, -1, 2]) * 3)
-    for sc, off in zip(scenes, tables[0, :, 0]):
-        src[off:off + sc.img.size] = sc.img.reshape(-1)
+    n_px, raw = int(tables[1, -1, 0] + tables[1, -1, 1] * tables[1, -1, 2]), scenes[0].img
+    if ctx.bands is None:
+        src = stage("group_scene", n_px * 3)
+        for sc, off in zip(scenes, tables[0, :, 0]):
+            src[off:off + sc.img.size] = sc.img.reshape(-1)
+    else:                                              # SCENE_BANDS: the ragged buffer holds the raw pixels, n_px x C elements of one dtype
+        src = stage("group_scene", n_px * raw.shape[2] * raw.itemsize)
+        elems = src.view(raw.dtype)
+        for sc, off in zip(scenes, tables[1, :, 0] * raw.shape[2]):
+            elems[off:off + sc.img.size] = sc.img.reshape(-1)
     ragged = io.upload_packed("group_scene", src)
     tables_d = io.upload("group_tables", tables)
     if any_mask:
@@ -988,6 +1000,8 @@ def _group_stack(ctx, io, scenes):
         mragged = io.upload_packed("group_mask", msrc)
     io.step("upload")
     host = torch.from_numpy(tables)
+    if ctx.bands is not None:                          # one apply launch over the ragged buffer, then the unchanged pack kernel
+        ragged = _scene_bands_front(ctx, io, ragged.view(torch.from_numpy(raw[:0, :0].reshape(0)).dtype).view(n_px, raw.shape[2])).view(-1)
     scene = net.scene_group_pack(ragged, host[0], 3, Ha, Wa, mode, fill, table_dev=tables_d[0])
     valid_d = net.scene_group_pack(mragged, host[2], 1, Ha, Wa, mode, (0, 0, 0), table_dev=tables_d[2]) if any_mask else None
     io.step("pack")
@@ -1092,7 +1106,7 @@ class _Lane:
 class _BlockingIO:
     """How infer_one_img and the tile-sharded loops move a scene's arrays: one blocking copy each way, pageable memory.  The other
     implementation of the same four operations is _LaneIO.  `lap` (a _Laps) names the steps of pass 1 for the profile."""
-    STEPS = {"upload": "scene upload", "pad": "scene pad", "pack": "group pack", "select": "tile selection (count kernel + counts D2H)", "fill": "nodata fill",
+    STEPS = {"upload": "scene upload", "bands": "band select + stretch", "pad": "scene pad", "pack": "group pack", "select": "tile selection (count kernel + counts D2H)", "fill": "nodata fill",
              "pass 1": "pass 1 (GPU)"}
     alloc = None                                       # the pass-2 collate fills plain numpy arrays
 
@@ -1105,8 +1119,9 @@ class _BlockingIO:
 
     upload_packed = upload                             # an array that `alloc` supplied and the collate filled
 
-    def counts(self, fn, after_compute=False):
-        """fn() -> the valid-pixel counts on the device; returns them on the host (int32 [n]) after one wait."""
+    def counts(self, fn, after_compute=False, name="counts"):
+        """fn() -> the valid-pixel counts on the device; returns them on the host (int32 [n]) after one wait.  (SCENE_BANDS fetches its
+        histogram the same way, under a name of its own.)"""
         return fn().cpu().numpy()
 
     def step(self, name):
@@ -1118,7 +1133,7 @@ class _LaneIO:
     """The operations of _BlockingIO on infer_imgs' lane, for ONE scene in flight (`pool`: its page-locked staging): uploads are staged
     and stream-ordered, the counts come back over the copy stream, the pass-2 collate writes straight into the staging buffers.  With the
     profile on, five device events time the scene's pass 1, pass 2 and score download."""
-    STEPS = {"upload": "stage + queue scene upload", "pad": "queue scene pad", "pack": "queue group pack", "select": "tile selection (upload lane)", "pass 1": "queue pass 1"}
+    STEPS = {"upload": "stage + queue scene upload", "bands": "band select + stretch (upload lane)", "pad": "queue scene pad", "pack": "queue group pack", "select": "tile selection (upload lane)", "pass 1": "queue pass 1"}
     EVENTS = {"launch pass 1": 0, "normalised": 1, "pass 2 uploaded": 2, "pass 2 launched": 3, "pass 2 on its way back": 4}
 
     def __init__(self, lane, pool, lap):
@@ -1135,14 +1150,14 @@ class _LaneIO:
     def upload_packed(self, name, arr):
         return self.lane.upload_staged(self.stage[name][:arr.shape[0]])
 
-    def counts(self, fn, after_compute=False):
+    def counts(self, fn, after_compute=False, name="counts"):
         # after_compute: fn reads what the compute stream produced (the padded mask of SCENE_PAD), so the upload lane waits for it first
         if after_compute and self.lane.cuda:
             self.lane.copy_stream.wait_stream(torch.cuda.current_stream(self.lane.device))
         # on the upload lane: the count kernel uses no workspace of the library context, so it and the n int32 on their way back are
         # queued on the copy stream.  Like every upload of this lane they start after what the compute stream holds at this moment (the
         # previous scene's TopoNet work, about a millisecond), and the host waits for the counts
-        return self.lane.on_copy_stream(self.pool, "counts", fn)
+        return self.lane.on_copy_stream(self.pool, name, fn)
 
     def step(self, name):
         if self.t is not None and name in self.EVENTS:
@@ -1162,6 +1177,8 @@ class _SceneSetup:
         dist = sharded and D.is_distributed()
         self.world = torch.distributed.get_world_size() if dist else 1
         self.rank = torch.distributed.get_rank() if dist else 0
+        self.bands = scene_bands_key(config)             # SCENE_BANDS, or None: no scene takes a step of it
+        self.bands_luts = {}                             # levels -> the tables of a fixed range on the device, built once per call
 
     @functools.cached_property
     def features(self):
@@ -1215,6 +1232,8 @@ def _pass1_front(ctx, io, img, valid=None, group=None):
     device of rank 0 — fetching them is the caller's.  SCENE_PAD lives here and nowhere else: the real scene (and mask)
     is uploaded and padded on the device, everything up to the normalise runs on that virtual scene through the same calls, the u8 masks
     are cropped to the real scene before they travel, and the job carries the tiles in the real scene's frame for pass 2.
+    SCENE_BANDS: the raw u8 / u16 [H,W,C] scene is uploaded and converted to the u8 [H,W,3] scene right behind the upload
+    (_scene_bands_front), before the pad and the fill; nothing after that step knows of it.
     group (SCENE_GROUP; img and valid are None then): a planned group, a list of _GroupScene, takes the place of the one
     scene — one ragged upload and one pack launch build the vertical stack of the scenes (each padded by its own pads) and of their masks,
     then the stack IS the scene of the code below, and one crop launch cuts every scene's window out of the stack's masks; the job
@@ -1242,6 +1261,8 @@ def _pass1_front(ctx, io, img, valid=None, group=None):
         if valid is not None:
             valid_d = io.upload("valid_mask", valid)       # a key of its own: "valid" stages pass 2's pair flags
         io.step("upload")
+        if ctx.bands is not None:                          # the raw scene -> the u8 [H,W,3] scene of every line below; the raw one is dropped
+            scene = _scene_bands_front(ctx, io, scene, valid_d if valid is not None else None)
         if pads is not None:
             scene = net.scene_pad(scene, pads, pad[4], pad[5])
             if valid is not None:                          # the mask by the same rule: reflect / edge mirror its validity, constant padding is nodata
@@ -1289,6 +1310,25 @@ def _pass1_front(ctx, io, img, valid=None, group=None):
             job.kp_u8, job.road_u8 = net.scene_group_crop(job.kp_u8, job.road_u8, crop_table, table_dev=crop_table_d), None
     io.step("normalised")
     return job
+
+
+def _scene_bands_front(ctx, io, raw, valid_d=None):
+    """SCENE_BANDS lives here and nowhere else: the raw scene on the device (u8 / u16 [..., C]; a group's ragged buffer
+    [n, C]) -> the u8 [..., 3] scene.  A percentile stretch counts the exact histogram of the selected bands over the valid pixels (before
+    any padding or nodata fill), fetches it the way the tile selection fetches its counts, and reads the ranges off it on the host; the
+    tables are built on the host in float64 (radiometry.py) — once per call for a fixed range — and the device only gathers from them.
+    Every rank of a tile-sharded run holds the scene and the mask, counts the same integers and builds the same tables: no collective."""
+    net, bands = ctx.net, ctx.bands
+    levels = 256 if raw.dtype == torch.uint8 else 65536
+    lut_d = ctx.bands_luts.get(levels)
+    if bands.percentile is not None:
+        hist = io.counts(lambda: net.scene_bands_hist(raw, bands.select, valid_d), name="bands_hist")
+        lut_d = io.upload("bands_lut", band_luts(stretch_from_hist(hist, *bands.percentile), bands.gamma, levels))
+    elif lut_d is None:
+        lut_d = ctx.bands_luts[levels] = io.upload("bands_lut", band_luts(fixed_ranges(bands, levels), bands.gamma, levels))
+    scene = net.scene_bands_apply(raw, bands.select, lut_d)
+    io.step("bands")
+    return scene
 
 
 def _group_children(group, first, kept):
@@ -1401,6 +1441,7 @@ def infer_imgs(net, imgs, config, device=None, tile_sharded=None, pipelined=None
     fuse_window(config)
     tta_plan(config)
     scene_pad_key(config)
+    bands = scene_bands_key(config)
     n_group = scene_group_key(config, group)
     valids = _valid_iter(valids)
     if D.is_distributed() if tile_sharded is None else tile_sharded:
@@ -1415,6 +1456,9 @@ def infer_imgs(net, imgs, config, device=None, tile_sharded=None, pipelined=None
             for img in imgs:
                 yield infer_one_img(net, img, config, device=device, valid=next(valids))
         return
+    if n_group > 1 and bands is not None and bands.percentile is not None:
+        raise ValueError("SCENE_BANDS: a percentile stretch needs every scene's own tables and a host round trip in the middle of a group; "
+                         "with SCENE_GROUP use a fixed stretch range (or run the scenes one by one)")
     ctx = _SceneSetup(net, config, device, sharded=False)
     device, K = ctx.device, ctx.K
     lane = _Lane(device)
@@ -1848,8 +1892,21 @@ def main(argv=None):
                     help="(extension) run up to N consecutive scenes as one — one upload, one pass 1 over all their tiles in full batches, "
                          "one TopoNet launch sequence — overriding the config's SCENE_GROUP; for streams of small scenes (chips).  1: scene "
                          "by scene.  Not with --shard tiles / tiles-pipelined")
+    ap.add_argument("--bands", default=None, metavar="I,J,K",
+                    help="(extension) the three bands of a multi-band scene (.npy, uint8 / uint16 [H,W,C]) that become R, G, B, overriding "
+                         "select of the config's SCENE_BANDS; repeats allowed (0,0,0: a panchromatic scene as grey)")
+    ap.add_argument("--stretch-range", default=None, nargs=2, type=int, metavar=("LO", "HI"),
+                    help="(extension) the input levels that map to 0 and 255, overriding stretch of the config's SCENE_BANDS")
+    ap.add_argument("--stretch-percentile", default=None, nargs=2, type=float, metavar=("PLO", "PHI"),
+                    help="(extension) stretch every selected band between these two percentiles of its valid pixels, per scene "
+                         "(numpy.percentile, method lower), overriding stretch of the config's SCENE_BANDS; not with --scene-group")
+    ap.add_argument("--gamma", default=None, type=float, metavar="G",
+                    help="(extension) gamma of the stretch (out = 255 t^(1/G)), overriding gamma of the config's SCENE_BANDS")
     args = ap.parse_args(argv)
     config = load_config(args.config)
+    if args.bands is not None or args.stretch_range is not None or args.stretch_percentile is not None or args.gamma is not None:
+        config.SCENE_BANDS = scene_bands_override(config, None if args.bands is None else [int(b) for b in args.bands.split(",")],
+                                                  args.stretch_range, args.stretch_percentile, args.gamma)
     if args.scene_group is not None:
         config.SCENE_GROUP = args.scene_group
     if args.scene_pad is not None or args.scene_pad_mode is not None:
@@ -1862,6 +1919,9 @@ def main(argv=None):
     fuse_window(config)                          # and so does a FUSE_WINDOW that cannot be used
     tta_plan(config)                             # and a TTA list that cannot be run
     scene_pad_plan((1, 1), config)               # and a SCENE_PAD (or the NODATA_FILL it uses) that cannot be used
+    bands = scene_bands_key(config)              # and a SCENE_BANDS that cannot be used
+    if bands is not None and bands.percentile is not None and scene_group_key(config) > 1:
+        raise ValueError("SCENE_BANDS: a percentile stretch does not combine with SCENE_GROUP (every scene needs its own tables); use a fixed range")
     if scene_group_key(config) > 1 and args.shard != "scenes" and int(os.environ.get("WORLD_SIZE", "1")) > 1:      # and a SCENE_GROUP
         raise ValueError("SCENE_GROUP applies to --shard scenes (every rank runs whole scenes); a tile-sharded mode runs its scenes one by one")
     device = torch.device("cuda") if args.device == "cuda" else torch.device(args.device)

@@ -702,6 +702,55 @@ class SAMRoad(nn.Module):
                                             out.data_ptr(), self._stream(dev)), "srh_scene_pad")
         return out
 
+    # ---- scene level, 16-bit and multi-band scenes (SCENE_BANDS) ---------------------------------------------------------
+    @staticmethod
+    def _bands_src(src, select):
+        """(dtype code, levels, pixels, C, select as a host int32[3]) of a raw scene [..., C] (uint8 / uint16, contiguous, 1 <= C <= 16)."""
+        import ctypes
+        codes = {torch.uint8: (_lib.SRH_U8, 256), torch.uint16: (_lib.SRH_U16, 65536)}
+        if src.dtype not in codes or src.dim() < 2 or not src.is_contiguous() or not 1 <= src.shape[-1] <= 16 or src.numel() < 1:
+            raise ValueError(f"a raw scene is a contiguous uint8 / uint16 [..., C] tensor with 1 <= C <= 16, got {src.dtype} {tuple(src.shape)}")
+        C = int(src.shape[-1])
+        select = [int(b) for b in select]
+        if len(select) != 3 or not all(0 <= b < C for b in select):
+            raise ValueError(f"select must be three band indices in 0..{C - 1}, got {select!r}")
+        n = src.numel() // C
+        if n > 2 ** 31 - 1:
+            raise ValueError(f"a raw scene has at most 2^31 - 1 pixels, got {n}")
+        return (*codes[src.dtype], n, C, (ctypes.c_int32 * 3)(*select))
+
+    @torch.no_grad()
+    def scene_bands_hist(self, src, select, valid=None):
+        """The exact histogram of the three selected bands (srh_scene_bands_hist): src uint8 / uint16 [..., C] on the GPU (any element-
+        aligned address), select three band indices, valid uint8 / bool with one entry per pixel (non-zero = counted) or None -> uint32
+        [3, levels] on the GPU, levels 256 / 65536 by dtype.  The call uses no workspace of the library context."""
+        dev = src.device
+        ctx, _ = self._weights(dev)
+        code, levels, n, C, sel = self._bands_src(src, select)
+        if valid is not None:
+            if valid.device != dev or valid.dtype not in (torch.uint8, torch.bool) or valid.numel() != n or not valid.is_contiguous():
+                raise ValueError(f"valid must be a contiguous uint8 / bool tensor of {n} pixels on {dev}, got {valid.dtype} {tuple(valid.shape)} on {valid.device}")
+        hist = torch.empty((3, levels), dtype=torch.uint32, device=dev)
+        with torch.cuda.device(dev):
+            ctx.check(ctx.lib.srh_scene_bands_hist(ctx.handle, src.data_ptr(), code, n, C, sel, None if valid is None else valid.data_ptr(),
+                                                   hist.data_ptr(), self._stream(dev)), "srh_scene_bands_hist")
+        return hist
+
+    @torch.no_grad()
+    def scene_bands_apply(self, src, select, lut):
+        """src uint8 / uint16 [..., C] on the GPU -> a NEW uint8 tensor [..., 3]: channel b = lut[b][src[..., select[b]]], lut uint8
+        [3, levels] on the GPU (srh_scene_bands_apply).  The source is not written; it may be any contiguous view."""
+        dev = src.device
+        ctx, _ = self._weights(dev)
+        code, levels, n, C, sel = self._bands_src(src, select)
+        if lut.device != dev or lut.dtype != torch.uint8 or tuple(lut.shape) != (3, levels) or not lut.is_contiguous():
+            raise ValueError(f"lut must be a contiguous uint8 [3, {levels}] tensor on {dev}, got {lut.dtype} {tuple(lut.shape)} on {lut.device}")
+        out = torch.empty(tuple(src.shape[:-1]) + (3,), dtype=torch.uint8, device=dev)
+        with torch.cuda.device(dev):
+            ctx.check(ctx.lib.srh_scene_bands_apply(ctx.handle, src.data_ptr(), code, n, C, sel, lut.data_ptr(), out.data_ptr(),
+                                                    self._stream(dev)), "srh_scene_bands_apply")
+        return out
+
     # ---- scene level, groups of small scenes (SCENE_GROUP, DESIGN.md §6h) -------------------------------------------------------------
     @staticmethod
     def _group_table(table, table_dev, dev):

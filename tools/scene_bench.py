@@ -19,6 +19,10 @@ The final map_decoder bias is lowered so that the random network yields sparse m
                                                                     # infer_imgs with SCENE_GROUP 16: scenes/s, tiles/s, device ms of pass 1 and
                                                                     # pass 2 per group, host ms per scene; --group 1 is the loop without the key
     python tools/scene_bench.py --patch 256 --margin 0 --scene 400 --tiles 4 --scenes 256 --group 16     # the spacenet_4x4 geometry: 16 tiles of 256 px
+    python tools/scene_bench.py --bands 4 uint16 --stretch percentile 2 98    # SCENE_BANDS: the scene arrives as a raw uint16 scene of 4 bands;
+                                                                    # band selection and the stretch run on the device in front of pass 1
+                                                                    # (--stretch range LO HI: a fixed range; default: the whole range).  Adds
+                                                                    # "scene_bands": the new stages and the numpy host step they replace
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 tools/scene_bench.py    # N GPUs:
         tiles sharded over the ranks (RCCL: packed-weight broadcast, banded canvas reduce, point broadcast, vote gather);
         rank 0 prints ms/scene (max over ranks) and the per-rank stage times
@@ -86,6 +90,88 @@ def stream(args, net, cfg, H, W):
                       "edges_per_scene": round(float(np.mean([o[1].shape[0] for o in outs])), 1)}))
 
 
+def bands_front(net, cfg, raw_d, valid_d=None):
+    """The SCENE_BANDS front end as _pass1_front runs it, from the resident raw scene: [histogram -> host -> ranges ->] tables -> upload -> apply."""
+    from sam_road_amd import radiometry as R
+    key = R.scene_bands_key(cfg)
+    levels = 256 if raw_d.dtype == torch.uint8 else 65536
+    if key.percentile is not None:
+        ranges = R.stretch_from_hist(net.scene_bands_hist(raw_d, key.select, valid_d).cpu().numpy(), *key.percentile)
+    else:
+        ranges = R.fixed_ranges(key, levels)
+    return net.scene_bands_apply(raw_d, key.select, torch.from_numpy(R.band_luts(ranges, key.gamma, levels)).to(raw_d.device))
+
+
+def bands_scene(args, net, cfg, img, dev, rng, iters=20):
+    """--bands C DTYPE [--stretch ...]: sets cfg.SCENE_BANDS and returns (the raw scene, the report): device ms of the two kernels alone
+    (events around `iters` launches after a warm-up) with the bytes they must move, host ms of the whole front end (with the percentile's
+    round trip and the table build) and of the numpy step it replaces (np.percentile per band + rescale + cast), both on this box."""
+    from sam_road_amd import radiometry as R
+    C, dt = int(args.bands[0]), np.dtype(args.bands[1])
+    if dt not in R.LEVELS or not 1 <= C <= R.MAX_BANDS:
+        raise SystemExit("--bands takes C in 1..16 and uint8 or uint16")
+    levels, (H, W) = R.LEVELS[dt], img.shape[:2]
+    raw = rng.integers(0, levels, size=(H, W, C), dtype=dt)
+    for b in range(min(3, C)):
+        raw[..., b] = img[..., b].astype(dt) * (257 if levels > 256 else 1)
+    key = {"select": [min(b, C - 1) for b in range(3)]}
+    if args.stretch is not None:
+        kind, a, b = args.stretch
+        if kind not in ("range", "percentile"):
+            raise SystemExit("--stretch takes 'range LO HI' or 'percentile PLO PHI'")
+        key["stretch"] = [int(a), int(b)] if kind == "range" else {"percentile": [float(a), float(b)]}
+    cfg.SCENE_BANDS = key
+    k = R.scene_bands_key(cfg)
+    raw_d = torch.from_numpy(raw).to(dev)
+    lut_d = torch.from_numpy(R.band_luts(R.fixed_ranges(k, levels) if k.percentile is None else [(0, levels - 1)] * 3, k.gamma, levels)).to(dev)
+
+    def device_ms(fn):
+        fn()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        e0.record()
+        for _ in range(iters):
+            fn()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) / iters
+
+    def wall_ms(fn, n=5):
+        fn()
+        ts = []
+        for _ in range(n):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            ts.append(1e3 * (time.perf_counter() - t0))
+        return float(np.median(ts))
+
+    def numpy_step():
+        out = np.empty((H, W, 3), np.uint8)
+        for j, b in enumerate(k.select):
+            x = raw[..., b]
+            lo, hi = np.percentile(x, list(k.percentile)) if k.percentile is not None else R.fixed_ranges(k, levels)[j]
+            t = np.clip((x.astype(np.float32) - lo) / max(float(hi - lo), 1.0), 0.0, 1.0)
+            out[..., j] = (255.0 * (t if k.gamma == 1.0 else t ** (1.0 / k.gamma)) + 0.5).astype(np.uint8)
+        return out
+
+    e = dt.itemsize
+    ms_hist = device_ms(lambda: net.scene_bands_hist(raw_d, k.select))
+    const_d = torch.full_like(raw_d, levels // 3)
+    ms_hist_const = device_ms(lambda: net.scene_bands_hist(const_d, k.select))
+    del const_d
+    ms_apply = device_ms(lambda: net.scene_bands_apply(raw_d, k.select, lut_d))
+    gbs = lambda nbytes, ms: round(nbytes / ms * 1e-6, 1)
+    report = {"bands": C, "dtype": dt.name, "key": key,
+              "hist_ms": round(ms_hist, 4), "hist_ms_all_one_value": round(ms_hist_const, 4), "hist_must_read_bytes": 3 * e * H * W,
+              "hist_GBps_of_must_read": gbs(3 * e * H * W, ms_hist),
+              "apply_ms": round(ms_apply, 4), "apply_must_move_bytes": (3 * e + 3) * H * W, "apply_GBps_of_must_move": gbs((3 * e + 3) * H * W, ms_apply),
+              "front_end_wall_ms": round(wall_ms(lambda: bands_front(net, cfg, raw_d)), 3),
+              "numpy_host_step_wall_ms": round(wall_ms(numpy_step, 3), 2)}
+    return raw, report
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--bias", type=float, default=-2.2)
@@ -104,6 +190,10 @@ def main():
                     help="SCENE_PAD: pad the scene by B px on every side on the device (default: the key is absent)")
     ap.add_argument("--scene-pad-mode", default=None, metavar="MODE", choices=("reflect", "edge", "constant"),
                     help="SCENE_PAD's mode (default reflect)")
+    ap.add_argument("--bands", nargs=2, default=None, metavar=("C", "DTYPE"),
+                    help="SCENE_BANDS: the scene is a raw C-band scene of DTYPE uint8 / uint16 (bands 0..2 hold the synthetic RGB, the rest noise)")
+    ap.add_argument("--stretch", nargs=3, default=None, metavar=("KIND", "A", "B"),
+                    help="with --bands: 'range LO HI' (ints) or 'percentile PLO PHI' (default: the whole range of the dtype)")
     ap.add_argument("--no-pipelined", action="store_true", help="skip the infer_imgs runs (12- and 48-scene streams)")
     ap.add_argument("--patch", type=int, default=512, metavar="P", help="PATCH_SIZE (default 512)")
     ap.add_argument("--margin", type=int, default=64, metavar="M", help="SAMPLE_MARGIN (default 64)")
@@ -165,6 +255,13 @@ def main():
     coarse = rng.integers(0, 256, size=(H // 8, W // 8, 3)).astype(np.float32)
     img = np.kron(coarse, np.ones((8, 8, 1), np.float32)).astype(np.uint8)
 
+    bands_report = None
+    if args.bands is not None:
+        if args.scenes is not None:
+            ap.error("--bands times one scene (not with --scenes)")
+        img, bands_report = bands_scene(args, net, cfg, img, dev, rng)
+    elif args.stretch is not None:
+        ap.error("--stretch goes with --bands")
     if args.scenes is not None:
         if world > 1 or args.scenes < 1 or args.group < 1:
             ap.error("--scenes M --group N take M, N >= 1 and one GPU")
@@ -196,8 +293,10 @@ def main():
 
     def pass1():              # this rank's share of the tiles (no collective: tile throughput)
         sc, vd = scene, valid_d
+        if bands_report is not None:   # from the resident RAW scene: histogram + round trip (percentile), tables, apply are part of every pass 1
+            sc = bands_front(net, cfg, scene, valid_d)
         if pads is not None:       # from the resident real scene: the pad is part of every pass 1
-            sc = net.scene_pad(scene, pads, pad[4], pad[5])
+            sc = net.scene_pad(sc, pads, pad[4], pad[5])
             vd = None if valid_d is None else net.scene_pad(valid_d, pads, pad[4], (0, 0, 0))
         if vd is not None:         # the masked pass 1 from the resident scene: count, fill (of a copy), kept tiles, masked normalise
             net.scene_tile_valid(vd, torch.as_tensor(_scene_plan(img, cfg)[2]).to(dev)).cpu()
@@ -279,6 +378,7 @@ def main():
                       "fuse_window": args.fuse_window or "uniform",
                       "tta": tta_names,
                       "scene_pad": None if pad is None else {"pads": list(pad[:4]), "mode": pad[4]},
+                      "scene_bands": bands_report,
                       "valid_frac": None if valid is None else round(float(valid.mean()), 4), "tiles_kept": len(infos), "tiles_all": n_all,
                       "ms_weight_share": round(1e3 * t_w, 2) if world > 1 else None, "per_rank": per_rank,
                       "infer_batch_size": args.batch, "ms_per_scene_pass1": round(1e3 * p1, 2),
