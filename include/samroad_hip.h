@@ -298,6 +298,29 @@ int srh_scene_bands_hist(srh_ctx* ctx, const void* src, int src_dtype, int64_t n
 int srh_scene_bands_apply(srh_ctx* ctx, const void* src, int src_dtype, int64_t n_pixels, int C, const int32_t* select,
                           const uint8_t* lut, uint8_t* dst, void* stream);
 
+/* Scenes at another ground resolution (config key SCENE_SCALE; an extension): the scene is resampled on the device in
+ * front of pass 1 and the masks are resampled back behind it.  One additive entry; the ABI number stays 11 because nothing existing
+ * changes, and a run without the key does not call it.
+ *
+ * srh_scene_resample: dst u8 [Ho, Wo, C] from src u8 [H, W, C] (both on the device, dense rows, any byte address, not overlapping), C = 3
+ *   (a scene) or 1 (a mask).  Each axis has a table on the device: start int32 [n_out] and weights u8 [n_out, T] whose rows sum to D; tap
+ *   t of output j reads input clamp(start[j] + t, 0, n_in - 1).  The tables state the rule (sam_road_amd/resample.py builds them: area
+ *   averaging down, bilinear up); the entry evaluates them exactly, in integers:
+ *     mode 0: dst = (sum_y sum_x wy wx src + (Dy Dx) / 2) / (Dy Dx) per channel — one rounding;
+ *     mode 1: src is a validity mask and dst = 1 iff every tap whose weights are non-zero on both axes is non-zero, else 0.
+ *   zero_where: u8 [Ho, Wo] on the device or NULL; where it is 0, dst is 0.  The source is not written, every byte of dst is written
+ *   exactly once and nothing else is.  Every tap index is clamped where it is used, so no table content leads outside src.
+ *   block_h x block_w: the outputs one workgroup produces (1..256 each).  win_h x win_w: the source window, in rows and pixels, it may
+ *   stage in LDS for the separable form of mode 0 — win_h * (round16(win_w C + 15) + 2 block_w C) bytes, at most 64 KiB; a block
+ *   whose taps span more, and every block of mode 1, gathers each output's taps from src instead (the same bytes).  0 x 0: no LDS at
+ *   all (the direct form).
+ *   SRH_ERR_BAD_ARG, and nothing is launched, unless the pointers (zero_where excepted) are non-null, C is 1 or 3, mode 0 or 1, H, W,
+ *   Ho, Wo >= 1 with H * W and Ho * Wo <= 2^31 - 1, 1 <= Ty, Tx <= 32, 1 <= Dy, Dx <= 32 and the block / window are as above.  The call
+ *   touches no workspace of the context.  Profiler row: scene_resample. */
+int srh_scene_resample(srh_ctx* ctx, const uint8_t* src, int H, int W, int C, uint8_t* dst, int Ho, int Wo, const int32_t* start_y,
+                       const uint8_t* weights_y, int Ty, int Dy, const int32_t* start_x, const uint8_t* weights_x, int Tx, int Dx, int mode,
+                       const uint8_t* zero_where, int block_h, int block_w, int win_h, int win_w, void* stream);
+
 /* op level (used by the parity tests to localise a failure; same kernels as above) ----------------- */
 
 /* out = act(A[M,K] W[N,K]^T + bias) (+resid); A,W fp16; N%128==0, K%64==0. act: 0/1 GELU/2 ReLU. */

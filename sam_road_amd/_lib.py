@@ -77,6 +77,7 @@ SYMBOLS = {
     "srh_scene_group_crop": (_I, [_P, _P, _P, _I, _I, _P, _P, _I, _P, _P, C.c_int64, _P]),
     "srh_scene_bands_hist": (_I, [_P, _P, _I, C.c_int64, _I, _P, _P, _P, _P]),
     "srh_scene_bands_apply": (_I, [_P, _P, _I, C.c_int64, _I, _P, _P, _P, _P]),
+    "srh_scene_resample": (_I, [_P, _P, _I, _I, _I, _P, _I, _I, _P, _P, _I, _I, _P, _P, _I, _I, _I, _P, _I, _I, _I, _I, _P]),
     "srh_op_patch_im2col": (_I, [_P, _P, _I, _I, _P, _I, _I, _I, _P, _P]),
     "srh_op_scores_unorient": (_I, [_P, _P, _I, _I, _I, _P, _P]),
     "srh_op_gemm": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P]),
@@ -154,6 +155,7 @@ class Context:
                            "(no MI355X visible? there is no CPU fallback)")
         self.handle = h
         self.device_index = int(device_index)
+        self.resample_tables = {}          # SCENE_SCALE: (n_in, n_out, p, q) -> one axis' tap tables on the device (model.scene_resample)
 
     @classmethod
     def get(cls, device_index):

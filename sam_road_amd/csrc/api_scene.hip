@@ -254,3 +254,23 @@ extern "C" int srh_scene_bands_apply(srh_ctx* c, const void* src, int src_dtype,
     TRYK(c, "scene_bands_apply", 0, (double)n_pixels * (3 * (p.wide ? 2 : 1) + 3), s, launch_scene_bands_apply(p, s));
     return 0;
 }
+
+// ---- scene level, another ground resolution (kernel in scene_scale.hip, behaviour in DESIGN.md §6j) ---------------------------------------
+extern "C" int srh_scene_resample(srh_ctx* c, const uint8_t* src, int H, int W, int C, uint8_t* dst, int Ho, int Wo, const int32_t* start_y,
+                                  const uint8_t* weights_y, int Ty, int Dy, const int32_t* start_x, const uint8_t* weights_x, int Tx, int Dx,
+                                  int mode, const uint8_t* zero_where, int block_h, int block_w, int win_h, int win_w, void* stream) {
+    if (!c || !src || !dst || !start_y || !weights_y || !start_x || !weights_x) return fail(c, SRH_ERR_BAD_ARG, "srh_scene_resample: null argument");
+    if ((C != 1 && C != 3) || (mode != SCALE_SUM && mode != SCALE_VALID)) return fail(c, SRH_ERR_BAD_ARG, "srh_scene_resample: bad channel count or mode");
+    if (H < 1 || W < 1 || Ho < 1 || Wo < 1 || !scene_dims_ok(H, W) || !scene_dims_ok(Ho, Wo)) return fail(c, SRH_ERR_BAD_ARG, "srh_scene_resample: bad sizes");
+    if (Ty < 1 || Tx < 1 || Ty > SCALE_MAX_T || Tx > SCALE_MAX_T || Dy < 1 || Dx < 1 || Dy > SCALE_MAX_D || Dx > SCALE_MAX_D)
+        return fail(c, SRH_ERR_BAD_ARG, "srh_scene_resample: 1 to 32 taps per axis and weight sums 1 to 32");
+    SceneScaleParams p;
+    p.src = src; p.dst = dst; p.zero_where = zero_where; p.sy = start_y; p.wy = weights_y; p.sx = start_x; p.wx = weights_x;
+    p.H = H; p.W = W; p.Ho = Ho; p.Wo = Wo; p.C = C; p.Ty = Ty; p.Tx = Tx; p.Dy = Dy; p.Dx = Dx; p.mode = mode;
+    p.bh = block_h; p.bw = block_w; p.win_h = win_h; p.win_w = win_w; p.magic = scale_magic(Dy * Dx);
+    if (!scale_params_ok(p)) return fail(c, SRH_ERR_BAD_ARG, "srh_scene_resample: bad block or window (1..256 outputs per axis, at most 64 KiB of LDS)");
+    hipSetDevice(c->device);
+    hipStream_t s = (hipStream_t)stream;
+    TRYK(c, "scene_resample", 0, ((double)H * W + (double)Ho * Wo) * C, s, launch_scene_resample(p, s));
+    return 0;
+}

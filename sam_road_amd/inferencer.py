@@ -28,6 +28,7 @@ from . import _lib
 from . import distributed as D
 from .graph_points import extract_graph_points
 from .hostcpu import fill_threads, usable_cpus, worker_threads
+from .resample import map_nodes, model_shape, scene_scale_key, scene_scale_override
 from .radiometry import band_luts, fixed_ranges, scene_bands_check, scene_bands_key, scene_bands_override, stretch_from_hist
 from .tiling import get_patch_info_hw, get_patch_info_one_img, patches_per_axis, shard_tiles
 
@@ -559,7 +560,9 @@ def infer_one_img(net, img, config, device=None, valid=None):
     garbage collector and numpy's huge-page madvise paused for the duration of the call, see _host_quiet).
     valid (extension; bool or uint8 [H,W], non-zero = valid pixel; None = every pixel): only tiles that hold enough valid pixels are
     run (config.MIN_VALID_FRACTION), nodata pixels are replaced by config.NODATA_FILL on the device copy of the scene, and both masks
-    are 0 on nodata, so no graph point lies there.  An all-true mask gives the result of valid=None bit for bit."""
+    are 0 on nodata, so no graph point lies there.  An all-true mask gives the result of valid=None bit for bit.
+    config.SCENE_SCALE (extension): img (and valid) are at another ground resolution than the model's; both passes run on
+    the scene resampled on the device, and the masks [H,W] and the nodes (row, col) come back in the scene's own pixels."""
     with _host_quiet():
         return _infer_one_img(net, img, config, device, valid)
 
@@ -580,7 +583,9 @@ def neighbor_queries(config):
 def _scene_plan(img, config):
     """Validated scene + its tile list (inferencer.py:63-76): (img u8 [H,W,3], infos, tile origins int32 [n,2] (x0, y0)) — under
     SCENE_PAD infos and origins are those of the padded scene (scene_pad_plan(img.shape, config) says how it is padded); under
-    SCENE_BANDS img is the raw scene, u8 / u16 [H,W,C], checked against the key.
+    SCENE_BANDS img is the raw scene, u8 / u16 [H,W,C], checked against the key; under SCENE_SCALE the pads and the tiles are
+    those of the MODEL frame, ceil(H p / q) x ceil(W p / q), and its size is what the limits apply to (the scene itself stays within 2^31 - 1
+    pixels).
     H and W are independent; the reference's tile rule is applied per axis (tiling.get_patch_info_hw), and
     INFER_PATCHES_PER_EDGE may be an int or [n_y, n_x].  Everything that can be refused is refused here, before the device is
     touched."""
@@ -595,11 +600,21 @@ def _scene_plan(img, config):
         raise ValueError(f"infer_one_img expects an HxWx3 uint8 scene, got {img.dtype} {tuple(img.shape)}")
     if img.shape[0] < 1 or img.shape[1] < 1:
         raise ValueError(f"infer_one_img expects a scene of at least 1 x 1 pixels, got {tuple(img.shape)}")
-    pad = scene_pad_plan(img.shape, config)
+    Hm, Wm = _model_frame(img.shape, scene_scale_key(config))
+    pad = scene_pad_plan((Hm, Wm), config)
     top, bottom, left, right = pad[:4] if pad is not None else (0, 0, 0, 0)
     # SCENE_PAD: the tiles are planned on the virtual (padded) scene; infos / origins are in ITS frame
-    infos, all_xy = _tile_plan(int(img.shape[0]) + top + bottom, int(img.shape[1]) + left + right, config, padded=pad is not None)
+    infos, all_xy = _tile_plan(Hm + top + bottom, Wm + left + right, config, padded=pad is not None)
     return img, infos, all_xy
+
+
+def _model_frame(shape, scale):
+    """(H, W) of the frame pass 1 runs in: the scene's own without SCENE_SCALE, else ceil(H p / q) x ceil(W p / q) — and the scene itself
+    must stay within the 2^31 - 1 pixels the resample entry takes."""
+    H, W = int(shape[0]), int(shape[1])
+    if scale is not None and H * W > 2 ** 31 - 1:
+        raise ValueError(f"scene {H} x {W} has more than 2^31 - 1 pixels")
+    return model_shape((H, W), scale)
 
 
 def _tile_plan(H, W, config, stacklevel=3, padded=False):
@@ -735,7 +750,9 @@ def scene_tiles(shape, config, valid=None, net=None):
     counts come from `net.scene_tile_valid` on the model's device, so `net` is required then (there is no host fallback).  The list is
     a TilePlan: its `orientations` are the names of config.TTA (['id'] without the key) — every tile of the list runs once per name.
     Under config.SCENE_PAD the tiles are those of the padded scene in the frame of the REAL one — origin (x0 - left, y0 - top), so a tile
-    may start below 0 or overhang — and `pads` holds (top, bottom, left, right); the mask is padded like the scene before it is counted."""
+    may start below 0 or overhang — and `pads` holds (top, bottom, left, right); the mask is padded like the scene before it is counted.
+    Under config.SCENE_SCALE the plan is that of the MODEL frame: `scale` holds (p, q) ((1, 1) without the key), `model_shape` the frame's
+    (H, W), the tiles, the pads and the size limits refer to it, and the mask is resampled by the validity rule before it is counted."""
     neighbor_queries(config)
     if len(shape) not in (2, 3) or (len(shape) == 3 and shape[2] != 3):
         raise ValueError(f"shape must be (H, W) or (H, W, 3), got {tuple(shape)}")
@@ -743,20 +760,24 @@ def scene_tiles(shape, config, valid=None, net=None):
     orientations = tta_plan(config)[0]
     if H < 1 or W < 1:
         raise ValueError(f"a scene has at least 1 x 1 pixels, got shape {tuple(shape)}")
-    pad = scene_pad_plan((H, W), config)
+    scale = scene_scale_key(config)
+    Hm, Wm = _model_frame((H, W), scale)
+    pad = scene_pad_plan((Hm, Wm), config)
     pads = pad[:4] if pad is not None else (0, 0, 0, 0)
-    infos, all_xy = _tile_plan(H + pads[0] + pads[1], W + pads[2] + pads[3], config, padded=pad is not None)
+    infos, all_xy = _tile_plan(Hm + pads[0] + pads[1], Wm + pads[2] + pads[3], config, padded=pad is not None)
     if valid is None:
-        return TilePlan(_shift_infos(infos, pads), orientations, pads)
+        return TilePlan(_shift_infos(infos, pads), orientations, pads, scale, (Hm, Wm))
     v8, frac, _ = _valid_plan(valid, (H, W), config)
     if net is None:
         raise ValueError("scene_tiles needs the model (net=) to count valid pixels on the device")
     device = next(net.parameters()).device
     valid_d = torch.from_numpy(v8).to(device)
+    if scale is not None:
+        valid_d = net.scene_resample(valid_d, *scale, valid_rule=True)
     if any(pads):
         valid_d = net.scene_pad(valid_d, pads, pad[4], (0, 0, 0))
     counts = net.scene_tile_valid(valid_d, torch.as_tensor(all_xy).to(device)).cpu().numpy()
-    return TilePlan(_shift_infos([infos[i] for i in select_tiles(counts, config.PATCH_SIZE, frac)], pads), orientations, pads)
+    return TilePlan(_shift_infos([infos[i] for i in select_tiles(counts, config.PATCH_SIZE, frac)], pads), orientations, pads, scale, (Hm, Wm))
 
 
 def _shift_infos(infos, pads):
@@ -1009,13 +1030,16 @@ def _group_stack(ctx, io, scenes):
 
 
 class TilePlan(list):
-    """What scene_tiles returns: the list of tiles, in `orientations` the names every one of them is run in, and in `pads` the (top, bottom,
-    left, right) of SCENE_PAD (zeros without it)."""
+    """What scene_tiles returns: the list of tiles, in `orientations` the names every one of them is run in, in `pads` the (top, bottom,
+    left, right) of SCENE_PAD (zeros without it), in `scale` the (p, q) of SCENE_SCALE ((1, 1) without it) and in `model_shape` the (H, W)
+    of the frame the tiles lie in (None: the scene's own)."""
 
-    def __init__(self, infos, orientations, pads=(0, 0, 0, 0)):
+    def __init__(self, infos, orientations, pads=(0, 0, 0, 0), scale=None, model_shape=None):
         super().__init__(infos)
         self.orientations = list(orientations)
         self.pads = tuple(int(v) for v in pads)
+        self.scale = (1, 1) if scale is None else (int(scale[0]), int(scale[1]))
+        self.model_shape = None if model_shape is None else (int(model_shape[0]), int(model_shape[1]))
 
 
 def _empty_result(H, W):
@@ -1106,7 +1130,7 @@ class _Lane:
 class _BlockingIO:
     """How infer_one_img and the tile-sharded loops move a scene's arrays: one blocking copy each way, pageable memory.  The other
     implementation of the same four operations is _LaneIO.  `lap` (a _Laps) names the steps of pass 1 for the profile."""
-    STEPS = {"upload": "scene upload", "bands": "band select + stretch", "pad": "scene pad", "pack": "group pack", "select": "tile selection (count kernel + counts D2H)", "fill": "nodata fill",
+    STEPS = {"upload": "scene upload", "bands": "band select + stretch", "scale": "scene resample", "pad": "scene pad", "pack": "group pack", "select": "tile selection (count kernel + counts D2H)", "fill": "nodata fill",
              "pass 1": "pass 1 (GPU)"}
     alloc = None                                       # the pass-2 collate fills plain numpy arrays
 
@@ -1133,7 +1157,7 @@ class _LaneIO:
     """The operations of _BlockingIO on infer_imgs' lane, for ONE scene in flight (`pool`: its page-locked staging): uploads are staged
     and stream-ordered, the counts come back over the copy stream, the pass-2 collate writes straight into the staging buffers.  With the
     profile on, five device events time the scene's pass 1, pass 2 and score download."""
-    STEPS = {"upload": "stage + queue scene upload", "bands": "band select + stretch (upload lane)", "pad": "queue scene pad", "pack": "queue group pack", "select": "tile selection (upload lane)", "pass 1": "queue pass 1"}
+    STEPS = {"upload": "stage + queue scene upload", "bands": "band select + stretch (upload lane)", "scale": "queue scene resample", "pad": "queue scene pad", "pack": "queue group pack", "select": "tile selection (upload lane)", "pass 1": "queue pass 1"}
     EVENTS = {"launch pass 1": 0, "normalised": 1, "pass 2 uploaded": 2, "pass 2 launched": 3, "pass 2 on its way back": 4}
 
     def __init__(self, lane, pool, lap):
@@ -1179,6 +1203,7 @@ class _SceneSetup:
         self.rank = torch.distributed.get_rank() if dist else 0
         self.bands = scene_bands_key(config)             # SCENE_BANDS, or None: no scene takes a step of it
         self.bands_luts = {}                             # levels -> the tables of a fixed range on the device, built once per call
+        self.scale = scene_scale_key(config)             # SCENE_SCALE as (p, q), or None: no scene takes a step of it
 
     @functools.cached_property
     def features(self):
@@ -1194,8 +1219,9 @@ class _SceneSetup:
 @dataclasses.dataclass
 class _SceneJob:
     """One scene from pass 1 to its result."""
-    shape: tuple                      # (H, W) of the real scene: what the masks and the nodes refer to
-    infos: list                       # the tiles that run (the kept ones under a mask), in the frame of the real scene (SCENE_PAD: shifted)
+    shape: tuple                      # (H, W) of the real scene: what the masks and the nodes the caller gets refer to
+    infos: list                       # the tiles that run (the kept ones under a mask), in the frame of the real scene (SCENE_PAD: shifted;
+                                      # SCENE_SCALE: of the model frame, in which pass 2 runs)
     all_xy: np.ndarray                # their origins int32 [n,2] (x0, y0) on the canvases (SCENE_PAD: the virtual scene)
     pads: tuple = (0, 0, 0, 0)        # SCENE_PAD's (top, bottom, left, right): the canvases are shape + pads
     empty: bool = False               # a mask kept no tile: nothing was launched and the fields below stay as they are
@@ -1223,17 +1249,28 @@ class _SceneJob:
     group: list = None
     mask_off: int = 0
     row0: int = 0                     # first query row of a child in the group's one ragged pass 2
+    # SCENE_SCALE: the scene carries two frames.  kp_u8 / road_u8 above are the masks of the scene frame (`shape`), the
+    # ones the caller gets; the model-frame masks travel too, for the unchanged point extraction, and the nodes are mapped at the end
+    scale: tuple = None               # (p, q), or None: one frame, nothing below is used
+    model_shape: tuple = None         # (H, W) of the model frame (None: `shape`)
+    model_kp_u8: torch.Tensor = None  # the model-frame masks on the device (rank 0), then on their way to the host
+    model_road_u8: torch.Tensor = None
+    model_masks: list = None
 
 
 def _pass1_front(ctx, io, img, valid=None, group=None):
-    """Pass 1 of one scene, queued (GPU): plan, upload, [border padding,] [tile selection, nodata fill,] crop -> encoder -> decoder ->
-    fused canvases, [canvas reduce,] normalise[, masks cropped back].  `io` decides how arrays travel and when the host waits
+    """Pass 1 of one scene, queued (GPU): plan, upload, [band step,] [resample,] [border padding,] [tile selection, nodata fill,] crop ->
+    encoder -> decoder -> fused canvases, [canvas reduce,] normalise[, masks cropped back][, masks resampled back].  `io` decides how arrays travel and when the host waits
     (_BlockingIO / _LaneIO); everything else is the same for every loop.  Returns the _SceneJob: embeddings resident, the u8 masks on the
     device of rank 0 — fetching them is the caller's.  SCENE_PAD lives here and nowhere else: the real scene (and mask)
     is uploaded and padded on the device, everything up to the normalise runs on that virtual scene through the same calls, the u8 masks
     are cropped to the real scene before they travel, and the job carries the tiles in the real scene's frame for pass 2.
     SCENE_BANDS: the raw u8 / u16 [H,W,C] scene is uploaded and converted to the u8 [H,W,3] scene right behind the upload
     (_scene_bands_front), before the pad and the fill; nothing after that step knows of it.
+    SCENE_SCALE lives here and nowhere else: right behind the band step the scene is resampled to the model frame by p/q
+    (the mask by the validity rule), everything up to the crop runs in that frame through the same calls, and at the end both masks are
+    resampled back to the scene's own size by q/p, 0 wherever the scene's mask is.  The job carries both pairs of masks (the model-frame
+    ones feed the unchanged point extraction and pass 2) and the tiles in the model frame; the nodes are mapped where the result is formed.
     group (SCENE_GROUP; img and valid are None then): a planned group, a list of _GroupScene, takes the place of the one
     scene — one ragged upload and one pack launch build the vertical stack of the scenes (each padded by its own pads) and of their masks,
     then the stack IS the scene of the code below, and one crop launch cuts every scene's window out of the stack's masks; the job
@@ -1248,13 +1285,15 @@ def _pass1_front(ctx, io, img, valid=None, group=None):
         infos = list(range(all_xy.shape[0]))           # on the stack a tile is known by its index alone
         xy_dev = io.upload("xy", all_xy)
         shape, pads, job_pads = tuple(int(v) for v in scene.shape[:2]), None, (0, 0, 0, 0)
+        scene_shape = shape
     else:
         img, infos, all_xy = _scene_plan(img, config)
-        pad = scene_pad_plan(img.shape, config)
-        shape = tuple(int(v) for v in img.shape[:2])
+        scene_shape = tuple(int(v) for v in img.shape[:2])
+        shape = model_shape(scene_shape, ctx.scale)        # the frame of everything between the two resample steps (no key: the scene's)
+        pad = scene_pad_plan(shape, config)
         pads = pad[:4] if pad is not None and any(pad[:4]) else None     # all four 0: the launches of a run without the key
         if valid is not None:
-            valid, min_frac, fill = _valid_plan(valid, shape, config)
+            valid, min_frac, fill = _valid_plan(valid, scene_shape, config)
         pass1_kw, norm_kw, n_orient = ctx.features
         scene = io.upload("scene", img)                    # the u8 scene, ONCE; tiles are cropped on the device
         xy_dev = io.upload("xy", all_xy)
@@ -1263,6 +1302,11 @@ def _pass1_front(ctx, io, img, valid=None, group=None):
         io.step("upload")
         if ctx.bands is not None:                          # the raw scene -> the u8 [H,W,3] scene of every line below; the raw one is dropped
             scene = _scene_bands_front(ctx, io, scene, valid_d if valid is not None else None)
+        if ctx.scale is not None:                          # the scene -> the model frame; the mask by the validity rule, and the scene-frame
+            scene = net.scene_resample(scene, *ctx.scale)  # one is kept for the way back
+            if valid is not None:
+                valid_scene, valid_d = valid_d, net.scene_resample(valid_d, *ctx.scale, valid_rule=True)
+            io.step("scale")
         if pads is not None:
             scene = net.scene_pad(scene, pads, pad[4], pad[5])
             if valid is not None:                          # the mask by the same rule: reflect / edge mirror its validity, constant padding is nodata
@@ -1272,12 +1316,12 @@ def _pass1_front(ctx, io, img, valid=None, group=None):
     if valid is not None:
         # every rank holds the scene and the mask, computes the same integer counts and therefore the same kept list: from here
         # on infos / all_xy / xy_dev ARE the kept tiles (a subsequence of an x-outer list is x-outer, so the banded reduce stays valid)
-        kept = select_tiles(io.counts(lambda: net.scene_tile_valid(valid_d, xy_dev), after_compute=pads is not None or group is not None),
+        kept = select_tiles(io.counts(lambda: net.scene_tile_valid(valid_d, xy_dev), after_compute=pads is not None or group is not None or ctx.scale is not None),
                             config.PATCH_SIZE, min_frac)
         io.step("select")
         infos, all_xy = [infos[i] for i in kept], np.ascontiguousarray(all_xy[kept])
         if len(kept) == 0:                             # nothing to run: the encoder is not launched and no exchange step is entered
-            job = _SceneJob(shape, _shift_infos(infos, job_pads), all_xy, job_pads, empty=True)
+            job = _SceneJob(scene_shape, _shift_infos(infos, job_pads), all_xy, job_pads, empty=True)
             if group is not None:
                 job.group = _group_children(group, first, infos)
             return job
@@ -1287,7 +1331,9 @@ def _pass1_front(ctx, io, img, valid=None, group=None):
         scene = net.scene_fill_invalid(scene, valid_d, fill)
         io.step("fill")
         norm_kw = dict(valid=valid_d, **norm_kw)
-    job = _SceneJob(shape, _shift_infos(infos, job_pads), all_xy, job_pads)
+    job = _SceneJob(scene_shape, _shift_infos(infos, job_pads), all_xy, job_pads)
+    if group is None and ctx.scale is not None:
+        job.scale, job.model_shape = ctx.scale, shape
     job.lo, job.hi = shard_tiles(len(infos), ctx.world, ctx.rank)
     io.step("launch pass 1")
     # FUSE_WINDOW: every rank weights its own chunk of the kept list.  TTA: every orientation runs that chunk (selection and fill happened
@@ -1305,6 +1351,10 @@ def _pass1_front(ctx, io, img, valid=None, group=None):
         if pads is not None:                           # the real scene's window of the virtual masks, cut out on the device: H * W bytes travel
             (top, _, left, _), (H, W) = pads, shape
             job.kp_u8, job.road_u8 = (m[top:top + H, left:left + W].contiguous() for m in (job.kp_u8, job.road_u8))
+        if job.scale is not None:                      # the way back: both masks to the scene's own size by q/p, 0 on the scene's nodata
+            (p, q), job.model_kp_u8, job.model_road_u8 = job.scale, job.kp_u8, job.road_u8
+            job.kp_u8, job.road_u8 = (net.scene_resample(m, q, p, out_shape=scene_shape, zero_where=valid_scene if valid is not None else None)
+                                      for m in (job.model_kp_u8, job.model_road_u8))
         if group is not None:                          # every scene's window of the stack's masks, one launch, one allocation
             job.group = _group_children(group, first, infos)
             job.kp_u8, job.road_u8 = net.scene_group_crop(job.kp_u8, job.road_u8, crop_table, table_dev=crop_table_d), None
@@ -1347,10 +1397,12 @@ def _group_children(group, first, kept):
     return children
 
 
-def _pass2_sharded(ctx, job, kp_mask, road_mask, stats=None, lap=None):
+def _pass2_sharded(ctx, job, kp_mask, road_mask, stats=None, lap=None, scene_masks=None):
     """From a scene's masks on the host (rank 0; None elsewhere) to its result tuple on rank 0, None on the other ranks: graph points
     (host, rank 0) -> broadcast -> per-tile queries (host) -> sampler + TopoNet (GPU) -> directed edge votes of this rank's tiles ->
-    gather -> edges.  The two exchange steps run in the same order on every rank.  `stats` collects wall times and exchanged bytes."""
+    gather -> edges.  The two exchange steps run in the same order on every rank.  `stats` collects wall times and exchanged bytes.
+    scene_masks (SCENE_SCALE, rank 0): kp_mask / road_mask are the model-frame masks, everything above runs in that frame, and the result
+    carries these scene-frame masks and the nodes mapped to the scene frame (_scene_frame)."""
     import collections
     net, config, device, world, rank = ctx.net, ctx.config, ctx.device, ctx.world, ctx.rank
     stats = stats if stats is not None else collections.defaultdict(float)
@@ -1367,7 +1419,7 @@ def _pass2_sharded(ctx, job, kp_mask, road_mask, stats=None, lap=None):
     graph_points = D.broadcast_points(graph_points, src=0, device=device if world > 1 else None)
     stats["points_bytes"] += 16 * graph_points.shape[0] * ((world - 1) if rank == 0 else 1)     # rank 0: sent to every peer; others: received
     if graph_points.shape[0] == 0:
-        return None if rank != 0 else (graph_points, np.zeros((0, 2), dtype=np.int32), kp_mask, road_mask)
+        return None if rank != 0 else _scene_frame(job, (graph_points, np.zeros((0, 2), dtype=np.int32), kp_mask, road_mask), scene_masks)
     n_pts = graph_points.shape[0]
     if world > 1 and config.EXACT_VOTE_MERGE:
         # exact multi-rank merge (extension key, default off): every raw vote goes to rank 0 in the one-process visiting order
@@ -1393,19 +1445,30 @@ def _pass2_sharded(ctx, job, kp_mask, road_mask, stats=None, lap=None):
     pred_edges = votes_to_edges(uk, sums, cnts, first, n_pts, config.TOPO_THRESHOLD)
     stats["merge_host_ms"] += 1e3 * (time.perf_counter() - t3)
     lap("threshold + edge list")
-    return graph_points[:, ::-1], pred_edges, kp_mask, road_mask      # nodes as (row, col)
+    return _scene_frame(job, (graph_points[:, ::-1], pred_edges, kp_mask, road_mask), scene_masks)      # nodes as (row, col)
+
+
+def _scene_frame(job, result, scene_masks):
+    """A result tuple formed in the model frame as the caller gets it under SCENE_SCALE: the nodes (row, col) mapped by the node rule
+    (resample.map_nodes), the scene-frame masks in place of the model-frame ones; the edges are indices and stay.  No key: untouched."""
+    if job.scale is None:
+        return result
+    nodes, edges, _, _ = result
+    return map_nodes(nodes, job.shape, *job.scale), edges, scene_masks[0], scene_masks[1]
 
 
 def _infer_one_img(net, img, config, device=None, valid=None):
     ctx = _SceneSetup(net, config, device, sharded=True)
     lap = _Laps("infer_one_img", sync=ctx.device)      # tuning aid: wall time of each stage (synchronises the device)
     job = _pass1_front(ctx, _BlockingIO(ctx.device, lap), img, valid)
-    kp_mask = road_mask = None
+    kp_mask = road_mask = scene_masks = None
     if job.kp_u8 is not None:                          # rank 0 of a scene that ran
         kp_mask, road_mask = job.kp_u8.cpu().numpy(), job.road_u8.cpu().numpy()
+        if job.scale is not None:                      # those are the caller's; the points come from the model-frame masks
+            scene_masks, (kp_mask, road_mask) = (kp_mask, road_mask), (job.model_kp_u8.cpu().numpy(), job.model_road_u8.cpu().numpy())
         _poll_finite(net, ctx.device)                  # the masks are on the host, so every LayerNorm pass of pass 1 has reported
         lap("normalise + mask D2H")
-    return _pass2_sharded(ctx, job, kp_mask, road_mask, lap=lap)
+    return _pass2_sharded(ctx, job, kp_mask, road_mask, lap=lap, scene_masks=scene_masks)
 
 
 def _valid_iter(valids):
@@ -1443,6 +1506,8 @@ def infer_imgs(net, imgs, config, device=None, tile_sharded=None, pipelined=None
     scene_pad_key(config)
     bands = scene_bands_key(config)
     n_group = scene_group_key(config, group)
+    if scene_scale_key(config) is not None and n_group > 1:
+        raise ValueError(f"SCENE_SCALE does not combine with SCENE_GROUP = {n_group} (a group's stack holds scenes of one frame): drop one of them")
     valids = _valid_iter(valids)
     if D.is_distributed() if tile_sharded is None else tile_sharded:
         if n_group > 1:
@@ -1473,6 +1538,8 @@ def infer_imgs(net, imgs, config, device=None, tile_sharded=None, pipelined=None
             job.masks = [torch.zeros(job.shape, dtype=torch.uint8) for _ in range(2)] if group is None else None
             return job
         job.masks, job.e1 = lane.download(pool, "mask", [job.kp_u8, job.road_u8] if group is None else [job.kp_u8])
+        if job.scale is not None:                      # the second staged download: the model-frame masks; its event covers both
+            job.model_masks, job.e1 = lane.download(pool, "model_mask", [job.model_kp_u8, job.model_road_u8])
         lap("queue normalise + mask download")
         return job
 
@@ -1480,7 +1547,8 @@ def infer_imgs(net, imgs, config, device=None, tile_sharded=None, pipelined=None
         if job.e1 is not None:
             job.e1.synchronize()
         job.kp_mask, job.road_mask = (m.numpy().copy() for m in job.masks)
-        job.graph_points = extract_graph_points(job.kp_mask, job.road_mask, config)
+        # SCENE_SCALE: the points come from the model-frame masks (read where they were staged: the pool is this scene's until it is done)
+        job.graph_points = extract_graph_points(*((job.kp_mask, job.road_mask) if job.model_masks is None else (m.numpy() for m in job.model_masks)), config)
         lap("extract_graph_points")
         if job.graph_points.shape[0] == 0:
             return
@@ -1500,6 +1568,8 @@ def infer_imgs(net, imgs, config, device=None, tile_sharded=None, pipelined=None
 
     def finish(job):                                   # H2: votes -> edges
         nodes = job.graph_points[:, ::-1]              # (row, col)
+        if job.scale is not None:
+            nodes = map_nodes(nodes, job.shape, *job.scale)
         no_edges = np.zeros((0, 2), dtype=np.int32)
         if job.graph_points.shape[0] == 0:
             return job.graph_points, no_edges, job.kp_mask, job.road_mask
@@ -1723,29 +1793,32 @@ def _infer_imgs_tile_sharded(net, imgs, config, device=None, stats=None, valids=
         if job.bands is not None:
             # this rank's own share: the band it ships to rank 0 (rank 0: what it receives), so that per-rank statistics are per rank
             x0, x1 = job.bands[rank]
-            rows = job.shape[0] + job.pads[0] + job.pads[1]      # a band is a strip of columns of the full canvas HEIGHT
+            rows = (job.model_shape or job.shape)[0] + job.pads[0] + job.pads[1]      # a band is a strip of columns of the full canvas HEIGHT
             stats["canvas_bytes"] += D.canvas_bytes(job.bands, rows) if rank == 0 else 2 * 4 * rows * max(0, x1 - x0)
         if job.kp_u8 is not None:
+            both = [job.kp_u8, job.road_u8] + ([job.model_kp_u8, job.model_road_u8] if job.scale is not None else [])
             if cuda:       # asynchronous download behind the scene's own kernels: the host does not wait here
-                job.masks = [torch.empty(t.shape, dtype=t.dtype, pin_memory=True) for t in (job.kp_u8, job.road_u8)]
-                for h, t in zip(job.masks, (job.kp_u8, job.road_u8)):
+                job.masks = [torch.empty(t.shape, dtype=t.dtype, pin_memory=True) for t in both]
+                for h, t in zip(job.masks, both):
                     h.copy_(t, non_blocking=True)
                 job.e1 = torch.cuda.Event()
                 job.e1.record(torch.cuda.current_stream(device))
             else:
-                job.masks = [job.kp_u8, job.road_u8]
+                job.masks = both
         stats["pass1_queue_ms"] += 1e3 * (time.perf_counter() - t0)
         return job
 
     def stage2(job):
         t0 = time.perf_counter()
-        kp_mask = road_mask = None
+        kp_mask = road_mask = scene_masks = None
         if job.masks is not None:
             if job.e1 is not None:
                 job.e1.synchronize()
-            kp_mask, road_mask = (np.array(m.numpy()) for m in job.masks)
+            kp_mask, road_mask, *model = (np.array(m.numpy()) for m in job.masks)
+            if model:                                  # SCENE_SCALE: the scene-frame masks are the caller's, the points come from the model frame's
+                scene_masks, (kp_mask, road_mask) = (kp_mask, road_mask), model
             stats["points_host_ms"] += 1e3 * (time.perf_counter() - t0)      # the wait for the masks counts as host time of the points
-        return _pass2_sharded(ctx, job, kp_mask, road_mask, stats)
+        return _pass2_sharded(ctx, job, kp_mask, road_mask, stats, scene_masks=scene_masks)
 
     it = iter(imgs)
     img = next(it, None)
@@ -1888,6 +1961,13 @@ def main(argv=None):
     ap.add_argument("--scene-pad-mode", default=None, metavar="MODE", choices=SCENE_PAD_MODES,
                     help="(extension) how the padding is filled, overriding the mode of the config's SCENE_PAD: reflect (default), edge "
                          "or constant (the colour NODATA_FILL)")
+    ap.add_argument("--scene-scale", default=None, nargs=2, type=int, metavar=("P", "Q"),
+                    help="(extension) the scenes' ground resolution as the fraction P/Q, model pixels per scene pixel (a 0.5 m/px scene for a "
+                         "1 m/px model: 1 2), overriding the config's SCENE_SCALE: the scene is resampled on the device in front of pass 1, the "
+                         "masks and the graph come back in the scene's own pixels.  1 <= P, Q <= 16, 1/8 <= P/Q <= 4; not with --scene-group")
+    ap.add_argument("--scene-gsd", default=None, type=float, metavar="A",
+                    help="(extension) the same as metres per scene pixel: the scale is A / B with --model-gsd B, which must be such a fraction")
+    ap.add_argument("--model-gsd", default=None, type=float, metavar="B", help="(extension) metres per pixel the model was trained at (default 1.0)")
     ap.add_argument("--scene-group", default=None, type=int, metavar="N",
                     help="(extension) run up to N consecutive scenes as one — one upload, one pass 1 over all their tiles in full batches, "
                          "one TopoNet launch sequence — overriding the config's SCENE_GROUP; for streams of small scenes (chips).  1: scene "
@@ -1909,6 +1989,8 @@ def main(argv=None):
                                                   args.stretch_range, args.stretch_percentile, args.gamma)
     if args.scene_group is not None:
         config.SCENE_GROUP = args.scene_group
+    if args.scene_scale is not None or args.scene_gsd is not None or args.model_gsd is not None:
+        config.SCENE_SCALE = scene_scale_override(config, args.scene_scale, args.scene_gsd, args.model_gsd)
     if args.scene_pad is not None or args.scene_pad_mode is not None:
         config.SCENE_PAD = scene_pad_override(config, args.scene_pad, args.scene_pad_mode)
     if args.fuse_window is not None:
@@ -1920,6 +2002,7 @@ def main(argv=None):
     tta_plan(config)                             # and a TTA list that cannot be run
     scene_pad_plan((1, 1), config)               # and a SCENE_PAD (or the NODATA_FILL it uses) that cannot be used
     bands = scene_bands_key(config)              # and a SCENE_BANDS that cannot be used
+    scene_scale_key(config)                      # and a SCENE_SCALE that cannot be used (or that meets a SCENE_GROUP)
     if bands is not None and bands.percentile is not None and scene_group_key(config) > 1:
         raise ValueError("SCENE_BANDS: a percentile stretch does not combine with SCENE_GROUP (every scene needs its own tables); use a fixed range")
     if scene_group_key(config) > 1 and args.shard != "scenes" and int(os.environ.get("WORLD_SIZE", "1")) > 1:      # and a SCENE_GROUP

@@ -751,6 +751,56 @@ class SAMRoad(nn.Module):
                                                     self._stream(dev)), "srh_scene_bands_apply")
         return out
 
+    # ---- scene level, another ground resolution (SCENE_SCALE) -----------------------------------------------------------
+    @staticmethod
+    def _resample_tables(ctx, dev, n_in, n_out, p, q):
+        """One axis' tables on the device, (start int32 [n_out], weights uint8 [n_out, T], T, D): built by resample.axis_tables and
+        cached on the library context by (n_in, n_out, p, q)."""
+        from . import resample
+        cache = ctx.resample_tables
+        key = (n_in, n_out, p, q)
+        if key not in cache:
+            if len(cache) >= 64:                       # a stream of scenes of ever new sizes: start over
+                cache.clear()
+            s, w, T, D = resample.axis_tables(n_in, p, q, n_out)
+            cache[key] = (torch.from_numpy(s).to(dev), torch.from_numpy(w).to(dev), T, D)
+        return cache[key]
+
+    @torch.no_grad()
+    def scene_resample(self, t, p, q, out_shape=None, valid_rule=False, zero_where=None, direct=False):
+        """t [H,W,3] (a scene) or [H,W] (a mask; bool allowed) uint8 on the GPU -> a NEW tensor [Ho, Wo(, 3)] of the same dtype, resampled
+        by the fraction p/q (two ints >= 1, p != q) exactly as resample.resample_ref does (srh_scene_resample): area averaging for p < q,
+        bilinear at pixel centres for p > q, one rounding.  out_shape: (Ho, Wo), default (ceil(H p / q), ceil(W p / q)).  valid_rule: t is
+        a validity mask and an output pixel is 1 iff every tap with a non-zero weight is non-zero.  zero_where: uint8 / bool [Ho, Wo] on
+        the GPU; the result is 0 where it is 0.  direct: every output gathers its own taps instead of the separable form through LDS (the
+        same bytes; for measurements).  The source is not written; it may be any contiguous view, at any byte address."""
+        from . import resample
+        dev = t.device
+        ctx, _ = self._weights(dev)
+        if t.dtype not in (torch.uint8, torch.bool) or t.dim() not in (2, 3) or (t.dim() == 3 and t.shape[2] != 3) or not t.is_contiguous():
+            raise ValueError(f"scene_resample takes a contiguous uint8 [H,W,3] or uint8 / bool [H,W] tensor, got {t.dtype} {tuple(t.shape)}")
+        for v in (p, q):
+            if isinstance(v, bool) or not isinstance(v, int) or v < 1:
+                raise ValueError(f"p and q must be ints >= 1, got {p!r} and {q!r}")
+        H, W, ch = int(t.shape[0]), int(t.shape[1]), 3 if t.dim() == 3 else 1
+        Ho, Wo = (resample.out_size(H, p, q), resample.out_size(W, p, q)) if out_shape is None else (int(out_shape[0]), int(out_shape[1]))
+        if p == q or H < 1 or W < 1 or Ho < 1 or Wo < 1 or H * W > 2 ** 31 - 1 or Ho * Wo > 2 ** 31 - 1:
+            raise ValueError(f"scene_resample: p != q and 1 to 2^31 - 1 pixels on both sides, got {p}/{q} for {tuple(t.shape)} -> {(Ho, Wo)}")
+        if zero_where is not None:
+            zero_where = self._valid_u8(zero_where, Ho, Wo, dev)
+        sy, wy, Ty, Dy = self._resample_tables(ctx, dev, H, Ho, p, q)
+        sx, wx, Tx, Dx = self._resample_tables(ctx, dev, W, Wo, p, q)
+        bh, bw, win_h, win_w = resample.block_plan(Ty, Tx, p, q, ch)
+        if direct or valid_rule:
+            win_h = win_w = 0
+        out = torch.empty((Ho, Wo) + tuple(t.shape[2:]), dtype=t.dtype, device=dev)
+        with torch.cuda.device(dev):
+            ctx.check(ctx.lib.srh_scene_resample(ctx.handle, t.data_ptr(), H, W, ch, out.data_ptr(), Ho, Wo, sy.data_ptr(), wy.data_ptr(), Ty, Dy,
+                                                 sx.data_ptr(), wx.data_ptr(), Tx, Dx, 1 if valid_rule else 0,
+                                                 None if zero_where is None else zero_where.data_ptr(), bh, bw, win_h, win_w, self._stream(dev)),
+                      "srh_scene_resample")
+        return out
+
     # ---- scene level, groups of small scenes (SCENE_GROUP, DESIGN.md §6h) -------------------------------------------------------------
     @staticmethod
     def _group_table(table, table_dev, dev):

@@ -23,6 +23,10 @@ The final map_decoder bias is lowered so that the random network yields sparse m
                                                                     # band selection and the stretch run on the device in front of pass 1
                                                                     # (--stretch range LO HI: a fixed range; default: the whole range).  Adds
                                                                     # "scene_bands": the new stages and the numpy host step they replace
+    python tools/scene_bench.py --scene 4096 --tiles 16 --scale 1 2    # SCENE_SCALE: a 4096^2 scene at 0.5 m/px runs in the 2048^2 model frame
+                                                                    # (--tiles counts tiles of the MODEL frame); the resample steps are part of
+                                                                    # every pass 1, and "scene_scale" reports their device time alone, forward
+                                                                    # and back, in the separable LDS form and in the direct form
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 tools/scene_bench.py    # N GPUs:
         tiles sharded over the ranks (RCCL: packed-weight broadcast, banded canvas reduce, point broadcast, vote gather);
         rank 0 prints ms/scene (max over ranks) and the per-rank stage times
@@ -172,6 +176,37 @@ def bands_scene(args, net, cfg, img, dev, rng, iters=20):
     return raw, report
 
 
+def scale_report(net, scale, scene_d, iters=20):
+    """--scale P Q: device ms of the resample steps alone (events around `iters` launches after a warm-up) with the bytes they must move:
+    the scene forward (p/q), the two masks back (q/p, to the scene's own size), each in the separable LDS form and in the direct form."""
+    p, q = scale
+    H, W = int(scene_d.shape[0]), int(scene_d.shape[1])
+
+    def device_ms(fn):
+        fn()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        e0.record()
+        for _ in range(iters):
+            fn()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) / iters
+
+    small = net.scene_resample(scene_d, p, q)
+    Hm, Wm = int(small.shape[0]), int(small.shape[1])
+    masks = [small[..., c].contiguous() for c in (0, 1)]
+    back = lambda direct: [net.scene_resample(m, q, p, out_shape=(H, W), direct=direct) for m in masks]
+    assert torch.equal(net.scene_resample(scene_d, p, q, direct=True), small) and all(torch.equal(a, b) for a, b in zip(back(False), back(True)))
+    fwd_bytes, back_bytes = 3 * (H * W + Hm * Wm), 2 * (H * W + Hm * Wm)
+    rep = {"scale": [p, q], "scene": [H, W], "model_frame": [Hm, Wm], "forward_must_move_bytes": fwd_bytes, "back_must_move_bytes": back_bytes}
+    for name, direct in (("lds", False), ("direct", True)):
+        f, b = device_ms(lambda: net.scene_resample(scene_d, p, q, direct=direct)), device_ms(lambda: back(direct))
+        rep.update({f"forward_ms_{name}": round(f, 4), f"back_two_masks_ms_{name}": round(b, 4),
+                    f"forward_GBps_{name}": round(fwd_bytes / f * 1e-6, 1), f"back_GBps_{name}": round(back_bytes / b * 1e-6, 1)})
+    return rep
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--bias", type=float, default=-2.2)
@@ -194,6 +229,8 @@ def main():
                     help="SCENE_BANDS: the scene is a raw C-band scene of DTYPE uint8 / uint16 (bands 0..2 hold the synthetic RGB, the rest noise)")
     ap.add_argument("--stretch", nargs=3, default=None, metavar=("KIND", "A", "B"),
                     help="with --bands: 'range LO HI' (ints) or 'percentile PLO PHI' (default: the whole range of the dtype)")
+    ap.add_argument("--scale", nargs=2, type=int, default=None, metavar=("P", "Q"),
+                    help="SCENE_SCALE: the scene is at P/Q model pixels per scene pixel and is resampled on the device (default: the key is absent)")
     ap.add_argument("--no-pipelined", action="store_true", help="skip the infer_imgs runs (12- and 48-scene streams)")
     ap.add_argument("--patch", type=int, default=512, metavar="P", help="PATCH_SIZE (default 512)")
     ap.add_argument("--margin", type=int, default=64, metavar="M", help="SAMPLE_MARGIN (default 64)")
@@ -229,10 +266,17 @@ def main():
         cfg.TTA = [t.strip() for t in args.tta.split(",")]
     if args.scene_pad is not None or args.scene_pad_mode is not None:
         cfg.SCENE_PAD = {"border": args.scene_pad or 0, "mode": args.scene_pad_mode or "reflect"}
+    if args.scale is not None:
+        if args.valid_frac is not None or args.scenes is not None:
+            ap.error("--scale times one unmasked scene (not with --valid-frac or --scenes)")
+        cfg.SCENE_SCALE = list(args.scale)
     from sam_road_amd.inferencer import fuse_window, scene_pad_plan, tta_plan
+    from sam_road_amd.resample import model_shape, scene_scale_key
     window = fuse_window(cfg)
     tta_names, tta = tta_plan(cfg)
-    pad = scene_pad_plan((H, W), cfg)
+    scale = scene_scale_key(cfg)
+    Hm, Wm = model_shape((H, W), scale)                # the frame pass 1 runs in (the scene's own without --scale)
+    pad = scene_pad_plan((Hm, Wm), cfg)
     pads = pad[:4] if pad is not None and any(pad[:4]) else None      # all four 0: the run of a scene without the key
     net = SAMRoad(cfg)
     g = torch.Generator().manual_seed(1234)
@@ -288,13 +332,16 @@ def main():
     tkw = {} if len(tta) == 1 else dict(tta=tta)                      # TTA: pass 1 runs the list once per orientation,
     xy_norm = xy if len(tta) == 1 else xy.repeat(len(tta), 1)         # the normalise gets the k-fold list
 
-    def crop(m):              # SCENE_PAD: the real scene's window of a mask of the padded scene, cut out on the device
-        return m if pads is None else m[pads[0]:pads[0] + H, pads[2]:pads[2] + W].contiguous()
+    def crop(m):              # SCENE_PAD: the real scene's window of a mask of the padded scene, cut out on the device;
+        m = m if pads is None else m[pads[0]:pads[0] + Hm, pads[2]:pads[2] + Wm].contiguous()      # SCENE_SCALE: then the way back
+        return m if scale is None else net.scene_resample(m, scale[1], scale[0], out_shape=(H, W))
 
     def pass1():              # this rank's share of the tiles (no collective: tile throughput)
         sc, vd = scene, valid_d
         if bands_report is not None:   # from the resident RAW scene: histogram + round trip (percentile), tables, apply are part of every pass 1
             sc = bands_front(net, cfg, scene, valid_d)
+        if scale is not None:      # from the resident scene at its own resolution: the resample is part of every pass 1
+            sc = net.scene_resample(sc, *scale)
         if pads is not None:       # from the resident real scene: the pad is part of every pass 1
             sc = net.scene_pad(sc, pads, pad[4], pad[5])
             vd = None if valid_d is None else net.scene_pad(valid_d, pads, pad[4], (0, 0, 0))
@@ -379,6 +426,7 @@ def main():
                       "tta": tta_names,
                       "scene_pad": None if pad is None else {"pads": list(pad[:4]), "mode": pad[4]},
                       "scene_bands": bands_report,
+                      "scene_scale": None if scale is None else scale_report(net, scale, scene if bands_report is None else bands_front(net, cfg, scene)),
                       "valid_frac": None if valid is None else round(float(valid.mean()), 4), "tiles_kept": len(infos), "tiles_all": n_all,
                       "ms_weight_share": round(1e3 * t_w, 2) if world > 1 else None, "per_rank": per_rank,
                       "infer_batch_size": args.batch, "ms_per_scene_pass1": round(1e3 * p1, 2),
