@@ -321,6 +321,29 @@ int srh_scene_resample(srh_ctx* ctx, const uint8_t* src, int H, int W, int C, ui
                        const uint8_t* weights_y, int Ty, int Dy, const int32_t* start_x, const uint8_t* weights_x, int Tx, int Dx, int mode,
                        const uint8_t* zero_where, int block_h, int block_w, int win_h, int win_w, void* stream);
 
+/* Small mask components dropped on the device (config key MASK_CLEAN; an extension): a connected-component filter of the
+ * u8 masks between the normalise step and the download.  One additive entry; the ABI number stays 11 because nothing existing changes,
+ * and a run without the key does not call it.
+ *
+ * srh_mask_clean: filters n u8 images IN PLACE.  Image k is a dense H_k x W_k block at byte offset OFF_k of buf (buf_bytes bytes on the
+ *   device, any byte address).  A pixel is foreground iff its level is >= T_ON_k; the components are the connected components of the
+ *   foreground under `connectivity` (8 or 4) inside the image — nothing connects two images, however their blocks lie; a component
+ *   stays iff its pixel count is >= MIN_AREA_k and its highest level is >= T_PEAK_k; the pixels of the others become 0 and every other
+ *   byte of buf is untouched (sam_road_amd/mask_clean.py states the rule: mask_clean_ref).
+ *   The table, int64 [n, 8], is given twice, as for srh_scene_group_pack: table_host is validated, table_dev is what the kernels read.
+ *   Row k: {OFF, H, W, T_ON, MIN_AREA, T_PEAK, BASE, SEG0}, BASE = sum of H W and SEG0 = sum of H ceil(W / 64) over the rows before k.
+ *   parent, area, peak: int32 [ws_pixels] each on the device, the CALLER's — the entry touches no workspace of the context; their
+ *   content on entry does not matter and is undefined afterwards.
+ *   Five launches per call whatever the images hold (init, merge, flatten, statistics, apply: label equivalence with a union-find in
+ *   global memory).  No workgroup waits for another, nothing is read back and the host does not wait.
+ *   SRH_ERR_BAD_ARG, and nothing is launched, for a null pointer, a connectivity other than 4 or 8, a workspace that is not 4-byte
+ *   aligned, n outside 1 .. 4096, or a host table in which a block has H or W < 1, leaves buf or overlaps another block, T_ON or T_PEAK
+ *   lies outside 0 .. 256, MIN_AREA is < 1, BASE or SEG0 is not the running sum, or the pixels of all images exceed ws_pixels or
+ *   2^31 - 1.  Every pixel and neighbour access of the kernels is bounded by the row's H and W.  Profiler rows: mask_clean_init,
+ *   mask_clean_merge, mask_clean_flatten, mask_clean_stats, mask_clean_apply. */
+int srh_mask_clean(srh_ctx* ctx, uint8_t* buf, int64_t buf_bytes, const int64_t* table_host, const int64_t* table_dev, int n,
+                   int connectivity, int32_t* parent, int32_t* area, int32_t* peak, int64_t ws_pixels, void* stream);
+
 /* op level (used by the parity tests to localise a failure; same kernels as above) ----------------- */
 
 /* out = act(A[M,K] W[N,K]^T + bias) (+resid); A,W fp16; N%128==0, K%64==0. act: 0/1 GELU/2 ReLU. */

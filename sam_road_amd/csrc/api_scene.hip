@@ -274,3 +274,27 @@ extern "C" int srh_scene_resample(srh_ctx* c, const uint8_t* src, int H, int W, 
     TRYK(c, "scene_resample", 0, ((double)H * W + (double)Ho * Wo) * C, s, launch_scene_resample(p, s));
     return 0;
 }
+
+// ---- scene level, connected-component filter of the masks (kernels in mask_clean.hip, behaviour in DESIGN.md §6k) ----------------------------
+extern "C" int srh_mask_clean(srh_ctx* c, uint8_t* buf, int64_t buf_bytes, const int64_t* table_host, const int64_t* table_dev, int n,
+                              int connectivity, int32_t* parent, int32_t* area, int32_t* peak, int64_t ws_pixels, void* stream) {
+    if (!c || !buf || !table_host || !table_dev || !parent || !area || !peak) return fail(c, SRH_ERR_BAD_ARG, "srh_mask_clean: null argument");
+    if (connectivity != 4 && connectivity != 8) return fail(c, SRH_ERR_BAD_ARG, "srh_mask_clean: the connectivity is 4 or 8");
+    if (((reinterpret_cast<uintptr_t>(parent) | reinterpret_cast<uintptr_t>(area) | reinterpret_cast<uintptr_t>(peak)) & 3))
+        return fail(c, SRH_ERR_BAD_ARG, "srh_mask_clean: a misaligned workspace");
+    if (!mask_clean_table_ok(table_host, n, buf_bytes, ws_pixels))
+        return fail(c, SRH_ERR_BAD_ARG, "srh_mask_clean: an inconsistent table (blocks inside the buffer and disjoint, running BASE and SEG0, thresholds 0 to "
+                                        "256, min_area >= 1, at most 2^31 - 1 pixels, all of them in the workspaces)");
+    hipSetDevice(c->device);
+    hipStream_t s = (hipStream_t)stream;
+    MaskCleanParams p;
+    p.buf = buf; p.table = table_dev; p.n = n; p.conn = connectivity; p.parent = parent; p.area = area; p.peak = peak;
+    p.n_segs = mask_clean_segs(table_host, n);
+    const double px = (double)(table_host[(long)(n - 1) * MC_COLS + MC_BASE] + table_host[(long)(n - 1) * MC_COLS + MC_H] * table_host[(long)(n - 1) * MC_COLS + MC_W]);
+    TRYK(c, "mask_clean_init", 0, px * 13, s, launch_mask_clean(p, 0, s));
+    TRYK(c, "mask_clean_merge", 0, px * 6, s, launch_mask_clean(p, 1, s));
+    TRYK(c, "mask_clean_flatten", 0, px * 9, s, launch_mask_clean(p, 2, s));
+    TRYK(c, "mask_clean_stats", 0, px * 5, s, launch_mask_clean(p, 3, s));
+    TRYK(c, "mask_clean_apply", 0, px * 6, s, launch_mask_clean(p, 4, s));
+    return 0;
+}

@@ -7,6 +7,7 @@
 #include "scene_group_piece.hpp"
 #include "scene_bands_piece.hpp"
 #include "scene_scale_piece.hpp"
+#include "mask_clean_piece.hpp"
 
 namespace srh {
 
@@ -197,6 +198,10 @@ int launch_scene_bands_apply(const SceneBandsParams& p, hipStream_t s);
 // Scene resampling (scene_scale.hip; SceneScaleParams in scene_scale_piece.hpp): dst = src resampled by two per-axis tap
 // tables, the weighted sum with one rounding or the validity rule; -2 for parameters outside their range.
 int launch_scene_resample(const SceneScaleParams& p, hipStream_t s);
+// Connected-component filter of u8 masks, in place (mask_clean.hip; MaskCleanParams and the table in mask_clean_piece.hpp):
+// step 0 .. 4 = init, merge, flatten, statistics, apply — five launches per call, none of which waits for another workgroup.  The table
+// is on the device and has been checked on the host (mask_clean_table_ok); -2 for bad parameters.
+int launch_mask_clean(const MaskCleanParams& p, int step, hipStream_t s);
 
 // Bilinear sampler (F.grid_sample, align_corners=False, zeros) on channels-last embeddings.
 struct SampleParams {

@@ -28,6 +28,7 @@ from . import _lib
 from . import distributed as D
 from .graph_points import extract_graph_points
 from .hostcpu import fill_threads, usable_cpus, worker_threads
+from .mask_clean import idle as _rule_idle, mask_clean_key, mask_clean_override, mask_clean_table
 from .resample import map_nodes, model_shape, scene_scale_key, scene_scale_override
 from .radiometry import band_luts, fixed_ranges, scene_bands_check, scene_bands_key, scene_bands_override, stretch_from_hist
 from .tiling import get_patch_info_hw, get_patch_info_one_img, patches_per_axis, shard_tiles
@@ -1189,6 +1190,23 @@ class _LaneIO:
         self.lap(self.STEPS.get(name))
 
 
+MASK_CLEAN_MAX_IMAGES = 4096             # = MC_MAX_IMAGES of csrc/mask_clean_piece.hpp: the images of one srh_mask_clean call
+
+
+def mask_clean_plan(config):
+    """config.MASK_CLEAN parsed: a mask_clean.MaskCleanPlan — per mask (t_on, min_area, t_peak), and the connectivity —
+    or None when the key is missing, None, empty or names nothing that could drop a component: no scene takes a step of it then.
+    ValueError for anything else (mask_clean.mask_clean_key), before the device is touched."""
+    return mask_clean_key(config)
+
+
+def _mask_clean_images(plan, blocks, total):
+    """The images of one srh_mask_clean call over a uint8 [2, total] buffer (row 0 keypoint masks, row 1 road masks) that holds the H x W
+    blocks `blocks` = [(offset in a row, H, W), ...]: the table (host, int64 [n,8]), or None when no mask has a rule that can drop."""
+    images = [(row * total + off, H, W, rule) for row, rule in enumerate((plan.keypoint, plan.road)) if not _rule_idle(rule) for off, H, W in blocks]
+    return mask_clean_table(images) if images else None
+
+
 class _SceneSetup:
     """What one infer_one_img / infer_imgs / _infer_imgs_tile_sharded call fixes for all of its scenes.  sharded: the scenes' tiles are
     split over the ranks of torch.distributed (world 1 without it); False: this process runs whole scenes and issues no collective."""
@@ -1204,6 +1222,7 @@ class _SceneSetup:
         self.bands = scene_bands_key(config)             # SCENE_BANDS, or None: no scene takes a step of it
         self.bands_luts = {}                             # levels -> the tables of a fixed range on the device, built once per call
         self.scale = scene_scale_key(config)             # SCENE_SCALE as (p, q), or None: no scene takes a step of it
+        self.clean = mask_clean_plan(config)             # MASK_CLEAN as a MaskCleanPlan, or None: no scene takes a step of it
 
     @functools.cached_property
     def features(self):
@@ -1260,7 +1279,8 @@ class _SceneJob:
 
 def _pass1_front(ctx, io, img, valid=None, group=None):
     """Pass 1 of one scene, queued (GPU): plan, upload, [band step,] [resample,] [border padding,] [tile selection, nodata fill,] crop ->
-    encoder -> decoder -> fused canvases, [canvas reduce,] normalise[, masks cropped back][, masks resampled back].  `io` decides how arrays travel and when the host waits
+    encoder -> decoder -> fused canvases, [canvas reduce,] normalise[, masks cropped back][, small components dropped][, masks resampled
+    back].  `io` decides how arrays travel and when the host waits
     (_BlockingIO / _LaneIO); everything else is the same for every loop.  Returns the _SceneJob: embeddings resident, the u8 masks on the
     device of rank 0 — fetching them is the caller's.  SCENE_PAD lives here and nowhere else: the real scene (and mask)
     is uploaded and padded on the device, everything up to the normalise runs on that virtual scene through the same calls, the u8 masks
@@ -1271,6 +1291,9 @@ def _pass1_front(ctx, io, img, valid=None, group=None):
     (the mask by the validity rule), everything up to the crop runs in that frame through the same calls, and at the end both masks are
     resampled back to the scene's own size by q/p, 0 wherever the scene's mask is.  The job carries both pairs of masks (the model-frame
     ones feed the unchanged point extraction and pass 2) and the tiles in the model frame; the nodes are mapped where the result is formed.
+    MASK_CLEAN lives here and nowhere else: on rank 0, behind the normalise and the crop to the real scene and in front of
+    the way back and the download, the connected components of each thresholded mask that are too small or too faint are set to 0 in
+    place (net.mask_clean: five queued launches, nothing read back); its table travels with the scene's other uploads.
     group (SCENE_GROUP; img and valid are None then): a planned group, a list of _GroupScene, takes the place of the one
     scene — one ragged upload and one pack launch build the vertical stack of the scenes (each padded by its own pads) and of their masks,
     then the stack IS the scene of the code below, and one crop launch cuts every scene's window out of the stack's masks; the job
@@ -1286,6 +1309,9 @@ def _pass1_front(ctx, io, img, valid=None, group=None):
         xy_dev = io.upload("xy", all_xy)
         shape, pads, job_pads = tuple(int(v) for v in scene.shape[:2]), None, (0, 0, 0, 0)
         scene_shape = shape
+        if ctx.clean is not None:                      # MASK_CLEAN: one image per mask and scene, at its place in scene_group_crop's output
+            n_px = sum(sc.shape[0] * sc.shape[1] for sc in group)
+            clean_table = _mask_clean_images(ctx.clean, [(int(off), *sc.shape) for sc, off in zip(group, crop_table[:, 0])], n_px)
     else:
         img, infos, all_xy = _scene_plan(img, config)
         scene_shape = tuple(int(v) for v in img.shape[:2])
@@ -1297,6 +1323,8 @@ def _pass1_front(ctx, io, img, valid=None, group=None):
         pass1_kw, norm_kw, n_orient = ctx.features
         scene = io.upload("scene", img)                    # the u8 scene, ONCE; tiles are cropped on the device
         xy_dev = io.upload("xy", all_xy)
+        if ctx.clean is not None:                          # MASK_CLEAN: the two masks of the real scene (model frame), one above the other
+            clean_table = _mask_clean_images(ctx.clean, [(0, *shape)], shape[0] * shape[1])
         if valid is not None:
             valid_d = io.upload("valid_mask", valid)       # a key of its own: "valid" stages pass 2's pair flags
         io.step("upload")
@@ -1313,6 +1341,8 @@ def _pass1_front(ctx, io, img, valid=None, group=None):
                 valid_d = net.scene_pad(valid_d, pads, pad[4], (0, 0, 0))
             io.step("pad")
         job_pads = pads or (0, 0, 0, 0)
+    if ctx.clean is not None and clean_table is not None and ctx.rank == 0:
+        clean_table_d = io.upload("clean_table", clean_table)     # travels with the scene: the filter below adds no host wait
     if valid is not None:
         # every rank holds the scene and the mask, computes the same integer counts and therefore the same kept list: from here
         # on infos / all_xy / xy_dev ARE the kept tiles (a subsequence of an x-outer list is x-outer, so the banded reduce stays valid)
@@ -1351,6 +1381,12 @@ def _pass1_front(ctx, io, img, valid=None, group=None):
         if pads is not None:                           # the real scene's window of the virtual masks, cut out on the device: H * W bytes travel
             (top, _, left, _), (H, W) = pads, shape
             job.kp_u8, job.road_u8 = (m[top:top + H, left:left + W].contiguous() for m in (job.kp_u8, job.road_u8))
+        if group is None and ctx.clean is not None and clean_table is not None:
+            # MASK_CLEAN lives here and nowhere else: the components of the masks of the REAL scene — cropped, before they
+            # are resampled back or travel — in place in one [2,H,W] tensor, so that one call serves both masks; queued, nothing read back
+            both = torch.stack((job.kp_u8, job.road_u8))
+            net.mask_clean(both.view(-1), clean_table, table_dev=clean_table_d, connectivity=ctx.clean.connectivity)
+            job.kp_u8, job.road_u8 = both[0], both[1]
         if job.scale is not None:                      # the way back: both masks to the scene's own size by q/p, 0 on the scene's nodata
             (p, q), job.model_kp_u8, job.model_road_u8 = job.scale, job.kp_u8, job.road_u8
             job.kp_u8, job.road_u8 = (net.scene_resample(m, q, p, out_shape=scene_shape, zero_where=valid_scene if valid is not None else None)
@@ -1358,6 +1394,8 @@ def _pass1_front(ctx, io, img, valid=None, group=None):
         if group is not None:                          # every scene's window of the stack's masks, one launch, one allocation
             job.group = _group_children(group, first, infos)
             job.kp_u8, job.road_u8 = net.scene_group_crop(job.kp_u8, job.road_u8, crop_table, table_dev=crop_table_d), None
+            if ctx.clean is not None and clean_table is not None:      # every mask of every scene is an image of its own: one call
+                net.mask_clean(job.kp_u8.view(-1), clean_table, table_dev=clean_table_d, connectivity=ctx.clean.connectivity)
     io.step("normalised")
     return job
 
@@ -1505,7 +1543,11 @@ def infer_imgs(net, imgs, config, device=None, tile_sharded=None, pipelined=None
     tta_plan(config)
     scene_pad_key(config)
     bands = scene_bands_key(config)
+    clean = mask_clean_plan(config)
     n_group = scene_group_key(config, group)
+    if clean is not None and 2 * n_group > MASK_CLEAN_MAX_IMAGES:
+        raise ValueError(f"MASK_CLEAN filters the two masks of every scene of a group in one call of at most {MASK_CLEAN_MAX_IMAGES} images: "
+                         f"SCENE_GROUP = {n_group} is too large, use at most {MASK_CLEAN_MAX_IMAGES // 2}")
     if scene_scale_key(config) is not None and n_group > 1:
         raise ValueError(f"SCENE_SCALE does not combine with SCENE_GROUP = {n_group} (a group's stack holds scenes of one frame): drop one of them")
     valids = _valid_iter(valids)
@@ -1968,6 +2010,14 @@ def main(argv=None):
     ap.add_argument("--scene-gsd", default=None, type=float, metavar="A",
                     help="(extension) the same as metres per scene pixel: the scale is A / B with --model-gsd B, which must be such a fraction")
     ap.add_argument("--model-gsd", default=None, type=float, metavar="B", help="(extension) metres per pixel the model was trained at (default 1.0)")
+    ap.add_argument("--mask-min-area", default=None, nargs="+", type=int, metavar="N",
+                    help="(extension) ROAD [KEYPOINT]: drop the connected components of the thresholded road (keypoint) mask that have fewer than "
+                         "N pixels before the graph points are extracted, on the device, overriding min_area of the config's MASK_CLEAN")
+    ap.add_argument("--mask-min-peak", default=None, nargs="+", type=float, metavar="P",
+                    help="(extension) ROAD [KEYPOINT]: drop the components whose highest score is not above P (in [0, 1)), overriding min_peak "
+                         "of the config's MASK_CLEAN")
+    ap.add_argument("--mask-connectivity", default=None, type=int, metavar="N",
+                    help="(extension) 8 (default) or 4: which neighbours connect two mask pixels, overriding connectivity of the config's MASK_CLEAN")
     ap.add_argument("--scene-group", default=None, type=int, metavar="N",
                     help="(extension) run up to N consecutive scenes as one — one upload, one pass 1 over all their tiles in full batches, "
                          "one TopoNet launch sequence — overriding the config's SCENE_GROUP; for streams of small scenes (chips).  1: scene "
@@ -1991,6 +2041,8 @@ def main(argv=None):
         config.SCENE_GROUP = args.scene_group
     if args.scene_scale is not None or args.scene_gsd is not None or args.model_gsd is not None:
         config.SCENE_SCALE = scene_scale_override(config, args.scene_scale, args.scene_gsd, args.model_gsd)
+    if args.mask_min_area is not None or args.mask_min_peak is not None or args.mask_connectivity is not None:
+        config.MASK_CLEAN = mask_clean_override(config, args.mask_min_area, args.mask_min_peak, args.mask_connectivity)
     if args.scene_pad is not None or args.scene_pad_mode is not None:
         config.SCENE_PAD = scene_pad_override(config, args.scene_pad, args.scene_pad_mode)
     if args.fuse_window is not None:
@@ -2003,6 +2055,7 @@ def main(argv=None):
     scene_pad_plan((1, 1), config)               # and a SCENE_PAD (or the NODATA_FILL it uses) that cannot be used
     bands = scene_bands_key(config)              # and a SCENE_BANDS that cannot be used
     scene_scale_key(config)                      # and a SCENE_SCALE that cannot be used (or that meets a SCENE_GROUP)
+    mask_clean_plan(config)                      # and a MASK_CLEAN that cannot be used
     if bands is not None and bands.percentile is not None and scene_group_key(config) > 1:
         raise ValueError("SCENE_BANDS: a percentile stretch does not combine with SCENE_GROUP (every scene needs its own tables); use a fixed range")
     if scene_group_key(config) > 1 and args.shard != "scenes" and int(os.environ.get("WORLD_SIZE", "1")) > 1:      # and a SCENE_GROUP

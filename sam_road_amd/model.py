@@ -864,3 +864,46 @@ class SAMRoad(nn.Module):
                                                    t.data_ptr(), t_dev.data_ptr(), int(t.shape[0]), out[0].data_ptr(), out[1].data_ptr(), total,
                                                    self._stream(dev)), "srh_scene_group_crop")
         return out
+
+    # ---- scene level, small mask components dropped (MASK_CLEAN) ---------------------------------------------------------
+    @torch.no_grad()
+    def mask_clean(self, buf_u8, table, table_dev=None, connectivity=8):
+        """The connected-component filter of mask_clean.mask_clean_ref, IN PLACE, on every image that `table` describes inside buf_u8, a
+        flat contiguous uint8 tensor on the GPU (srh_mask_clean): table int64 [n,8] on the HOST (mask_clean.mask_clean_table), one row
+        {byte offset in buf_u8, H, W, t_on, min_area, t_peak, BASE, SEG0} per image.  Nothing connects two images.  table_dev: the table on
+        the GPU if the caller has uploaded it already.  The workspaces — an int32 parent / label per pixel plus an area and a peak per
+        label — are allocated here for the call; the five launches are queued on the current stream and nothing is read back.  Returns
+        buf_u8."""
+        dev = buf_u8.device
+        ctx, _ = self._weights(dev)
+        if buf_u8.dtype != torch.uint8 or buf_u8.dim() != 1 or not buf_u8.is_contiguous() or buf_u8.numel() < 1:
+            raise ValueError(f"mask_clean takes a flat contiguous uint8 tensor, got {buf_u8.dtype} {tuple(buf_u8.shape)}")
+        if connectivity not in (4, 8):
+            raise ValueError(f"connectivity must be 4 or 8, got {connectivity!r}")
+        t, t_dev = self._group_table(table, table_dev, dev)
+        total = int((t[:, 1] * t[:, 2]).sum())
+        if total < 1 or total > 2 ** 31 - 1:
+            raise ValueError(f"mask_clean: the table describes {total} pixels; 1 to 2^31 - 1 are supported")
+        ws = torch.empty((3, total), dtype=torch.int32, device=dev)
+        with torch.cuda.device(dev):
+            ctx.check(ctx.lib.srh_mask_clean(ctx.handle, buf_u8.data_ptr(), buf_u8.numel(), t.data_ptr(), t_dev.data_ptr(), int(t.shape[0]),
+                                             int(connectivity), ws[0].data_ptr(), ws[1].data_ptr(), ws[2].data_ptr(), total, self._stream(dev)),
+                      "srh_mask_clean")
+        return buf_u8
+
+    def mask_clean_pair(self, kp_u8, road_u8, plan):
+        """mask_clean for the two [H,W] masks of one scene under a mask_clean.MaskCleanPlan, in place: one call when both are rows of one
+        contiguous [2,H,W] tensor, else one call per mask; a mask whose rule drops nothing is left out.  Returns (kp_u8, road_u8)."""
+        from . import mask_clean as mc
+        for m in (kp_u8, road_u8):
+            if m.dtype != torch.uint8 or m.dim() != 2 or not m.is_contiguous() or tuple(m.shape) != tuple(kp_u8.shape):
+                raise ValueError(f"mask_clean_pair takes two contiguous uint8 [H,W] masks of one shape, got {m.dtype} {tuple(m.shape)}")
+        H, W = int(kp_u8.shape[0]), int(kp_u8.shape[1])
+        live = [(m, rule) for m, rule in ((kp_u8, plan.keypoint), (road_u8, plan.road)) if not mc.idle(rule)]
+        if len(live) == 2 and road_u8.data_ptr() == kp_u8.data_ptr() + H * W and kp_u8.untyped_storage().data_ptr() == road_u8.untyped_storage().data_ptr():
+            both = torch.as_strided(kp_u8, (2 * H * W,), (1,))
+            self.mask_clean(both, mc.mask_clean_table([(0, H, W, plan.keypoint), (H * W, H, W, plan.road)]), connectivity=plan.connectivity)
+        else:
+            for m, rule in live:
+                self.mask_clean(m.view(-1), mc.mask_clean_table([(0, H, W, rule)]), connectivity=plan.connectivity)
+        return kp_u8, road_u8

@@ -27,6 +27,11 @@ The final map_decoder bias is lowered so that the random network yields sparse m
                                                                     # (--tiles counts tiles of the MODEL frame); the resample steps are part of
                                                                     # every pass 1, and "scene_scale" reports their device time alone, forward
                                                                     # and back, in the separable LDS form and in the direct form
+    python tools/scene_bench.py --mask-clean 200 0.6 [20 0.5]       # MASK_CLEAN: road min_area and min_peak [keypoint's]; the filter is part of
+                                                                    # every timed run, and "mask_clean" reports its device time alone — on the
+                                                                    # scene's own masks and on a random mask at density 0.5, per kernel — next to
+                                                                    # pass 1's, the pipelined loop with and without the key in turn, and the host
+                                                                    # time of mask_clean_ref on the same masks
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 tools/scene_bench.py    # N GPUs:
         tiles sharded over the ranks (RCCL: packed-weight broadcast, banded canvas reduce, point broadcast, vote gather);
         rank 0 prints ms/scene (max over ranks) and the per-rank stage times
@@ -207,6 +212,93 @@ def scale_report(net, scale, scene_d, iters=20):
     return rep
 
 
+def mask_clean_report(net, cfg, img, valid, pass1, iters=10):
+    """--mask-clean: device ms of the filter alone (events around each of `iters` calls on a fresh copy of the masks, after a warm-up) on
+    the scene's own two masks, on two random masks at density 0.5 and on two all-foreground masks (one component each), with the per-kernel rows of one profiled call; device ms of this
+    scene's pass 1; ms per scene of the pipelined loop without / with / without / with the key; host ms of mask_clean_ref."""
+    import sam_road_amd.inferencer as inf
+    from sam_road_amd import Config, _lib
+    from sam_road_amd.mask_clean import mask_clean_ref, mask_clean_stats, mask_clean_table
+    plan = inf.mask_clean_plan(cfg)
+    plain = Config({k: v for k, v in cfg.items() if k != "MASK_CLEAN"})
+    _, _, kp, road = inf.infer_one_img(net, img, plain, valid=valid)
+    H, W = kp.shape
+    dev = next(net.parameters()).device
+    ctx = _lib.Context.get(dev.index)
+    table = mask_clean_table([(0, H, W, plan.keypoint), (H * W, H, W, plan.road)])
+    table_d = torch.from_numpy(table).to(dev)
+    rng = np.random.default_rng(7)
+
+    def random_mask(rule):
+        fg = rng.random((H, W)) < 0.5
+        return np.where(fg, rng.integers(rule.t_on, 256, size=(H, W)), rng.integers(0, max(1, rule.t_on), size=(H, W))).astype(np.uint8)
+
+    def measure(pair):
+        src = torch.from_numpy(np.stack(pair)).to(dev)
+        work = torch.empty_like(src)
+        run = lambda: net.mask_clean(work.copy_(src).view(-1), table, table_dev=table_d, connectivity=plan.connectivity)
+        run()
+        want = [mask_clean_ref(m, *rule, plan.connectivity) for m, rule in zip(pair, (plan.keypoint, plan.road))]
+        got = work.cpu().numpy()
+        if not np.array_equal(got, np.stack(want)):
+            for k in range(2):
+                bad = got[k] != want[k]
+                print(f"mask {k}: {int(bad.sum())} px differ, kept wrongly {int((bad & (got[k] != 0)).sum())}, rows {np.unique(np.nonzero(bad)[0])[:8].tolist()} "
+                      f"cols {np.unique(np.nonzero(bad)[1])[:8].tolist()} levels {pair[k][bad][:8].tolist()}", file=sys.stderr, flush=True)
+            raise SystemExit("the device filter differs from mask_clean_ref")
+        evs = []
+        for _ in range(iters):
+            work.copy_(src)
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            net.mask_clean(work.view(-1), table, table_dev=table_d, connectivity=plan.connectivity)
+            e1.record()
+            evs.append((e0, e1))
+        torch.cuda.synchronize()
+        ms = sorted(a.elapsed_time(b) for a, b in evs)
+        ctx.profile_read()
+        ctx.profile_enable(True)
+        run()
+        torch.cuda.synchronize()
+        rows = {r["name"]: round(r["ms"], 4) for r in ctx.profile_read() if r["name"].startswith("mask_clean")}
+        ctx.profile_enable(False)
+        t0 = time.perf_counter()
+        for m, rule in zip(pair, (plan.keypoint, plan.road)):
+            mask_clean_ref(m, *rule, plan.connectivity)
+        host = 1e3 * (time.perf_counter() - t0)
+        comps = [int(mask_clean_stats(m, rule.t_on, plan.connectivity)[0].size) for m, rule in zip(pair, (plan.keypoint, plan.road))]
+        return {"device_ms_median": round(ms[len(ms) // 2], 4), "device_ms_min_max": [round(ms[0], 4), round(ms[-1], 4)], "kernel_ms_one_call": rows,
+                "host_ms_mask_clean_ref_both_masks": round(host, 1), "components": comps,
+                "foreground_frac": [round(float((m >= rule.t_on).mean()), 4) for m, rule in zip(pair, (plan.keypoint, plan.road))],
+                "pixels_dropped": [int((w != m).sum()) for w, m in zip(want, pair)]}
+
+    rep = {"key": cfg.MASK_CLEAN, "rules": [list(plan.keypoint), list(plan.road)], "connectivity": plan.connectivity, "masks": [H, W],
+           "own_masks": measure((kp, road)), "random_0.5": measure((random_mask(plan.keypoint), random_mask(plan.road))),
+           "all_foreground": measure(tuple(rng.integers(max(1, rule.t_on), 256, size=(H, W)).astype(np.uint8) for rule in (plan.keypoint, plan.road)))}
+    evs = []
+    for _ in range(3):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        pass1()
+        e1.record()
+        evs.append((e0, e1))
+    torch.cuda.synchronize()
+    rep["pass1_device_ms"] = [round(a.elapsed_time(b), 2) for a, b in evs]
+
+    def piped(c, n=12):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in inf.infer_imgs(net, (img for _ in range(n)), c, valids=(valid for _ in range(n))):
+            pass
+        torch.cuda.synchronize()
+        return round(1e3 * (time.perf_counter() - t0) / n, 2)
+
+    piped(plain, 3), piped(cfg, 3)
+    rep["pipelined_ms_per_scene_runs_of_12"] = {"without_a": [piped(plain) for _ in range(3)], "with_a": [piped(cfg) for _ in range(3)],
+                                                "without_b": [piped(plain) for _ in range(3)], "with_b": [piped(cfg) for _ in range(3)]}
+    return rep
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--bias", type=float, default=-2.2)
@@ -231,6 +323,8 @@ def main():
                     help="with --bands: 'range LO HI' (ints) or 'percentile PLO PHI' (default: the whole range of the dtype)")
     ap.add_argument("--scale", nargs=2, type=int, default=None, metavar=("P", "Q"),
                     help="SCENE_SCALE: the scene is at P/Q model pixels per scene pixel and is resampled on the device (default: the key is absent)")
+    ap.add_argument("--mask-clean", nargs="+", default=None, metavar="V",
+                    help="MASK_CLEAN: ROAD_MIN_AREA ROAD_MIN_PEAK [KEYPOINT_MIN_AREA KEYPOINT_MIN_PEAK] (default: the key is absent)")
     ap.add_argument("--no-pipelined", action="store_true", help="skip the infer_imgs runs (12- and 48-scene streams)")
     ap.add_argument("--patch", type=int, default=512, metavar="P", help="PATCH_SIZE (default 512)")
     ap.add_argument("--margin", type=int, default=64, metavar="M", help="SAMPLE_MARGIN (default 64)")
@@ -270,7 +364,15 @@ def main():
         if args.valid_frac is not None or args.scenes is not None:
             ap.error("--scale times one unmasked scene (not with --valid-frac or --scenes)")
         cfg.SCENE_SCALE = list(args.scale)
-    from sam_road_amd.inferencer import fuse_window, scene_pad_plan, tta_plan
+    if args.mask_clean is not None:
+        if len(args.mask_clean) not in (2, 4) or args.scenes is not None or world > 1:
+            ap.error("--mask-clean takes ROAD_MIN_AREA ROAD_MIN_PEAK [KEYPOINT_MIN_AREA KEYPOINT_MIN_PEAK]; one GPU, not with --scenes")
+        v = args.mask_clean
+        cfg.MASK_CLEAN = {"road": {"min_area": int(v[0]), "min_peak": float(v[1])}}
+        if len(v) == 4:
+            cfg.MASK_CLEAN["keypoint"] = {"min_area": int(v[2]), "min_peak": float(v[3])}
+    from sam_road_amd.inferencer import fuse_window, mask_clean_plan, scene_pad_plan, tta_plan
+    clean = mask_clean_plan(cfg)
     from sam_road_amd.resample import model_shape, scene_scale_key
     window = fuse_window(cfg)
     tta_names, tta = tta_plan(cfg)
@@ -332,8 +434,11 @@ def main():
     tkw = {} if len(tta) == 1 else dict(tta=tta)                      # TTA: pass 1 runs the list once per orientation,
     xy_norm = xy if len(tta) == 1 else xy.repeat(len(tta), 1)         # the normalise gets the k-fold list
 
-    def crop(m):              # SCENE_PAD: the real scene's window of a mask of the padded scene, cut out on the device;
-        m = m if pads is None else m[pads[0]:pads[0] + Hm, pads[2]:pads[2] + Wm].contiguous()      # SCENE_SCALE: then the way back
+    def cleaned(kpu, ru):     # SCENE_PAD: the real scene's window of the masks of the padded scene, cut out on the device; MASK_CLEAN: the
+        kpu, ru = (m if pads is None else m[pads[0]:pads[0] + Hm, pads[2]:pads[2] + Wm].contiguous() for m in (kpu, ru))      # filter on them
+        return (kpu, ru) if clean is None else net.mask_clean_pair(kpu, ru, clean)
+
+    def crop(m):              # SCENE_SCALE: the way back
         return m if scale is None else net.scene_resample(m, scale[1], scale[0], out_shape=(H, W))
 
     def pass1():              # this rank's share of the tiles (no collective: tile throughput)
@@ -349,10 +454,10 @@ def main():
             net.scene_tile_valid(vd, torch.as_tensor(_scene_plan(img, cfg)[2]).to(dev)).cpu()
             filled = net.scene_fill_invalid(sc.clone(), vd, (124, 116, 104))
             kp, road, emb = net.scene_pass1(filled, xy[lo:hi], args.batch, **wkw, **tkw)
-            kpu, ru = net.scene_normalise(kp, road, xy_norm, valid=vd, **wkw)
+            kpu, ru = cleaned(*net.scene_normalise(kp, road, xy_norm, valid=vd, **wkw))
             return crop(kpu).cpu(), crop(ru).cpu()
         kp, road, emb = net.scene_pass1(sc, xy[lo:hi], args.batch, **wkw, **tkw)
-        kpu, ru = net.scene_normalise(kp, road, xy_norm, **wkw)
+        kpu, ru = cleaned(*net.scene_normalise(kp, road, xy_norm, **wkw))
         return crop(kpu).cpu(), crop(ru).cpu()
 
     pass1()
@@ -427,6 +532,7 @@ def main():
                       "scene_pad": None if pad is None else {"pads": list(pad[:4]), "mode": pad[4]},
                       "scene_bands": bands_report,
                       "scene_scale": None if scale is None else scale_report(net, scale, scene if bands_report is None else bands_front(net, cfg, scene)),
+                      "mask_clean": None if clean is None else mask_clean_report(net, cfg, img, valid, pass1),
                       "valid_frac": None if valid is None else round(float(valid.mean()), 4), "tiles_kept": len(infos), "tiles_all": n_all,
                       "ms_weight_share": round(1e3 * t_w, 2) if world > 1 else None, "per_rank": per_rank,
                       "infer_batch_size": args.batch, "ms_per_scene_pass1": round(1e3 * p1, 2),
