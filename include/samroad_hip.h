@@ -344,6 +344,34 @@ int srh_scene_resample(srh_ctx* ctx, const uint8_t* src, int H, int W, int C, ui
 int srh_mask_clean(srh_ctx* ctx, uint8_t* buf, int64_t buf_bytes, const int64_t* table_host, const int64_t* table_dev, int n,
                    int connectivity, int32_t* parent, int32_t* area, int32_t* peak, int64_t ws_pixels, void* stream);
 
+/* The validity mask from a nodata VALUE (config key SCENE_NODATA; an extension): which pixels of the raw scene hold the
+ * value, and that set grown by r pixels, on the device right behind the upload.  (The area rule in between is srh_mask_clean as it is.)
+ * Two additive entries; the ABI number stays 11 because nothing existing changes, and a run without the key calls neither.
+ *
+ * srh_scene_nodata_match: the source is n_pixels pixels of C elements, dense, on the device: src_dtype SRH_U8 (any byte address) or
+ *   SRH_U16 (any 2-byte-aligned address), 1 <= C <= 16, 1 <= n_pixels <= 2^31 - 1.  It knows nothing of rows: a scene and the ragged
+ *   buffer of a scene group are the same to it.  lo, hi: HOST arrays of C ints in 0 .. 65535; band c hits iff lo[c] <= element <=
+ *   hi[c] (lo > hi: never).  match: SRH_NODATA_ALL = every band hits, SRH_NODATA_ANY = at least one does.  and_with: u8 [n_pixels] on
+ *   the device or NULL; invert: 0 / 1.  out u8 [n_pixels] on the device (any byte address, overlapping neither src nor and_with):
+ *   out[i] = (invert ? !hit : hit) & (and_with ? and_with[i] != 0 : 1), 0 or 1.  The source is read and never written, every byte of
+ *   out is written exactly once and nothing else is.  No atomics, no LDS.
+ * srh_scene_nodata_grow: n images, image k a dense H_k x W_k u8 block at byte offset OFF_k of src AND of dst (and of and_with, if
+ *   given), each buffer `bytes` bytes on the device, src and dst not overlapping.  g[y, x] = 1 iff a pixel of the image within
+ *   Chebyshev distance r of (y, x) is non-zero in src — nothing outside the image counts, and nothing connects two images; dst =
+ *   (invert ? !g : g) & (and_with ? and_with != 0 : 1).  1 <= r <= 16.  The table, int64 [n, 8], is given twice, as for srh_mask_clean:
+ *   table_host is validated, table_dev is what the kernel reads.  Row k: {OFF, H, W, ...}; columns 3 .. 7 are not read, so a
+ *   srh_mask_clean table serves as it is.  Every byte of every block of dst is written exactly once and nothing else is.
+ * SRH_ERR_BAD_ARG, and nothing is launched, for a null pointer (and_with excepted), another dtype, C, n_pixels, match, invert or r
+ * outside their range, a bound outside 0 .. 65535, a misaligned u16 source, out overlapping src or and_with, src and dst of the grow
+ * overlapping, n outside 1 .. 4096, or a host table in which a block has H or W < 1, leaves the buffers, overlaps another block, or
+ * the pixels exceed 2^31 - 1.  Neither touches a workspace of the context.  Profiler rows: scene_nodata_match, scene_nodata_grow. */
+#define SRH_NODATA_ALL 0
+#define SRH_NODATA_ANY 1
+int srh_scene_nodata_match(srh_ctx* ctx, const void* src, int src_dtype, int64_t n_pixels, int C, const int32_t* lo, const int32_t* hi,
+                           int match, const uint8_t* and_with, int invert, uint8_t* out, void* stream);
+int srh_scene_nodata_grow(srh_ctx* ctx, const uint8_t* src, uint8_t* dst, int64_t bytes, const int64_t* table_host,
+                          const int64_t* table_dev, int n, int r, const uint8_t* and_with, int invert, void* stream);
+
 /* op level (used by the parity tests to localise a failure; same kernels as above) ----------------- */
 
 /* out = act(A[M,K] W[N,K]^T + bias) (+resid); A,W fp16; N%128==0, K%64==0. act: 0/1 GELU/2 ReLU. */

@@ -14,6 +14,7 @@ SRH_F32, SRH_F16, SRH_U8, SRH_I32, SRH_I64, SRH_U16 = 0, 1, 2, 3, 4, 5
 ABI_VERSION = 11
 SRH_GEMM_A_BLOCKED16, SRH_GEMM_OUT_BLOCKED16 = 1, 2       # srh_op_gemm_ex flags (include/samroad_hip.h)
 SRH_PAD_MODES = {"reflect": 0, "edge": 1, "constant": 2}  # srh_scene_pad modes (SRH_PAD_*)
+SRH_NODATA_MATCH = {"all": 0, "any": 1}                   # srh_scene_nodata_match modes (SRH_NODATA_*)
 
 
 class SrhError(RuntimeError):
@@ -79,6 +80,8 @@ SYMBOLS = {
     "srh_scene_bands_apply": (_I, [_P, _P, _I, C.c_int64, _I, _P, _P, _P, _P]),
     "srh_scene_resample": (_I, [_P, _P, _I, _I, _I, _P, _I, _I, _P, _P, _I, _I, _P, _P, _I, _I, _I, _P, _I, _I, _I, _I, _P]),
     "srh_mask_clean": (_I, [_P, _P, C.c_int64, _P, _P, _I, _I, _P, _P, _P, C.c_int64, _P]),
+    "srh_scene_nodata_match": (_I, [_P, _P, _I, C.c_int64, _I, _P, _P, _I, _P, _I, _P, _P]),
+    "srh_scene_nodata_grow": (_I, [_P, _P, _P, C.c_int64, _P, _P, _I, _I, _P, _I, _P]),
     "srh_op_patch_im2col": (_I, [_P, _P, _I, _I, _P, _I, _I, _I, _P, _P]),
     "srh_op_scores_unorient": (_I, [_P, _P, _I, _I, _I, _P, _P]),
     "srh_op_gemm": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P]),

@@ -298,3 +298,54 @@ extern "C" int srh_mask_clean(srh_ctx* c, uint8_t* buf, int64_t buf_bytes, const
     TRYK(c, "mask_clean_apply", 0, px * 6, s, launch_mask_clean(p, 4, s));
     return 0;
 }
+
+// ---- scene level, the validity mask from a nodata value (kernels in scene_nodata.hip, behaviour in DESIGN.md §6l) ---------------------------
+static_assert(SRH_NODATA_ALL == ND_ALL && SRH_NODATA_ANY == ND_ANY, "match modes of the header and the kernel");
+
+static bool ranges_overlap(const void* a, double a_bytes, const void* b, double b_bytes) {
+    const double a0 = (double)reinterpret_cast<uintptr_t>(a), b0 = (double)reinterpret_cast<uintptr_t>(b);
+    return a0 < b0 + b_bytes && b0 < a0 + a_bytes;
+}
+
+extern "C" int srh_scene_nodata_match(srh_ctx* c, const void* src, int src_dtype, int64_t n_pixels, int C, const int32_t* lo, const int32_t* hi,
+                                      int match, const uint8_t* and_with, int invert, uint8_t* out, void* stream) {
+    if (!c || !src || !lo || !hi || !out) return fail(c, SRH_ERR_BAD_ARG, "srh_scene_nodata_match: null argument");
+    if (src_dtype != SRH_U8 && src_dtype != SRH_U16) return fail(c, SRH_ERR_BAD_ARG, "srh_scene_nodata_match: the source is SRH_U8 or SRH_U16");
+    if (C < 1 || C > ND_MAX_C || n_pixels < 1 || n_pixels > ND_MAX_PIXELS)
+        return fail(c, SRH_ERR_BAD_ARG, "srh_scene_nodata_match: 1 to 16 bands and 1 to 2^31 - 1 pixels");
+    if ((match != SRH_NODATA_ALL && match != SRH_NODATA_ANY) || (invert != 0 && invert != 1))
+        return fail(c, SRH_ERR_BAD_ARG, "srh_scene_nodata_match: match is SRH_NODATA_ALL / SRH_NODATA_ANY and invert 0 / 1");
+    if (src_dtype == SRH_U16 && (reinterpret_cast<uintptr_t>(src) & 1)) return fail(c, SRH_ERR_BAD_ARG, "srh_scene_nodata_match: a u16 source is 2-byte aligned");
+    SceneNodataParams p;
+    for (int b = 0; b < C; ++b) {
+        if (lo[b] < 0 || lo[b] > 65535 || hi[b] < 0 || hi[b] > 65535) return fail(c, SRH_ERR_BAD_ARG, "srh_scene_nodata_match: a bound is 0 to 65535");
+        p.lohi[b] = (uint32_t)lo[b] | ((uint32_t)hi[b] << 16);
+    }
+    const double src_bytes = (double)n_pixels * C * (src_dtype == SRH_U16 ? 2 : 1);
+    if (ranges_overlap(out, (double)n_pixels, src, src_bytes) || (and_with && ranges_overlap(out, (double)n_pixels, and_with, (double)n_pixels)))
+        return fail(c, SRH_ERR_BAD_ARG, "srh_scene_nodata_match: out overlaps src or and_with");
+    p.src = src; p.and_with = and_with; p.out = out; p.n = (long)n_pixels; p.C = C; p.wide = src_dtype == SRH_U16; p.any = match; p.invert = invert;
+    hipSetDevice(c->device);
+    hipStream_t s = (hipStream_t)stream;
+    TRYK(c, "scene_nodata_match", 0, src_bytes + (double)n_pixels * (and_with ? 2 : 1), s, launch_scene_nodata_match(p, s));
+    return 0;
+}
+
+extern "C" int srh_scene_nodata_grow(srh_ctx* c, const uint8_t* src, uint8_t* dst, int64_t bytes, const int64_t* table_host,
+                                     const int64_t* table_dev, int n, int r, const uint8_t* and_with, int invert, void* stream) {
+    if (!c || !src || !dst || !table_host || !table_dev) return fail(c, SRH_ERR_BAD_ARG, "srh_scene_nodata_grow: null argument");
+    if (r < 1 || r > NG_MAX_R || (invert != 0 && invert != 1)) return fail(c, SRH_ERR_BAD_ARG, "srh_scene_nodata_grow: r is 1 to 16 and invert 0 / 1");
+    if (!grow_table_ok(table_host, n, bytes))
+        return fail(c, SRH_ERR_BAD_ARG, "srh_scene_nodata_grow: an inconsistent table (1 to 4096 blocks of at least 1 x 1 pixels, inside the buffers and "
+                                        "disjoint, at most 2^31 - 1 pixels)");
+    if (ranges_overlap(src, (double)bytes, dst, (double)bytes) || (and_with && ranges_overlap(and_with, (double)bytes, dst, (double)bytes)))
+        return fail(c, SRH_ERR_BAD_ARG, "srh_scene_nodata_grow: dst overlaps src or and_with");
+    hipSetDevice(c->device);
+    hipStream_t s = (hipStream_t)stream;
+    SceneGrowParams p;
+    p.src = src; p.dst = dst; p.and_with = and_with; p.table = table_dev; p.n = n; p.r = r; p.invert = invert;
+    double px = 0;
+    for (int k = 0; k < n; ++k) px += (double)(table_host[(long)k * NG_COLS + NG_H] * table_host[(long)k * NG_COLS + NG_W]);
+    TRYK(c, "scene_nodata_grow", 0, px * (and_with ? 3 : 2), s, launch_scene_nodata_grow(p, grow_max_blocks(table_host, n), s));
+    return 0;
+}

@@ -8,6 +8,7 @@
 #include "scene_bands_piece.hpp"
 #include "scene_scale_piece.hpp"
 #include "mask_clean_piece.hpp"
+#include "scene_nodata_piece.hpp"
 
 namespace srh {
 
@@ -202,6 +203,11 @@ int launch_scene_resample(const SceneScaleParams& p, hipStream_t s);
 // step 0 .. 4 = init, merge, flatten, statistics, apply — five launches per call, none of which waits for another workgroup.  The table
 // is on the device and has been checked on the host (mask_clean_table_ok); -2 for bad parameters.
 int launch_mask_clean(const MaskCleanParams& p, int step, hipStream_t s);
+// Validity mask from a nodata value (scene_nodata.hip; the parameters in scene_nodata_piece.hpp): the per-pixel match of a
+// raw u8 / u16 scene against per-band ranges, and the Chebyshev dilation of n u8 images described by a device table that has been checked
+// on the host (grow_table_ok; max_blocks = grow_max_blocks); -2 for bad parameters.
+int launch_scene_nodata_match(const SceneNodataParams& p, hipStream_t s);
+int launch_scene_nodata_grow(const SceneGrowParams& p, long max_blocks, hipStream_t s);
 
 // Bilinear sampler (F.grid_sample, align_corners=False, zeros) on channels-last embeddings.
 struct SampleParams {

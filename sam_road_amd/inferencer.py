@@ -29,6 +29,7 @@ from . import distributed as D
 from .graph_points import extract_graph_points
 from .hostcpu import fill_threads, usable_cpus, worker_threads
 from .mask_clean import idle as _rule_idle, mask_clean_key, mask_clean_override, mask_clean_table
+from .nodata import nodata_table, scene_nodata_check, scene_nodata_key, scene_nodata_override
 from .resample import map_nodes, model_shape, scene_scale_key, scene_scale_override
 from .radiometry import band_luts, fixed_ranges, scene_bands_check, scene_bands_key, scene_bands_override, stretch_from_hist
 from .tiling import get_patch_info_hw, get_patch_info_one_img, patches_per_axis, shard_tiles
@@ -601,6 +602,9 @@ def _scene_plan(img, config):
         raise ValueError(f"infer_one_img expects an HxWx3 uint8 scene, got {img.dtype} {tuple(img.shape)}")
     if img.shape[0] < 1 or img.shape[1] < 1:
         raise ValueError(f"infer_one_img expects a scene of at least 1 x 1 pixels, got {tuple(img.shape)}")
+    nodata = scene_nodata_key(config)
+    if nodata is not None:                                 # SCENE_NODATA: the value(s) against THIS scene's dtype and bands
+        scene_nodata_check(img, nodata)
     Hm, Wm = _model_frame(img.shape, scene_scale_key(config))
     pad = scene_pad_plan((Hm, Wm), config)
     top, bottom, left, right = pad[:4] if pad is not None else (0, 0, 0, 0)
@@ -664,10 +668,16 @@ def _valid_plan(valid, shape_hw, config):
         raise ValueError(f"valid must be a bool or uint8 mask, got dtype {valid.dtype}")
     if tuple(valid.shape) != tuple(shape_hw):
         raise ValueError(f"valid must have the scene's shape {tuple(shape_hw)}, got {tuple(valid.shape)}")
+    return (np.ascontiguousarray(valid).view(np.uint8), *_mask_keys(config))
+
+
+def _mask_keys(config):
+    """(MIN_VALID_FRACTION as a float in [0, 1] (missing key: 0), NODATA_FILL as three ints 0..255): what a masked scene reads from the
+    config, whether its mask was passed or derived (SCENE_NODATA).  ValueError for keys outside their range."""
     frac = 0.0 if _absent(config.MIN_VALID_FRACTION) else config.MIN_VALID_FRACTION
     if not (_is_int(frac) or isinstance(frac, (float, np.floating))) or not 0.0 <= float(frac) <= 1.0:        # NaN fails the range
         raise ValueError(f"MIN_VALID_FRACTION must be a number in [0, 1], got {frac!r}")
-    return np.ascontiguousarray(valid).view(np.uint8), float(frac), _nodata_fill(config)
+    return float(frac), _nodata_fill(config)
 
 
 def _nodata_fill(config):
@@ -745,7 +755,7 @@ def select_tiles(counts, patch_size, min_valid_fraction):
     return np.flatnonzero((counts > 0) & (counts >= float(min_valid_fraction) * int(patch_size) * int(patch_size)))
 
 
-def scene_tiles(shape, config, valid=None, net=None):
+def scene_tiles(shape, config, valid=None, net=None, img=None):
     """The tiles infer_one_img runs for a scene of `shape` = (H, W[, 3]): the list of (0, (x0, y0), (x1, y1)) in the reference's
     x-outer / y-inner order.  With `valid` (see infer_one_img) only the kept tiles, selected exactly as infer_one_img selects them: the
     counts come from `net.scene_tile_valid` on the model's device, so `net` is required then (there is no host fallback).  The list is
@@ -753,8 +763,19 @@ def scene_tiles(shape, config, valid=None, net=None):
     Under config.SCENE_PAD the tiles are those of the padded scene in the frame of the REAL one — origin (x0 - left, y0 - top), so a tile
     may start below 0 or overhang — and `pads` holds (top, bottom, left, right); the mask is padded like the scene before it is counted.
     Under config.SCENE_SCALE the plan is that of the MODEL frame: `scale` holds (p, q) ((1, 1) without the key), `model_shape` the frame's
-    (H, W), the tiles, the pads and the size limits refer to it, and the mask is resampled by the validity rule before it is counted."""
+    (H, W), the tiles, the pads and the size limits refer to it, and the mask is resampled by the validity rule before it is counted.
+    Under config.SCENE_NODATA the plan depends on the pixels: `img`, the raw scene of that shape, is required (and `net`),
+    and the mask is derived from it on the device exactly as infer_one_img derives it, ANDed with `valid` where one is given."""
     neighbor_queries(config)
+    nodata = scene_nodata_key(config)
+    if nodata is not None:
+        if img is None:
+            raise ValueError("scene_tiles: with SCENE_NODATA the plan depends on the pixels of the scene: pass the raw scene as img=")
+        img = np.asarray(img)
+        lo, hi = scene_nodata_check(img, nodata)
+        if tuple(img.shape[:2]) != tuple(int(v) for v in shape[:2]):
+            raise ValueError(f"img must have the shape {tuple(shape[:2])}, got {tuple(img.shape[:2])}")
+        shape = tuple(shape[:2])
     if len(shape) not in (2, 3) or (len(shape) == 3 and shape[2] != 3):
         raise ValueError(f"shape must be (H, W) or (H, W, 3), got {tuple(shape)}")
     H, W = int(shape[0]), int(shape[1])
@@ -766,13 +787,16 @@ def scene_tiles(shape, config, valid=None, net=None):
     pad = scene_pad_plan((Hm, Wm), config)
     pads = pad[:4] if pad is not None else (0, 0, 0, 0)
     infos, all_xy = _tile_plan(Hm + pads[0] + pads[1], Wm + pads[2] + pads[3], config, padded=pad is not None)
-    if valid is None:
+    if valid is None and nodata is None:
         return TilePlan(_shift_infos(infos, pads), orientations, pads, scale, (Hm, Wm))
-    v8, frac, _ = _valid_plan(valid, (H, W), config)
+    v8, frac = (None, _mask_keys(config)[0]) if valid is None else _valid_plan(valid, (H, W), config)[:2]
     if net is None:
         raise ValueError("scene_tiles needs the model (net=) to count valid pixels on the device")
     device = next(net.parameters()).device
-    valid_d = torch.from_numpy(v8).to(device)
+    valid_d = None if v8 is None else torch.from_numpy(v8).to(device)
+    if nodata is not None:
+        table = nodata_table([(0, H, W)], nodata)
+        valid_d = _scene_nodata_mask(net, nodata, torch.from_numpy(np.ascontiguousarray(img)).to(device), lo, hi, valid_d, table, None).view(H, W)
     if scale is not None:
         valid_d = net.scene_resample(valid_d, *scale, valid_rule=True)
     if any(pads):
@@ -962,14 +986,16 @@ def _scene_groups(imgs, valids, config, n):
         yield group
 
 
-def group_geometry(scenes, any_mask=None):
+def group_geometry(scenes, any_mask=None, all_masked=False):
     """The stack of a group: (Ha, Wa, tables int64 [T,n,8], tile origins int32 [N,2] on the stack, first tile of every
     scene [n+1]); sets every scene's row0.  Table rows are {byte offset, H, W, top, left, H', W', row0} (include/samroad_hip.h).  tables[0]
     packs the scenes (offsets into the ragged u8 [sum H W 3] buffer), tables[1] crops the masks (offsets into the ragged [sum H W]
     outputs) and, if any scene has a mask, tables[2] packs the masks: a masked scene's block is its H x W mask, an unmasked scene's is H' x
-    W' ones with no pads — its whole rectangle is valid, whatever the pad mode."""
+    W' ones with no pads — its whole rectangle is valid, whatever the pad mode.  all_masked (SCENE_NODATA: the device derives an H x W mask
+    for every scene): every row of tables[2] takes the masked-scene form, at the offsets of tables[1]."""
     if any_mask is None:
         any_mask = any(sc.valid is not None for sc in scenes)
+    any_mask = any_mask or all_masked
     n = len(scenes)
     tables = np.zeros((3 if any_mask else 2, n, 8), dtype=np.int64)
     row0 = off = moff = 0
@@ -980,8 +1006,9 @@ def group_geometry(scenes, any_mask=None):
         tables[0, k] = (3 * off, H, W, top, left, Hv, Wv, row0)
         tables[1, k] = (off, H, W, top, left, Hv, Wv, row0)
         if any_mask:
-            tables[2, k] = (moff, H, W, top, left, Hv, Wv, row0) if sc.valid is not None else (moff, Hv, Wv, 0, 0, Hv, Wv, row0)
-            moff += H * W if sc.valid is not None else Hv * Wv
+            own = all_masked or sc.valid is not None
+            tables[2, k] = (moff, H, W, top, left, Hv, Wv, row0) if own else (moff, Hv, Wv, 0, 0, Hv, Wv, row0)
+            moff += H * W if own else Hv * Wv
         xy.append(sc.all_xy + np.array([[0, row0]], dtype=np.int32))
         first.append(first[-1] + len(sc.infos))
         off += H * W
@@ -997,8 +1024,8 @@ def _group_stack(ctx, io, scenes):
     net, config = ctx.net, ctx.config
     pad = scene_pad_plan(scenes[0].shape, config)
     mode, fill = (pad[4], pad[5]) if pad is not None else ("reflect", (0, 0, 0))
-    any_mask = any(sc.valid is not None for sc in scenes)
-    Ha, Wa, tables, all_xy, first = group_geometry(scenes, any_mask)
+    any_mask, nodata = any(sc.valid is not None for sc in scenes), ctx.nodata
+    Ha, Wa, tables, all_xy, first = group_geometry(scenes, any_mask, all_masked=nodata is not None)
 
     def stage(name, n):
         return io.alloc(name, (n,), np.uint8) if io.alloc is not None else np.empty(n, np.uint8)
@@ -1015,6 +1042,11 @@ def _group_stack(ctx, io, scenes):
             elems[off:off + sc.img.size] = sc.img.reshape(-1)
     ragged = io.upload_packed("group_scene", src)
     tables_d = io.upload("group_tables", tables)
+    if nodata is not None and (nodata.min_area > 1 or nodata.grow > 0):      # the scenes' H x W blocks of the derived mask, at tables[1]'s offsets
+        nd_table = nodata_table([(int(off), int(h), int(w)) for off, h, w in tables[1, :, :3]], nodata)
+        nd_table_d = io.upload("nodata_table", nd_table)
+    else:
+        nd_table = nd_table_d = None
     if any_mask:
         msrc = stage("group_mask", int(tables[2, -1, 0] + tables[2, -1, 1] * tables[2, -1, 2]))
         for sc, (off, h, w) in zip(scenes, tables[2, :, :3]):
@@ -1022,6 +1054,12 @@ def _group_stack(ctx, io, scenes):
         mragged = io.upload_packed("group_mask", msrc)
     io.step("upload")
     host = torch.from_numpy(tables)
+    if nodata is not None:                             # SCENE_NODATA: the ragged raw buffer is matched in one launch (it knows nothing of rows);
+        lo, hi = scene_nodata_check(raw, nodata)       # the grow and the area rule run table-driven over the scenes' blocks
+        pixels = ragged.view(torch.from_numpy(raw[:0, :0].reshape(0)).dtype).view(n_px, raw.shape[2])
+        mragged = _scene_nodata_mask(net, nodata, pixels, lo, hi, mragged if any_mask else None, nd_table, nd_table_d)
+        any_mask = True
+        io.step("nodata")
     if ctx.bands is not None:                          # one apply launch over the ragged buffer, then the unchanged pack kernel
         ragged = _scene_bands_front(ctx, io, ragged.view(torch.from_numpy(raw[:0, :0].reshape(0)).dtype).view(n_px, raw.shape[2])).view(-1)
     scene = net.scene_group_pack(ragged, host[0], 3, Ha, Wa, mode, fill, table_dev=tables_d[0])
@@ -1131,7 +1169,7 @@ class _Lane:
 class _BlockingIO:
     """How infer_one_img and the tile-sharded loops move a scene's arrays: one blocking copy each way, pageable memory.  The other
     implementation of the same four operations is _LaneIO.  `lap` (a _Laps) names the steps of pass 1 for the profile."""
-    STEPS = {"upload": "scene upload", "bands": "band select + stretch", "scale": "scene resample", "pad": "scene pad", "pack": "group pack", "select": "tile selection (count kernel + counts D2H)", "fill": "nodata fill",
+    STEPS = {"upload": "scene upload", "nodata": "nodata mask", "bands": "band select + stretch", "scale": "scene resample", "pad": "scene pad", "pack": "group pack", "select": "tile selection (count kernel + counts D2H)", "fill": "nodata fill",
              "pass 1": "pass 1 (GPU)"}
     alloc = None                                       # the pass-2 collate fills plain numpy arrays
 
@@ -1158,7 +1196,7 @@ class _LaneIO:
     """The operations of _BlockingIO on infer_imgs' lane, for ONE scene in flight (`pool`: its page-locked staging): uploads are staged
     and stream-ordered, the counts come back over the copy stream, the pass-2 collate writes straight into the staging buffers.  With the
     profile on, five device events time the scene's pass 1, pass 2 and score download."""
-    STEPS = {"upload": "stage + queue scene upload", "bands": "band select + stretch (upload lane)", "scale": "queue scene resample", "pad": "queue scene pad", "pack": "queue group pack", "select": "tile selection (upload lane)", "pass 1": "queue pass 1"}
+    STEPS = {"upload": "stage + queue scene upload", "nodata": "queue nodata mask", "bands": "band select + stretch (upload lane)", "scale": "queue scene resample", "pad": "queue scene pad", "pack": "queue group pack", "select": "tile selection (upload lane)", "pass 1": "queue pass 1"}
     EVENTS = {"launch pass 1": 0, "normalised": 1, "pass 2 uploaded": 2, "pass 2 launched": 3, "pass 2 on its way back": 4}
 
     def __init__(self, lane, pool, lap):
@@ -1223,6 +1261,7 @@ class _SceneSetup:
         self.bands_luts = {}                             # levels -> the tables of a fixed range on the device, built once per call
         self.scale = scene_scale_key(config)             # SCENE_SCALE as (p, q), or None: no scene takes a step of it
         self.clean = mask_clean_plan(config)             # MASK_CLEAN as a MaskCleanPlan, or None: no scene takes a step of it
+        self.nodata = scene_nodata_key(config)           # SCENE_NODATA as a SceneNodata, or None: no scene takes a step of it
 
     @functools.cached_property
     def features(self):
@@ -1294,15 +1333,23 @@ def _pass1_front(ctx, io, img, valid=None, group=None):
     MASK_CLEAN lives here and nowhere else: on rank 0, behind the normalise and the crop to the real scene and in front of
     the way back and the download, the connected components of each thresholded mask that are too small or too faint are set to 0 in
     place (net.mask_clean: five queued launches, nothing read back); its table travels with the scene's other uploads.
+    SCENE_NODATA lives here and nowhere else: right behind the upload and in front of SCENE_BANDS the validity mask that the
+    device derives from the raw pixels (_scene_nodata_mask: one launch for value / tolerance / match, plus srh_mask_clean and the grow for
+    min_area / grow), ANDed with the caller's mask if there is one, takes the place of the uploaded mask; behind that point the scene "has
+    a mask" (masked) and nothing knows of the key.  The counts follow those kernels (after_compute); no mask is staged or uploaded unless the
+    caller gave one.
     group (SCENE_GROUP; img and valid are None then): a planned group, a list of _GroupScene, takes the place of the one
     scene — one ragged upload and one pack launch build the vertical stack of the scenes (each padded by its own pads) and of their masks,
     then the stack IS the scene of the code below, and one crop launch cuts every scene's window out of the stack's masks; the job
     is the stack's, its `group` the scenes' (see _SceneJob).  Without a group none of its branches is taken."""
     net, config = ctx.net, ctx.config
     if group is not None:
-        masked = [sc for sc in group if sc.valid is not None]
-        if masked:
-            valid, min_frac, fill = _valid_plan(masked[0].valid, masked[0].shape, config)
+        with_mask = [sc for sc in group if sc.valid is not None]
+        masked = bool(with_mask) or ctx.nodata is not None
+        if with_mask:
+            min_frac, fill = _valid_plan(with_mask[0].valid, with_mask[0].shape, config)[1:]
+        elif masked:
+            min_frac, fill = _mask_keys(config)
         pass1_kw, norm_kw, n_orient = ctx.features
         scene, valid_d, all_xy, first, crop_table, crop_table_d = _group_stack(ctx, io, group)
         infos = list(range(all_xy.shape[0]))           # on the stack a tile is known by its index alone
@@ -1318,8 +1365,11 @@ def _pass1_front(ctx, io, img, valid=None, group=None):
         shape = model_shape(scene_shape, ctx.scale)        # the frame of everything between the two resample steps (no key: the scene's)
         pad = scene_pad_plan(shape, config)
         pads = pad[:4] if pad is not None and any(pad[:4]) else None     # all four 0: the launches of a run without the key
+        masked, valid_d = valid is not None or ctx.nodata is not None, None
         if valid is not None:
             valid, min_frac, fill = _valid_plan(valid, scene_shape, config)
+        elif masked:
+            min_frac, fill = _mask_keys(config)
         pass1_kw, norm_kw, n_orient = ctx.features
         scene = io.upload("scene", img)                    # the u8 scene, ONCE; tiles are cropped on the device
         xy_dev = io.upload("xy", all_xy)
@@ -1327,26 +1377,37 @@ def _pass1_front(ctx, io, img, valid=None, group=None):
             clean_table = _mask_clean_images(ctx.clean, [(0, *shape)], shape[0] * shape[1])
         if valid is not None:
             valid_d = io.upload("valid_mask", valid)       # a key of its own: "valid" stages pass 2's pair flags
+        if ctx.nodata is not None and (ctx.nodata.min_area > 1 or ctx.nodata.grow > 0):
+            nd_table = nodata_table([(0, *scene_shape)], ctx.nodata)
+            nd_table_d = io.upload("nodata_table", nd_table)
         io.step("upload")
+        if ctx.nodata is not None:
+            # SCENE_NODATA lives here and nowhere else: right behind the upload and in front of SCENE_BANDS the mask the
+            # device derives from the raw pixels (ANDed with the caller's, if any) takes the place of the uploaded one.  From here on
+            # "this scene has a mask" (masked) is all anything knows
+            lo, hi = scene_nodata_check(img, ctx.nodata)
+            key2 = ctx.nodata.min_area > 1 or ctx.nodata.grow > 0
+            valid_d = _scene_nodata_mask(net, ctx.nodata, scene, lo, hi, valid_d, nd_table if key2 else None, nd_table_d if key2 else None).view(scene_shape)
+            io.step("nodata")
         if ctx.bands is not None:                          # the raw scene -> the u8 [H,W,3] scene of every line below; the raw one is dropped
-            scene = _scene_bands_front(ctx, io, scene, valid_d if valid is not None else None)
+            scene = _scene_bands_front(ctx, io, scene, valid_d, after_compute=ctx.nodata is not None)
         if ctx.scale is not None:                          # the scene -> the model frame; the mask by the validity rule, and the scene-frame
             scene = net.scene_resample(scene, *ctx.scale)  # one is kept for the way back
-            if valid is not None:
+            if masked:
                 valid_scene, valid_d = valid_d, net.scene_resample(valid_d, *ctx.scale, valid_rule=True)
             io.step("scale")
         if pads is not None:
             scene = net.scene_pad(scene, pads, pad[4], pad[5])
-            if valid is not None:                          # the mask by the same rule: reflect / edge mirror its validity, constant padding is nodata
+            if masked:                                     # the mask by the same rule: reflect / edge mirror its validity, constant padding is nodata
                 valid_d = net.scene_pad(valid_d, pads, pad[4], (0, 0, 0))
             io.step("pad")
         job_pads = pads or (0, 0, 0, 0)
     if ctx.clean is not None and clean_table is not None and ctx.rank == 0:
         clean_table_d = io.upload("clean_table", clean_table)     # travels with the scene: the filter below adds no host wait
-    if valid is not None:
+    if masked:
         # every rank holds the scene and the mask, computes the same integer counts and therefore the same kept list: from here
         # on infos / all_xy / xy_dev ARE the kept tiles (a subsequence of an x-outer list is x-outer, so the banded reduce stays valid)
-        kept = select_tiles(io.counts(lambda: net.scene_tile_valid(valid_d, xy_dev), after_compute=pads is not None or group is not None or ctx.scale is not None),
+        kept = select_tiles(io.counts(lambda: net.scene_tile_valid(valid_d, xy_dev), after_compute=pads is not None or group is not None or ctx.scale is not None or ctx.nodata is not None),
                             config.PATCH_SIZE, min_frac)
         io.step("select")
         infos, all_xy = [infos[i] for i in kept], np.ascontiguousarray(all_xy[kept])
@@ -1389,7 +1450,7 @@ def _pass1_front(ctx, io, img, valid=None, group=None):
             job.kp_u8, job.road_u8 = both[0], both[1]
         if job.scale is not None:                      # the way back: both masks to the scene's own size by q/p, 0 on the scene's nodata
             (p, q), job.model_kp_u8, job.model_road_u8 = job.scale, job.kp_u8, job.road_u8
-            job.kp_u8, job.road_u8 = (net.scene_resample(m, q, p, out_shape=scene_shape, zero_where=valid_scene if valid is not None else None)
+            job.kp_u8, job.road_u8 = (net.scene_resample(m, q, p, out_shape=scene_shape, zero_where=valid_scene if masked else None)
                                       for m in (job.model_kp_u8, job.model_road_u8))
         if group is not None:                          # every scene's window of the stack's masks, one launch, one allocation
             job.group = _group_children(group, first, infos)
@@ -1400,7 +1461,7 @@ def _pass1_front(ctx, io, img, valid=None, group=None):
     return job
 
 
-def _scene_bands_front(ctx, io, raw, valid_d=None):
+def _scene_bands_front(ctx, io, raw, valid_d=None, after_compute=False):
     """SCENE_BANDS lives here and nowhere else: the raw scene on the device (u8 / u16 [..., C]; a group's ragged buffer
     [n, C]) -> the u8 [..., 3] scene.  A percentile stretch counts the exact histogram of the selected bands over the valid pixels (before
     any padding or nodata fill), fetches it the way the tile selection fetches its counts, and reads the ranges off it on the host; the
@@ -1410,13 +1471,33 @@ def _scene_bands_front(ctx, io, raw, valid_d=None):
     levels = 256 if raw.dtype == torch.uint8 else 65536
     lut_d = ctx.bands_luts.get(levels)
     if bands.percentile is not None:
-        hist = io.counts(lambda: net.scene_bands_hist(raw, bands.select, valid_d), name="bands_hist")
+        # after_compute: valid_d is what the compute stream derived (SCENE_NODATA), so the upload lane waits for it first
+        hist = io.counts(lambda: net.scene_bands_hist(raw, bands.select, valid_d), name="bands_hist", **(dict(after_compute=True) if after_compute else {}))
         lut_d = io.upload("bands_lut", band_luts(stretch_from_hist(hist, *bands.percentile), bands.gamma, levels))
     elif lut_d is None:
         lut_d = ctx.bands_luts[levels] = io.upload("bands_lut", band_luts(fixed_ranges(bands, levels), bands.gamma, levels))
     scene = net.scene_bands_apply(raw, bands.select, lut_d)
     io.step("bands")
     return scene
+
+
+def _scene_nodata_mask(net, key, raw, lo, hi, and_with, table, table_d):
+    """SCENE_NODATA's device steps: the raw pixels on the device (u8 / u16 [..., C]; a group's ragged buffer [n, C]) -> the
+    flat u8 validity mask, one byte per pixel, that nodata.nodata_ref states: not nodata, ANDed with and_with (the caller's mask, laid out
+    like the result, or None).  With value / tolerance / match alone it is ONE launch.  Otherwise the match writes `hit`, srh_mask_clean —
+    as it is — clears its small components in place (min_area > 1), and the grow (or, without one, a second match on `hit` itself)
+    writes the finished mask; table / table_d describe the scenes' H x W blocks (nodata.nodata_table).  All queued, nothing read back."""
+    match = "any" if key.any else "all"
+    if and_with is not None:
+        and_with = and_with.view(-1)
+    if key.min_area <= 1 and key.grow == 0:
+        return net.scene_nodata_match(raw, lo, hi, match, and_with=and_with, invert=True).view(-1)
+    hit = net.scene_nodata_match(raw, lo, hi, match).view(-1)
+    if key.min_area > 1:
+        net.mask_clean(hit, table, table_dev=table_d, connectivity=key.connectivity)
+    if key.grow > 0:
+        return net.scene_nodata_grow(hit, table, key.grow, and_with=and_with, invert=True, table_dev=table_d)
+    return net.scene_nodata_match(hit.view(-1, 1), [0], [0], and_with=and_with).view(-1)          # not hit: the level of `hit` is 0
 
 
 def _group_children(group, first, kept):
@@ -1548,6 +1629,10 @@ def infer_imgs(net, imgs, config, device=None, tile_sharded=None, pipelined=None
     if clean is not None and 2 * n_group > MASK_CLEAN_MAX_IMAGES:
         raise ValueError(f"MASK_CLEAN filters the two masks of every scene of a group in one call of at most {MASK_CLEAN_MAX_IMAGES} images: "
                          f"SCENE_GROUP = {n_group} is too large, use at most {MASK_CLEAN_MAX_IMAGES // 2}")
+    nodata = scene_nodata_key(config)
+    if nodata is not None and nodata.min_area > 1 and n_group > MASK_CLEAN_MAX_IMAGES:
+        raise ValueError(f"SCENE_NODATA: min_area filters the derived mask of every scene of a group in one call of at most {MASK_CLEAN_MAX_IMAGES} "
+                         f"images: SCENE_GROUP = {n_group} is too large")
     if scene_scale_key(config) is not None and n_group > 1:
         raise ValueError(f"SCENE_SCALE does not combine with SCENE_GROUP = {n_group} (a group's stack holds scenes of one frame): drop one of them")
     valids = _valid_iter(valids)
@@ -2032,8 +2117,21 @@ def main(argv=None):
                          "(numpy.percentile, method lower), overriding stretch of the config's SCENE_BANDS; not with --scene-group")
     ap.add_argument("--gamma", default=None, type=float, metavar="G",
                     help="(extension) gamma of the stretch (out = 255 t^(1/G)), overriding gamma of the config's SCENE_BANDS")
+    ap.add_argument("--nodata", default=None, nargs="+", type=int, metavar="V",
+                    help="(extension) the nodata level of the raw scene, one for every band or one per band, overriding value of the config's "
+                         "SCENE_NODATA: the validity mask is derived from it on the device (and ANDed with --valid-masks / alpha)")
+    ap.add_argument("--nodata-tolerance", default=None, type=int, metavar="T",
+                    help="(extension) a band hits within T levels of the value, overriding tolerance of the config's SCENE_NODATA")
+    ap.add_argument("--nodata-match", default=None, choices=("all", "any"),
+                    help="(extension) all (default): every band must hit; any: one is enough — overriding match of the config's SCENE_NODATA")
+    ap.add_argument("--nodata-min-area", default=None, type=int, metavar="A",
+                    help="(extension) a connected set of fewer than A hit pixels is not nodata, overriding min_area of the config's SCENE_NODATA")
+    ap.add_argument("--nodata-grow", default=None, type=int, metavar="R",
+                    help="(extension) grow nodata by R pixels (0..16), overriding grow of the config's SCENE_NODATA")
     args = ap.parse_args(argv)
     config = load_config(args.config)
+    if any(v is not None for v in (args.nodata, args.nodata_tolerance, args.nodata_match, args.nodata_min_area, args.nodata_grow)):
+        config.SCENE_NODATA = scene_nodata_override(config, args.nodata, args.nodata_tolerance, args.nodata_match, args.nodata_min_area, args.nodata_grow)
     if args.bands is not None or args.stretch_range is not None or args.stretch_percentile is not None or args.gamma is not None:
         config.SCENE_BANDS = scene_bands_override(config, None if args.bands is None else [int(b) for b in args.bands.split(",")],
                                                   args.stretch_range, args.stretch_percentile, args.gamma)
@@ -2056,6 +2154,9 @@ def main(argv=None):
     bands = scene_bands_key(config)              # and a SCENE_BANDS that cannot be used
     scene_scale_key(config)                      # and a SCENE_SCALE that cannot be used (or that meets a SCENE_GROUP)
     mask_clean_plan(config)                      # and a MASK_CLEAN that cannot be used
+    nodata = scene_nodata_key(config)            # and a SCENE_NODATA that cannot be used
+    if nodata is not None and nodata.min_area > 1 and scene_group_key(config) > MASK_CLEAN_MAX_IMAGES:
+        raise ValueError(f"SCENE_NODATA: min_area does not combine with a SCENE_GROUP above {MASK_CLEAN_MAX_IMAGES}")
     if bands is not None and bands.percentile is not None and scene_group_key(config) > 1:
         raise ValueError("SCENE_BANDS: a percentile stretch does not combine with SCENE_GROUP (every scene needs its own tables); use a fixed range")
     if scene_group_key(config) > 1 and args.shard != "scenes" and int(os.environ.get("WORLD_SIZE", "1")) > 1:      # and a SCENE_GROUP

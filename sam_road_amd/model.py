@@ -907,3 +907,73 @@ class SAMRoad(nn.Module):
             for m, rule in live:
                 self.mask_clean(m.view(-1), mc.mask_clean_table([(0, H, W, rule)]), connectivity=plan.connectivity)
         return kp_u8, road_u8
+
+    # ---- scene level, the validity mask from a nodata value (SCENE_NODATA) ------------------------------------------------
+    @staticmethod
+    def _nodata_and(and_with, n, dev):
+        if and_with is None:
+            return None
+        if and_with.device != dev or and_with.dtype not in (torch.uint8, torch.bool) or and_with.numel() != n or not and_with.is_contiguous():
+            raise ValueError(f"and_with must be a contiguous uint8 / bool tensor of {n} pixels on {dev}, got {and_with.dtype} {tuple(and_with.shape)} on {and_with.device}")
+        return and_with
+
+    @torch.no_grad()
+    def scene_nodata_match(self, src, lo, hi, match="all", and_with=None, invert=False, out=None):
+        """Which pixels of a raw scene hold the nodata value (srh_scene_nodata_match): src uint8 / uint16 [..., C] on the GPU (any element-
+        aligned address, 1 <= C <= 16), lo / hi C ints each, the inclusive range of every band; match 'all' (every band inside its range)
+        or 'any' -> a NEW uint8 tensor [...] of 0 / 1 (or `out`, a flat contiguous uint8 view of one byte per pixel): (not hit if invert
+        else hit) & (and_with != 0), and_with a uint8 / bool tensor of one entry per pixel or None.  One launch, no workspace of the
+        library context; the source is not written."""
+        import ctypes
+        dev = src.device
+        ctx, _ = self._weights(dev)
+        codes = {torch.uint8: _lib.SRH_U8, torch.uint16: _lib.SRH_U16}
+        if src.dtype not in codes or src.dim() < 2 or not src.is_contiguous() or not 1 <= src.shape[-1] <= 16 or src.numel() < 1:
+            raise ValueError(f"a raw scene is a contiguous uint8 / uint16 [..., C] tensor with 1 <= C <= 16, got {src.dtype} {tuple(src.shape)}")
+        C = int(src.shape[-1])
+        n = src.numel() // C
+        lo, hi = [int(v) for v in lo], [int(v) for v in hi]
+        if len(lo) != C or len(hi) != C or not all(0 <= v <= 65535 for v in lo + hi):
+            raise ValueError(f"lo and hi must hold {C} ints in 0..65535 each, got {lo!r}, {hi!r}")
+        if match not in _lib.SRH_NODATA_MATCH:
+            raise ValueError(f"match must be one of {tuple(_lib.SRH_NODATA_MATCH)}, got {match!r}")
+        if n > 2 ** 31 - 1:
+            raise ValueError(f"a raw scene has at most 2^31 - 1 pixels, got {n}")
+        and_with = self._nodata_and(and_with, n, dev)
+        if out is None:
+            out = torch.empty(tuple(src.shape[:-1]), dtype=torch.uint8, device=dev)
+        elif out.device != dev or out.dtype != torch.uint8 or out.numel() != n or not out.is_contiguous():
+            raise ValueError(f"out must be a contiguous uint8 tensor of {n} pixels on {dev}, got {out.dtype} {tuple(out.shape)} on {out.device}")
+        with torch.cuda.device(dev):
+            ctx.check(ctx.lib.srh_scene_nodata_match(ctx.handle, src.data_ptr(), codes[src.dtype], n, C, (ctypes.c_int32 * C)(*lo), (ctypes.c_int32 * C)(*hi),
+                                                     _lib.SRH_NODATA_MATCH[match], None if and_with is None else and_with.data_ptr(), 1 if invert else 0,
+                                                     out.data_ptr(), self._stream(dev)), "srh_scene_nodata_match")
+        return out
+
+    @torch.no_grad()
+    def scene_nodata_grow(self, src_u8, table, r, and_with=None, invert=False, table_dev=None, out=None):
+        """The Chebyshev dilation by r (1..16) of every image that `table` describes inside src_u8, a flat contiguous uint8 tensor on the GPU
+        (srh_scene_nodata_grow): table int64 [n,8] on the HOST, one row {byte offset, H, W, ...} per image — columns 3..7 are not read, a
+        mask_clean table serves as it is.  Returns a NEW flat uint8 tensor of src_u8's size (or `out`, which must not overlap src_u8) whose
+        blocks hold (not g if invert else g) & (and_with != 0), g = 1 iff a pixel of the image within distance r is non-zero; and_with is
+        laid out like src_u8, or None.  Bytes outside the blocks are not written.  table_dev: the table on the GPU if the caller has uploaded
+        it already.  One launch, no workspace of the library context."""
+        dev = src_u8.device
+        ctx, _ = self._weights(dev)
+        if src_u8.dtype != torch.uint8 or src_u8.dim() != 1 or not src_u8.is_contiguous() or src_u8.numel() < 1:
+            raise ValueError(f"scene_nodata_grow takes a flat contiguous uint8 tensor, got {src_u8.dtype} {tuple(src_u8.shape)}")
+        r = int(r)
+        if not 1 <= r <= 16:
+            raise ValueError(f"r must be 1 to 16, got {r!r}")
+        t, t_dev = self._group_table(table, table_dev, dev)
+        n = src_u8.numel()
+        and_with = self._nodata_and(and_with, n, dev)
+        if out is None:
+            out = torch.empty((n,), dtype=torch.uint8, device=dev)
+        elif out.device != dev or out.dtype != torch.uint8 or out.numel() != n or not out.is_contiguous():
+            raise ValueError(f"out must be a contiguous uint8 tensor of {n} bytes on {dev}, got {out.dtype} {tuple(out.shape)} on {out.device}")
+        with torch.cuda.device(dev):
+            ctx.check(ctx.lib.srh_scene_nodata_grow(ctx.handle, src_u8.data_ptr(), out.data_ptr(), n, t.data_ptr(), t_dev.data_ptr(), int(t.shape[0]), r,
+                                                    None if and_with is None else and_with.data_ptr(), 1 if invert else 0, self._stream(dev)),
+                      "srh_scene_nodata_grow")
+        return out

@@ -32,6 +32,12 @@ The final map_decoder bias is lowered so that the random network yields sparse m
                                                                     # scene's own masks and on a random mask at density 0.5, per kernel — next to
                                                                     # pass 1's, the pipelined loop with and without the key in turn, and the host
                                                                     # time of mask_clean_ref on the same masks
+    python tools/scene_bench.py --nodata 0 --nodata-tolerance 3 --nodata-min-area 50 --nodata-grow 2 [--bands 4 uint16]    # SCENE_NODATA: the scene
+                                                                    # gets a collar, a fringe and interior specks of the value; "scene_nodata"
+                                                                    # compares the derived mask with nodata_ref (the run ends if they differ) and
+                                                                    # reports the device time of the nodata launches (match alone / the key as
+                                                                    # given, per kernel), pass 1's, the pipelined loop unmasked / keyed / with the
+                                                                    # identical mask passed as valid in turn, and the host time of nodata_ref
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 tools/scene_bench.py    # N GPUs:
         tiles sharded over the ranks (RCCL: packed-weight broadcast, banded canvas reduce, point broadcast, vote gather);
         rank 0 prints ms/scene (max over ranks) and the per-rank stage times
@@ -299,6 +305,104 @@ def mask_clean_report(net, cfg, img, valid, pass1, iters=10):
     return rep
 
 
+def nodata_paint(raw, value, rng):
+    """The synthetic scene of --nodata, IN PLACE: a triangular collar of the value at the origin (about 6 % of the scene), a 3 px fringe of
+    the three levels next to it, 200 isolated pixels and 40 blobs of 5..40 pixels of the value in the interior."""
+    H, W, C = raw.shape
+    levels = 256 if raw.dtype == np.uint8 else 65536
+    yy, xx = np.mgrid[0:H, 0:W]
+    collar = yy * W + xx * H < 0.35 * H * W
+    fringe = ((yy - 3) * W + (xx - 3) * H < 0.35 * H * W) & ~collar
+    near = np.array([value + d if value + 3 < levels else value - d for d in (1, 2, 3)])
+    keep = raw == value                                      # natural pixels of the value itself move one level away
+    raw[keep] = value + 1 if value + 1 < levels else value - 1
+    raw[collar] = value
+    raw[fringe] = near[rng.integers(0, 3, size=(int(fringe.sum()), C))]
+    for k in range(240):
+        h, w = (1, 1) if k < 200 else (int(rng.integers(1, 6)), int(rng.integers(5, 9)))
+        y, x = int(rng.integers(H // 2, H - 8)), int(rng.integers(8, W - 16))
+        raw[y:y + h, x:x + w] = value
+    return raw
+
+
+def nodata_report(args, net, cfg, raw, iters=20):
+    """--nodata: the derived mask against nodata_ref on this scene (the run ends if they differ); device ms of the nodata launches alone
+    (events around each of `iters` runs after a warm-up) for the value-only key and for the key as given, with the per-kernel rows of one
+    profiled run; device ms of pass 1 of the same scene (from the lane's events); ms per scene of the pipelined loop without a mask / with
+    the key / with the identical mask passed as `valid`, alternated; host ms of nodata_ref, the work the key takes off the feeding thread."""
+    import sam_road_amd.inferencer as inf
+    from sam_road_amd import Config, _lib
+    from sam_road_amd.nodata import nodata_ref, nodata_table, scene_nodata_check, scene_nodata_key
+    dev = next(net.parameters()).device
+    ctx = _lib.Context.get(dev.index)
+    key = scene_nodata_key(cfg)
+    H, W = raw.shape[:2]
+    lo, hi = scene_nodata_check(raw, key)
+    raw_d = torch.from_numpy(raw).to(dev)
+    table = nodata_table([(0, H, W)], key)
+    table_d = torch.from_numpy(table).to(dev)
+    t0 = time.perf_counter()
+    want = nodata_ref(raw, key)
+    host_ms = 1e3 * (time.perf_counter() - t0)
+    rep = {"key": dict(cfg.SCENE_NODATA), "raw": [str(raw.dtype), list(raw.shape)], "valid_frac": round(float(want.mean()), 4),
+           "host_ms_nodata_ref": round(host_ms, 1)}
+
+    def measure(k):
+        run = lambda: inf._scene_nodata_mask(net, k, raw_d, lo, hi, None, table, table_d)
+        got = run().view(H, W).cpu().numpy()
+        ref = nodata_ref(raw, k)
+        if not np.array_equal(got, ref):
+            bad = got != ref
+            raise SystemExit(f"the derived mask differs from nodata_ref on {int(bad.sum())} px, rows {np.unique(np.nonzero(bad)[0])[:8].tolist()}")
+        evs = []
+        for _ in range(iters):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            run()
+            e1.record()
+            evs.append((e0, e1))
+        torch.cuda.synchronize()
+        ms = sorted(a.elapsed_time(b) for a, b in evs)
+        ctx.profile_read()
+        ctx.profile_enable(True)
+        run()
+        torch.cuda.synchronize()
+        rows = {r["name"]: round(r["ms"], 4) for r in ctx.profile_read() if r["name"].startswith(("scene_nodata", "mask_clean"))}
+        ctx.profile_enable(False)
+        return {"device_ms_median": round(ms[len(ms) // 2], 4), "device_ms_min_max": [round(ms[0], 4), round(ms[-1], 4)], "kernel_ms_one_call": rows,
+                "equals_nodata_ref": True}
+
+    rep["match_alone"] = measure(key._replace(min_area=1, grow=0))
+    rep["key_as_given"] = measure(key)
+    plain = Config({k: v for k, v in cfg.items() if k != "SCENE_NODATA"})
+    inf._Lane.times = []
+
+    def piped(c, valid, n=12):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in inf.infer_imgs(net, (raw for _ in range(n)), c, **({} if valid is None else dict(valids=(valid for _ in range(n))))):
+            pass
+        torch.cuda.synchronize()
+        return round(1e3 * (time.perf_counter() - t0) / n, 2)
+
+    piped(plain, None, 3), piped(cfg, None, 3), piped(plain, want, 3)
+    inf._Lane.times.clear()
+    runs = {"unmasked": [], "keyed": [], "mask_passed_as_valid": []}
+    for _ in range(3):
+        runs["unmasked"].append(piped(plain, None))
+        runs["keyed"].append(piped(cfg, None))
+        runs["mask_passed_as_valid"].append(piped(plain, want))
+    rep["pipelined_ms_per_scene_runs_of_12_alternated"] = runs
+    p1 = sorted(t[1] for t in inf._Lane.times)
+    rep["pass1_device_ms_median_of_all_scenes_above"] = round(p1[len(p1) // 2], 2) if p1 else None
+    inf._Lane.times = None
+    a = inf.infer_one_img(net, raw, cfg)
+    b = inf.infer_one_img(net, raw, plain, valid=want)
+    rep["keyed_equals_mask_passed"] = all(np.array_equal(x, y) for x, y in zip(a, b))
+    rep["graph_points"], rep["edges"] = int(a[0].shape[0]), int(a[1].shape[0])
+    return rep
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--bias", type=float, default=-2.2)
@@ -325,6 +429,13 @@ def main():
                     help="SCENE_SCALE: the scene is at P/Q model pixels per scene pixel and is resampled on the device (default: the key is absent)")
     ap.add_argument("--mask-clean", nargs="+", default=None, metavar="V",
                     help="MASK_CLEAN: ROAD_MIN_AREA ROAD_MIN_PEAK [KEYPOINT_MIN_AREA KEYPOINT_MIN_PEAK] (default: the key is absent)")
+    ap.add_argument("--nodata", nargs="+", type=int, default=None, metavar="V",
+                    help="SCENE_NODATA: the value (one, or one per band); the synthetic scene gets a collar, a fringe and interior specks of it, the "
+                         "derived mask is compared with nodata_ref, and the nodata launches, pass 1 and the pipelined loop are timed (one GPU; with "
+                         "--bands C DTYPE the raw scene has C bands of that dtype)")
+    ap.add_argument("--nodata-tolerance", type=int, default=None, metavar="T")
+    ap.add_argument("--nodata-grow", type=int, default=None, metavar="R")
+    ap.add_argument("--nodata-min-area", type=int, default=None, metavar="A")
     ap.add_argument("--no-pipelined", action="store_true", help="skip the infer_imgs runs (12- and 48-scene streams)")
     ap.add_argument("--patch", type=int, default=512, metavar="P", help="PATCH_SIZE (default 512)")
     ap.add_argument("--margin", type=int, default=64, metavar="M", help="SAMPLE_MARGIN (default 64)")
@@ -401,6 +512,22 @@ def main():
     coarse = rng.integers(0, 256, size=(H // 8, W // 8, 3)).astype(np.float32)
     img = np.kron(coarse, np.ones((8, 8, 1), np.float32)).astype(np.uint8)
 
+    if args.nodata is not None:
+        if world > 1 or args.scenes is not None or args.valid_frac is not None or args.scale is not None:
+            ap.error("--nodata times one unmasked scene on one GPU (not with --scenes, --valid-frac or --scale)")
+        from sam_road_amd.nodata import scene_nodata_override
+        cfg.SCENE_NODATA = scene_nodata_override(cfg, args.nodata, args.nodata_tolerance, None, args.nodata_min_area, args.nodata_grow)
+        raw = img
+        if args.bands is not None:                         # bands 0..2 hold the synthetic RGB spread over the dtype's range, the rest noise
+            C, dtype = int(args.bands[0]), np.dtype(args.bands[1])
+            mul = 257 if dtype == np.uint16 else 1
+            raw = rng.integers(0, 256 * mul, size=(H, W, C)).astype(dtype)
+            raw[..., :3] = img.astype(dtype) * mul
+            cfg.SCENE_BANDS = {"select": [0, 1, 2]}
+        raw = np.ascontiguousarray(nodata_paint(raw, args.nodata[0], rng))
+        print(json.dumps({"scene": f"synthetic {H}x{W} {raw.dtype} x {raw.shape[2]} with a collar, a fringe and specks of {args.nodata[0]}",
+                          "infer_batch_size": args.batch, "scene_nodata": nodata_report(args, net, cfg, raw)}))
+        return
     bands_report = None
     if args.bands is not None:
         if args.scenes is not None:
