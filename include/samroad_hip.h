@@ -372,6 +372,30 @@ int srh_scene_nodata_match(srh_ctx* ctx, const void* src, int src_dtype, int64_t
 int srh_scene_nodata_grow(srh_ctx* ctx, const uint8_t* src, uint8_t* dst, int64_t bytes, const int64_t* table_host,
                           const int64_t* table_dev, int n, int r, const uint8_t* and_with, int invert, void* stream);
 
+/* The validity mask from the POLYGONS of an area of interest (config key SCENE_AOI; an extension): the even-odd fill of
+ * include and exclude polygons on the device, right behind the upload.  One additive entry; the ABI number stays 11 because nothing
+ * existing changes, and a run without the key does not call it.  (The buffer step is srh_scene_nodata_grow as it is, its invert flag
+ * doing the shrink.)
+ *
+ * srh_scene_aoi_fill: edges int32 [E, 4], rows {y0, x0, y1, x1} in 1/256 px of the pixel-corner frame (pixel (r, c) covers [r, r + 1) x
+ *   [c, c + 1)), every edge oriented y0 < y1, horizontal edges left out; polys int32 [n_include + n_exclude + 1], polygon k owns edges
+ *   polys[k] .. polys[k + 1], the include polygons first.  Both tables are given twice, as srh_mask_clean takes its table: the host
+ *   copy is validated, the device copy (edges 16-byte aligned) is what the kernel reads, and it is never written.  An edge crosses row
+ *   y iff y0 <= 256 y + 128 < y1 and then toggles every pixel of the row from column max(0, ceil(((x0 - 128) dy + (256 y + 128 - y0)
+ *   dx) / (256 dy))) on; a pixel is inside a polygon iff its toggles are odd.  aoi = (n_include ? inside any include polygon : 1) & not
+ *   inside any exclude polygon.  and_with: u8 [H, W] on the device or NULL; invert: 0 / 1.  out u8 [H, W] on the device, any byte
+ *   address: out[i] = (invert ? !aoi : aoi) & (and_with ? and_with[i] != 0 : 1), 0 or 1.  Every byte of out is written exactly once and
+ *   nothing else is.  One launch, no global atomics, no workspace of the context, nothing read back; the result does not depend on
+ *   scheduling.
+ * SRH_ERR_BAD_ARG, and nothing is launched, for a null pointer (and_with excepted), H or W < 1 or H W > 2^31 - 1, n_include or
+ * n_exclude < 0 or more than SRH_AOI_MAX_POLYGONS together, offsets that are not a running sum from 0 to at most SRH_AOI_MAX_EDGES, an
+ * edge with y0 >= y1, a coordinate outside +-2^28, invert outside 0 / 1, a misaligned device edge table, or out overlapping and_with.
+ * Profiler row: scene_aoi_fill. */
+#define SRH_AOI_MAX_POLYGONS 64
+#define SRH_AOI_MAX_EDGES 16384
+int srh_scene_aoi_fill(srh_ctx* ctx, const int32_t* edges_host, const int32_t* edges_dev, const int32_t* polys_host, const int32_t* polys_dev,
+                       int n_include, int n_exclude, int H, int W, const uint8_t* and_with, int invert, uint8_t* out, void* stream);
+
 /* op level (used by the parity tests to localise a failure; same kernels as above) ----------------- */
 
 /* out = act(A[M,K] W[N,K]^T + bias) (+resid); A,W fp16; N%128==0, K%64==0. act: 0/1 GELU/2 ReLU. */

@@ -349,3 +349,26 @@ extern "C" int srh_scene_nodata_grow(srh_ctx* c, const uint8_t* src, uint8_t* ds
     TRYK(c, "scene_nodata_grow", 0, px * (and_with ? 3 : 2), s, launch_scene_nodata_grow(p, grow_max_blocks(table_host, n), s));
     return 0;
 }
+
+// ---- scene level, the validity mask from the polygons of an area of interest (kernel in scene_aoi.hip, behaviour in DESIGN.md §6m) ------------
+static_assert(SRH_AOI_MAX_POLYGONS == AOI_MAX_POLYGONS && SRH_AOI_MAX_EDGES == AOI_MAX_EDGES, "limits of the header and the kernel");
+
+extern "C" int srh_scene_aoi_fill(srh_ctx* c, const int32_t* edges_host, const int32_t* edges_dev, const int32_t* polys_host, const int32_t* polys_dev,
+                                  int n_include, int n_exclude, int H, int W, const uint8_t* and_with, int invert, uint8_t* out, void* stream) {
+    if (!c || !edges_host || !edges_dev || !polys_host || !polys_dev || !out) return fail(c, SRH_ERR_BAD_ARG, "srh_scene_aoi_fill: null argument");
+    if (H < 1 || W < 1 || (double)H * W > (double)AOI_MAX_PIXELS) return fail(c, SRH_ERR_BAD_ARG, "srh_scene_aoi_fill: H and W are at least 1 and H W at most 2^31 - 1");
+    if (invert != 0 && invert != 1) return fail(c, SRH_ERR_BAD_ARG, "srh_scene_aoi_fill: invert is 0 / 1");
+    if (reinterpret_cast<uintptr_t>(edges_dev) & 15) return fail(c, SRH_ERR_BAD_ARG, "srh_scene_aoi_fill: the device edge table is 16-byte aligned");
+    if (!aoi_table_ok(edges_host, polys_host, n_include, n_exclude))
+        return fail(c, SRH_ERR_BAD_ARG, "srh_scene_aoi_fill: an inconsistent table (at most 64 polygons and 16384 edges, offsets a running sum from 0, "
+                                        "every edge y0 < y1, coordinates within +-2^28)");
+    const double px = (double)H * W;
+    if (and_with && ranges_overlap(out, px, and_with, px)) return fail(c, SRH_ERR_BAD_ARG, "srh_scene_aoi_fill: out overlaps and_with");
+    SceneAoiParams p;
+    p.edges = edges_dev; p.polys = polys_dev; p.and_with = and_with; p.out = out; p.n_include = n_include; p.n_exclude = n_exclude; p.H = H; p.W = W;
+    p.invert = invert;
+    hipSetDevice(c->device);
+    hipStream_t s = (hipStream_t)stream;
+    TRYK(c, "scene_aoi_fill", 0, px * (and_with ? 2 : 1) + 16.0 * polys_host[n_include + n_exclude], s, launch_scene_aoi_fill(p, s));
+    return 0;
+}

@@ -9,6 +9,7 @@
 #include "scene_scale_piece.hpp"
 #include "mask_clean_piece.hpp"
 #include "scene_nodata_piece.hpp"
+#include "scene_aoi_piece.hpp"
 
 namespace srh {
 
@@ -208,6 +209,10 @@ int launch_mask_clean(const MaskCleanParams& p, int step, hipStream_t s);
 // on the host (grow_table_ok; max_blocks = grow_max_blocks); -2 for bad parameters.
 int launch_scene_nodata_match(const SceneNodataParams& p, hipStream_t s);
 int launch_scene_nodata_grow(const SceneGrowParams& p, long max_blocks, hipStream_t s);
+// Validity mask from the polygons of an area of interest (scene_aoi.hip; the parameters in scene_aoi_piece.hpp): the even-odd
+// fill of include / exclude polygons given as a device table of edges that has been checked on the host (aoi_table_ok); -2 for bad
+// parameters.
+int launch_scene_aoi_fill(const SceneAoiParams& p, hipStream_t s);
 
 // Bilinear sampler (F.grid_sample, align_corners=False, zeros) on channels-last embeddings.
 struct SampleParams {

@@ -26,9 +26,10 @@ import torch
 
 from . import _lib
 from . import distributed as D
+from .aoi import aoi_edges, aoi_key_of, aoi_pack, aoi_ref, read_geojson, scene_aoi_key, scene_aoi_override
 from .graph_points import extract_graph_points
 from .hostcpu import fill_threads, usable_cpus, worker_threads
-from .mask_clean import idle as _rule_idle, mask_clean_key, mask_clean_override, mask_clean_table
+from .mask_clean import MaskRule, idle as _rule_idle, mask_clean_key, mask_clean_override, mask_clean_table
 from .nodata import nodata_table, scene_nodata_check, scene_nodata_key, scene_nodata_override
 from .resample import map_nodes, model_shape, scene_scale_key, scene_scale_override
 from .radiometry import band_luts, fixed_ranges, scene_bands_check, scene_bands_key, scene_bands_override, stretch_from_hist
@@ -557,16 +558,18 @@ def _host_quiet():
     return cm()
 
 
-def infer_one_img(net, img, config, device=None, valid=None):
+def infer_one_img(net, img, config, device=None, valid=None, aoi=None):
     """reference inferencer.py:61-234: (pred_nodes (row, col), pred_edges, keypoint_mask u8, road_mask u8) of one scene (with the
     garbage collector and numpy's huge-page madvise paused for the duration of the call, see _host_quiet).
     valid (extension; bool or uint8 [H,W], non-zero = valid pixel; None = every pixel): only tiles that hold enough valid pixels are
     run (config.MIN_VALID_FRACTION), nodata pixels are replaced by config.NODATA_FILL on the device copy of the scene, and both masks
     are 0 on nodata, so no graph point lies there.  An all-true mask gives the result of valid=None bit for bit.
     config.SCENE_SCALE (extension): img (and valid) are at another ground resolution than the model's; both passes run on
-    the scene resampled on the device, and the masks [H,W] and the nodes (row, col) come back in the scene's own pixels."""
+    the scene resampled on the device, and the masks [H,W] and the nodes (row, col) come back in the scene's own pixels.
+    aoi (extension): this scene's area of interest, a SCENE_AOI value (aoi.py) that takes the place of the config's key; None =
+    the config's key.  The polygons are rasterised on the device and the result is a validity mask like `valid`, ANDed with it."""
     with _host_quiet():
-        return _infer_one_img(net, img, config, device, valid)
+        return _infer_one_img(net, img, config, device, valid, aoi)
 
 
 MAX_NEIGHBOR_QUERIES_RANGE = (1, 64)
@@ -605,6 +608,7 @@ def _scene_plan(img, config):
     nodata = scene_nodata_key(config)
     if nodata is not None:                                 # SCENE_NODATA: the value(s) against THIS scene's dtype and bands
         scene_nodata_check(img, nodata)
+    scene_aoi_key(config)                                  # SCENE_AOI: a key that cannot be used is refused here
     Hm, Wm = _model_frame(img.shape, scene_scale_key(config))
     pad = scene_pad_plan((Hm, Wm), config)
     top, bottom, left, right = pad[:4] if pad is not None else (0, 0, 0, 0)
@@ -755,7 +759,7 @@ def select_tiles(counts, patch_size, min_valid_fraction):
     return np.flatnonzero((counts > 0) & (counts >= float(min_valid_fraction) * int(patch_size) * int(patch_size)))
 
 
-def scene_tiles(shape, config, valid=None, net=None, img=None):
+def scene_tiles(shape, config, valid=None, net=None, img=None, aoi=None):
     """The tiles infer_one_img runs for a scene of `shape` = (H, W[, 3]): the list of (0, (x0, y0), (x1, y1)) in the reference's
     x-outer / y-inner order.  With `valid` (see infer_one_img) only the kept tiles, selected exactly as infer_one_img selects them: the
     counts come from `net.scene_tile_valid` on the model's device, so `net` is required then (there is no host fallback).  The list is
@@ -765,8 +769,12 @@ def scene_tiles(shape, config, valid=None, net=None, img=None):
     Under config.SCENE_SCALE the plan is that of the MODEL frame: `scale` holds (p, q) ((1, 1) without the key), `model_shape` the frame's
     (H, W), the tiles, the pads and the size limits refer to it, and the mask is resampled by the validity rule before it is counted.
     Under config.SCENE_NODATA the plan depends on the pixels: `img`, the raw scene of that shape, is required (and `net`),
-    and the mask is derived from it on the device exactly as infer_one_img derives it, ANDed with `valid` where one is given."""
+    and the mask is derived from it on the device exactly as infer_one_img derives it, ANDed with `valid` where one is given.
+    Under config.SCENE_AOI (`aoi`: a scene's own value in its place, see infer_one_img) the polygons become a mask as in
+    infer_one_img: on the device when `net` is given, and — the plan depends on no pixel — from aoi.aoi_ref on the host, counted by numpy,
+    when it is not (and no SCENE_NODATA asks for the device)."""
     neighbor_queries(config)
+    aoi = aoi_key_of(aoi) if aoi is not None else scene_aoi_key(config)
     nodata = scene_nodata_key(config)
     if nodata is not None:
         if img is None:
@@ -787,13 +795,28 @@ def scene_tiles(shape, config, valid=None, net=None, img=None):
     pad = scene_pad_plan((Hm, Wm), config)
     pads = pad[:4] if pad is not None else (0, 0, 0, 0)
     infos, all_xy = _tile_plan(Hm + pads[0] + pads[1], Wm + pads[2] + pads[3], config, padded=pad is not None)
-    if valid is None and nodata is None:
+    if valid is None and nodata is None and aoi is None:
         return TilePlan(_shift_infos(infos, pads), orientations, pads, scale, (Hm, Wm))
     v8, frac = (None, _mask_keys(config)[0]) if valid is None else _valid_plan(valid, (H, W), config)[:2]
+    if net is None and aoi is not None and nodata is None:      # the host statement of the same plan
+        from .resample import resample_ref
+        v = aoi_ref((H, W), aoi, v8)
+        if scale is not None:
+            v = resample_ref(v, *scale, None, True, None)
+        if any(pads):
+            width = ((pads[0], pads[1]), (pads[2], pads[3]))
+            v = np.pad(v, width, mode="constant") if pad[4] == "constant" else np.pad(v, width, mode=pad[4])
+        P = int(config.PATCH_SIZE)
+        counts = np.array([int(np.count_nonzero(v[y0:y0 + P, x0:x0 + P])) for x0, y0 in np.asarray(all_xy).tolist()], dtype=np.int64)
+        return TilePlan(_shift_infos([infos[i] for i in select_tiles(counts, P, frac)], pads), orientations, pads, scale, (Hm, Wm))
     if net is None:
         raise ValueError("scene_tiles needs the model (net=) to count valid pixels on the device")
     device = next(net.parameters()).device
     valid_d = None if v8 is None else torch.from_numpy(v8).to(device)
+    if aoi is not None:
+        tab = aoi_edges(aoi, H, W)
+        grow = mask_clean_table([(0, H, W, MaskRule(1, 1, 0))]) if aoi.buffer else None
+        valid_d = _scene_aoi_mask(net, aoi, (H, W), valid_d, tab, None, grow, None).view(H, W)
     if nodata is not None:
         table = nodata_table([(0, H, W)], nodata)
         valid_d = _scene_nodata_mask(net, nodata, torch.from_numpy(np.ascontiguousarray(img)).to(device), lo, hi, valid_d, table, None).view(H, W)
@@ -1169,7 +1192,7 @@ class _Lane:
 class _BlockingIO:
     """How infer_one_img and the tile-sharded loops move a scene's arrays: one blocking copy each way, pageable memory.  The other
     implementation of the same four operations is _LaneIO.  `lap` (a _Laps) names the steps of pass 1 for the profile."""
-    STEPS = {"upload": "scene upload", "nodata": "nodata mask", "bands": "band select + stretch", "scale": "scene resample", "pad": "scene pad", "pack": "group pack", "select": "tile selection (count kernel + counts D2H)", "fill": "nodata fill",
+    STEPS = {"upload": "scene upload", "aoi": "area of interest mask", "nodata": "nodata mask", "bands": "band select + stretch", "scale": "scene resample", "pad": "scene pad", "pack": "group pack", "select": "tile selection (count kernel + counts D2H)", "fill": "nodata fill",
              "pass 1": "pass 1 (GPU)"}
     alloc = None                                       # the pass-2 collate fills plain numpy arrays
 
@@ -1196,7 +1219,7 @@ class _LaneIO:
     """The operations of _BlockingIO on infer_imgs' lane, for ONE scene in flight (`pool`: its page-locked staging): uploads are staged
     and stream-ordered, the counts come back over the copy stream, the pass-2 collate writes straight into the staging buffers.  With the
     profile on, five device events time the scene's pass 1, pass 2 and score download."""
-    STEPS = {"upload": "stage + queue scene upload", "nodata": "queue nodata mask", "bands": "band select + stretch (upload lane)", "scale": "queue scene resample", "pad": "queue scene pad", "pack": "queue group pack", "select": "tile selection (upload lane)", "pass 1": "queue pass 1"}
+    STEPS = {"upload": "stage + queue scene upload", "aoi": "queue area of interest mask", "nodata": "queue nodata mask", "bands": "band select + stretch (upload lane)", "scale": "queue scene resample", "pad": "queue scene pad", "pack": "queue group pack", "select": "tile selection (upload lane)", "pass 1": "queue pass 1"}
     EVENTS = {"launch pass 1": 0, "normalised": 1, "pass 2 uploaded": 2, "pass 2 launched": 3, "pass 2 on its way back": 4}
 
     def __init__(self, lane, pool, lap):
@@ -1262,6 +1285,8 @@ class _SceneSetup:
         self.scale = scene_scale_key(config)             # SCENE_SCALE as (p, q), or None: no scene takes a step of it
         self.clean = mask_clean_plan(config)             # MASK_CLEAN as a MaskCleanPlan, or None: no scene takes a step of it
         self.nodata = scene_nodata_key(config)           # SCENE_NODATA as a SceneNodata, or None: no scene takes a step of it
+        self.aoi = scene_aoi_key(config)                 # SCENE_AOI as a SceneAoi, or None: no scene takes a step of it (unless it brings its own)
+        self.aoi_tables = {}                             # (H, W) -> the host tables of the CONFIG's key, built once per scene size
 
     @functools.cached_property
     def features(self):
@@ -1316,7 +1341,7 @@ class _SceneJob:
     model_masks: list = None
 
 
-def _pass1_front(ctx, io, img, valid=None, group=None):
+def _pass1_front(ctx, io, img, valid=None, group=None, aoi=None):
     """Pass 1 of one scene, queued (GPU): plan, upload, [band step,] [resample,] [border padding,] [tile selection, nodata fill,] crop ->
     encoder -> decoder -> fused canvases, [canvas reduce,] normalise[, masks cropped back][, small components dropped][, masks resampled
     back].  `io` decides how arrays travel and when the host waits
@@ -1338,6 +1363,10 @@ def _pass1_front(ctx, io, img, valid=None, group=None):
     min_area / grow), ANDed with the caller's mask if there is one, takes the place of the uploaded mask; behind that point the scene "has
     a mask" (masked) and nothing knows of the key.  The counts follow those kernels (after_compute); no mask is staged or uploaded unless the
     caller gave one.
+    SCENE_AOI lives here and nowhere else: right behind the upload, in front of SCENE_NODATA and SCENE_BANDS, the mask the
+    device rasterises from the polygons (_scene_aoi_mask: one launch, plus the grow for a buffer; `aoi`, a scene's own SCENE_AOI value, takes
+    the place of the config's key), ANDed with the caller's mask, takes the place of the uploaded one; SCENE_NODATA then ANDs its own into it.
+    The edge table travels with the scene's other uploads; no mask is staged or uploaded unless the caller gave one.
     group (SCENE_GROUP; img and valid are None then): a planned group, a list of _GroupScene, takes the place of the one
     scene — one ragged upload and one pack launch build the vertical stack of the scenes (each padded by its own pads) and of their masks,
     then the stack IS the scene of the code below, and one crop launch cuts every scene's window out of the stack's masks; the job
@@ -1355,17 +1384,18 @@ def _pass1_front(ctx, io, img, valid=None, group=None):
         infos = list(range(all_xy.shape[0]))           # on the stack a tile is known by its index alone
         xy_dev = io.upload("xy", all_xy)
         shape, pads, job_pads = tuple(int(v) for v in scene.shape[:2]), None, (0, 0, 0, 0)
-        scene_shape = shape
+        scene_shape, aoi = shape, None                 # SCENE_AOI does not combine with a group (refused by infer_imgs)
         if ctx.clean is not None:                      # MASK_CLEAN: one image per mask and scene, at its place in scene_group_crop's output
             n_px = sum(sc.shape[0] * sc.shape[1] for sc in group)
             clean_table = _mask_clean_images(ctx.clean, [(int(off), *sc.shape) for sc, off in zip(group, crop_table[:, 0])], n_px)
     else:
         img, infos, all_xy = _scene_plan(img, config)
+        aoi = aoi_key_of(aoi) if aoi is not None else ctx.aoi
         scene_shape = tuple(int(v) for v in img.shape[:2])
         shape = model_shape(scene_shape, ctx.scale)        # the frame of everything between the two resample steps (no key: the scene's)
         pad = scene_pad_plan(shape, config)
         pads = pad[:4] if pad is not None and any(pad[:4]) else None     # all four 0: the launches of a run without the key
-        masked, valid_d = valid is not None or ctx.nodata is not None, None
+        masked, valid_d = valid is not None or ctx.nodata is not None or aoi is not None, None
         if valid is not None:
             valid, min_frac, fill = _valid_plan(valid, scene_shape, config)
         elif masked:
@@ -1380,7 +1410,21 @@ def _pass1_front(ctx, io, img, valid=None, group=None):
         if ctx.nodata is not None and (ctx.nodata.min_area > 1 or ctx.nodata.grow > 0):
             nd_table = nodata_table([(0, *scene_shape)], ctx.nodata)
             nd_table_d = io.upload("nodata_table", nd_table)
+        if aoi is not None:
+            aoi_tab = ctx.aoi_tables.get(scene_shape) if aoi is ctx.aoi else None
+            if aoi_tab is None:
+                aoi_tab = aoi_edges(aoi, *scene_shape)
+                if aoi is ctx.aoi:
+                    ctx.aoi_tables[scene_shape] = aoi_tab
+            aoi_tab_d = io.upload("aoi_table", aoi_pack(*aoi_tab[:2]))
+            aoi_grow = mask_clean_table([(0, *scene_shape, MaskRule(1, 1, 0))]) if aoi.buffer else None
+            aoi_grow_d = io.upload("aoi_grow_table", aoi_grow) if aoi.buffer else None
         io.step("upload")
+        if aoi is not None:
+            # SCENE_AOI lives here and nowhere else: the mask rasterised from the polygons, ANDed with the caller's, takes
+            # the place of the uploaded one; SCENE_NODATA below ANDs its own into it
+            valid_d = _scene_aoi_mask(net, aoi, scene_shape, valid_d, aoi_tab, aoi_tab_d, aoi_grow, aoi_grow_d).view(scene_shape)
+            io.step("aoi")
         if ctx.nodata is not None:
             # SCENE_NODATA lives here and nowhere else: right behind the upload and in front of SCENE_BANDS the mask the
             # device derives from the raw pixels (ANDed with the caller's, if any) takes the place of the uploaded one.  From here on
@@ -1390,7 +1434,7 @@ def _pass1_front(ctx, io, img, valid=None, group=None):
             valid_d = _scene_nodata_mask(net, ctx.nodata, scene, lo, hi, valid_d, nd_table if key2 else None, nd_table_d if key2 else None).view(scene_shape)
             io.step("nodata")
         if ctx.bands is not None:                          # the raw scene -> the u8 [H,W,3] scene of every line below; the raw one is dropped
-            scene = _scene_bands_front(ctx, io, scene, valid_d, after_compute=ctx.nodata is not None)
+            scene = _scene_bands_front(ctx, io, scene, valid_d, after_compute=ctx.nodata is not None or aoi is not None)
         if ctx.scale is not None:                          # the scene -> the model frame; the mask by the validity rule, and the scene-frame
             scene = net.scene_resample(scene, *ctx.scale)  # one is kept for the way back
             if masked:
@@ -1407,7 +1451,7 @@ def _pass1_front(ctx, io, img, valid=None, group=None):
     if masked:
         # every rank holds the scene and the mask, computes the same integer counts and therefore the same kept list: from here
         # on infos / all_xy / xy_dev ARE the kept tiles (a subsequence of an x-outer list is x-outer, so the banded reduce stays valid)
-        kept = select_tiles(io.counts(lambda: net.scene_tile_valid(valid_d, xy_dev), after_compute=pads is not None or group is not None or ctx.scale is not None or ctx.nodata is not None),
+        kept = select_tiles(io.counts(lambda: net.scene_tile_valid(valid_d, xy_dev), after_compute=pads is not None or group is not None or ctx.scale is not None or ctx.nodata is not None or aoi is not None),
                             config.PATCH_SIZE, min_frac)
         io.step("select")
         infos, all_xy = [infos[i] for i in kept], np.ascontiguousarray(all_xy[kept])
@@ -1500,6 +1544,21 @@ def _scene_nodata_mask(net, key, raw, lo, hi, and_with, table, table_d):
     return net.scene_nodata_match(hit.view(-1, 1), [0], [0], and_with=and_with).view(-1)          # not hit: the level of `hit` is 0
 
 
+def _scene_aoi_mask(net, key, shape, and_with, tables, table_d, grow_table, grow_table_d):
+    """SCENE_AOI's device steps: the u8 [H, W] validity mask that aoi.aoi_ref states, ANDed with and_with (the caller's mask
+    [H, W], or None).  Without a buffer it is ONE launch.  With one the fill writes the area (inverted for a negative buffer), and
+    srh_scene_nodata_grow — as it is — grows it by |buffer|, its invert flag turning the grown complement back, and takes and_with.
+    tables: aoi.aoi_edges' tuple; table_d: aoi.aoi_pack of it on the device; grow_table / grow_table_d: the one H x W block of the grow.
+    All queued, nothing read back."""
+    edges, polys, n_include, n_exclude = tables
+    if key.buffer == 0:
+        return net.scene_aoi_fill(shape, edges, polys, n_include, n_exclude, and_with=and_with, table_dev=table_d)
+    shrink = key.buffer < 0
+    area = net.scene_aoi_fill(shape, edges, polys, n_include, n_exclude, invert=shrink, table_dev=table_d)
+    return net.scene_nodata_grow(area.view(-1), grow_table, abs(key.buffer), and_with=None if and_with is None else and_with.view(-1), invert=shrink,
+                                 table_dev=grow_table_d)
+
+
 def _group_children(group, first, kept):
     """One child job per scene of a group: `kept`, ascending indices into the group's candidate tile list (scene k's candidates are
     first[k] .. first[k + 1]), mapped back to the scenes.  A child's tiles are its own, in its own real frame; [lo, hi) are its rows of
@@ -1576,10 +1635,10 @@ def _scene_frame(job, result, scene_masks):
     return map_nodes(nodes, job.shape, *job.scale), edges, scene_masks[0], scene_masks[1]
 
 
-def _infer_one_img(net, img, config, device=None, valid=None):
+def _infer_one_img(net, img, config, device=None, valid=None, aoi=None):
     ctx = _SceneSetup(net, config, device, sharded=True)
     lap = _Laps("infer_one_img", sync=ctx.device)      # tuning aid: wall time of each stage (synchronises the device)
-    job = _pass1_front(ctx, _BlockingIO(ctx.device, lap), img, valid)
+    job = _pass1_front(ctx, _BlockingIO(ctx.device, lap), img, valid, aoi=aoi)
     kp_mask = road_mask = scene_masks = None
     if job.kp_u8 is not None:                          # rank 0 of a scene that ran
         kp_mask, road_mask = job.kp_u8.cpu().numpy(), job.road_u8.cpu().numpy()
@@ -1596,7 +1655,7 @@ def _valid_iter(valids):
     return itertools.repeat(None) if valids is None else itertools.chain(iter(valids), itertools.repeat(None))
 
 
-def infer_imgs(net, imgs, config, device=None, tile_sharded=None, pipelined=None, valids=None, group=None):
+def infer_imgs(net, imgs, config, device=None, tile_sharded=None, pipelined=None, valids=None, group=None, aois=None):
     """infer_one_img over a sequence of scenes, as a generator of the same tuples in the same order — software-pipelined on
     one GPU: while the device runs pass 1 of scene i+1, the host does scene i's mask -> points -> pass-2 queries; scene i's
     TopoNet batches are queued behind that pass 1 and its edge vote runs while scene i+2 is on the device.  One compute stream
@@ -1618,7 +1677,10 @@ def infer_imgs(net, imgs, config, device=None, tile_sharded=None, pipelined=None
     host stages run one scene per worker thread.  The tuples and their order do not change; a group's results are yielded once the group
     is finished, the last, shorter group when the input ends, and a group of one scene takes the single-scene path.  The tile batches
     are composed differently from a scene's own, so on the GPU the masks agree with infer_one_img's within a level (tests/tolerances.py,
-    BATCH_INDEP_SCORE), not bit for bit.  Only this one-process loop groups: with a tile-sharded mode the key is a ValueError."""
+    BATCH_INDEP_SCORE), not bit for bit.  Only this one-process loop groups: with a tile-sharded mode the key is a ValueError.
+    aois: areas of interest parallel to imgs, as valids is: an entry is a SCENE_AOI value that takes the place of the config's
+    key for that scene, None the config's key.  SCENE_AOI does not combine with a group: one pixel-frame area for a stream of chips has no
+    meaning."""
     neighbor_queries(config)                          # fail before any scene touches the device
     fuse_window(config)
     tta_plan(config)
@@ -1635,7 +1697,9 @@ def infer_imgs(net, imgs, config, device=None, tile_sharded=None, pipelined=None
                          f"images: SCENE_GROUP = {n_group} is too large")
     if scene_scale_key(config) is not None and n_group > 1:
         raise ValueError(f"SCENE_SCALE does not combine with SCENE_GROUP = {n_group} (a group's stack holds scenes of one frame): drop one of them")
-    valids = _valid_iter(valids)
+    if n_group > 1 and (scene_aoi_key(config) is not None or aois is not None):
+        raise ValueError(f"SCENE_AOI does not combine with SCENE_GROUP = {n_group} (the polygons are in the pixel frame of ONE scene): drop one of them")
+    valids, aois = _valid_iter(valids), _valid_iter(aois)
     if D.is_distributed() if tile_sharded is None else tile_sharded:
         if n_group > 1:
             raise ValueError(f"SCENE_GROUP = {n_group} applies to the one-process scene loop (tile_sharded=False, CLI --shard scenes); a "
@@ -1643,10 +1707,10 @@ def infer_imgs(net, imgs, config, device=None, tile_sharded=None, pipelined=None
         if pipelined is None:
             pipelined = _cfg_switch(config.TILE_SHARD_PIPELINE, False)
         if pipelined:
-            yield from _infer_imgs_tile_sharded(net, imgs, config, device, valids=valids)
+            yield from _infer_imgs_tile_sharded(net, imgs, config, device, valids=valids, aois=aois)
         else:
             for img in imgs:
-                yield infer_one_img(net, img, config, device=device, valid=next(valids))
+                yield infer_one_img(net, img, config, device=device, valid=next(valids), aoi=next(aois))
         return
     if n_group > 1 and bands is not None and bands.percentile is not None:
         raise ValueError("SCENE_BANDS: a percentile stretch needs every scene's own tables and a host round trip in the middle of a group; "
@@ -1657,9 +1721,9 @@ def infer_imgs(net, imgs, config, device=None, tile_sharded=None, pipelined=None
     pools = [_StagingPool(device), _StagingPool(device)]
     lap = _Laps("infer_imgs")                          # tuning aid: host wall time of each step (no device synchronisation)
 
-    def launch_pass1(img, pool, valid=None, group=None):           # G1: upload, pass 1, normalise, masks on their way to the host
+    def launch_pass1(img, pool, valid=None, group=None, aoi=None):           # G1: upload, pass 1, normalise, masks on their way to the host
         io = _LaneIO(lane, pool, lap)
-        job = _pass1_front(ctx, io, img, valid, group)
+        job = _pass1_front(ctx, io, img, valid, group, aoi=aoi)
         job.io = io
         if job.empty:                                  # zero masks, no nodes (a group: every child is empty)
             job.masks = [torch.zeros(job.shape, dtype=torch.uint8) for _ in range(2)] if group is None else None
@@ -1727,7 +1791,7 @@ def infer_imgs(net, imgs, config, device=None, tile_sharded=None, pipelined=None
     if img is None:
         return
     with _host_quiet():
-        cur = launch_pass1(img, pools[0], next(valids))
+        cur = launch_pass1(img, pools[0], next(valids), aoi=next(aois))
     prev, i = None, 0
     while cur is not None:
         with _host_quiet():
@@ -1737,7 +1801,7 @@ def infer_imgs(net, imgs, config, device=None, tile_sharded=None, pipelined=None
                 _poll_finite(net, device)
             lap("wait for pass-1 masks")
             img = next(it, None)
-            nxt = launch_pass1(img, pools[(i + 1) % 2], next(valids)) if img is not None else None
+            nxt = launch_pass1(img, pools[(i + 1) % 2], next(valids), aoi=next(aois)) if img is not None else None
             res = finish(prev) if prev is not None else None
         if prev is not None:
             yield res
@@ -1895,7 +1959,7 @@ def _infer_imgs_grouped(ctx, lane, pools, lap, imgs, valids, n_group, launch_pas
         host_pool.shutdown(wait=False)
 
 
-def _infer_imgs_tile_sharded(net, imgs, config, device=None, stats=None, valids=None):
+def _infer_imgs_tile_sharded(net, imgs, config, device=None, stats=None, valids=None, aois=None):
     """Tile-sharded scenes (BASELINE configs[3]: ONE scene's tiles over the ranks of a node), software-pipelined like infer_imgs:
     every rank queues pass 1 of scene i+1 on its GPU BEFORE the host stages of scene i, so that rank 0's serial section (mask ->
     graph points, reference graph_extraction.py:130-139 / graph_utils.py:572-591, and the final vote merge) runs while all GPUs —
@@ -1912,11 +1976,11 @@ def _infer_imgs_tile_sharded(net, imgs, config, device=None, stats=None, valids=
     for k in ("pass1_queue_ms", "points_host_ms", "pass2_ms", "merge_host_ms", "canvas_bytes", "points_bytes", "votes_bytes", "scenes"):
         stats.setdefault(k, 0.0)
 
-    valids = _valid_iter(valids)
+    valids, aois = _valid_iter(valids), _valid_iter(aois)
 
-    def stage1(img, valid=None):
+    def stage1(img, valid=None, aoi=None):
         t0 = time.perf_counter()
-        job = _pass1_front(ctx, io, img, valid)
+        job = _pass1_front(ctx, io, img, valid, aoi=aoi)
         if job.bands is not None:
             # this rank's own share: the band it ships to rank 0 (rank 0: what it receives), so that per-rank statistics are per rank
             x0, x1 = job.bands[rank]
@@ -1952,11 +2016,11 @@ def _infer_imgs_tile_sharded(net, imgs, config, device=None, stats=None, valids=
     if img is None:
         return
     with _host_quiet():
-        cur = stage1(img, next(valids))
+        cur = stage1(img, next(valids), next(aois))
     while cur is not None:
         with _host_quiet():
             img = next(it, None)
-            nxt = stage1(img, next(valids)) if img is not None else None        # the next scene's pass 1 is on the device before this scene's host work
+            nxt = stage1(img, next(valids), next(aois)) if img is not None else None        # the next scene's pass 1 is on the device before this scene's host work
             res = stage2(cur)
         stats["scenes"] += 1
         yield res
@@ -2128,8 +2192,30 @@ def main(argv=None):
                     help="(extension) a connected set of fewer than A hit pixels is not nodata, overriding min_area of the config's SCENE_NODATA")
     ap.add_argument("--nodata-grow", default=None, type=int, metavar="R",
                     help="(extension) grow nodata by R pixels (0..16), overriding grow of the config's SCENE_NODATA")
+    ap.add_argument("--aoi", default=None, nargs="+", metavar="FILE",
+                    help="(extension) the area of interest as GeoJSON (Polygon, MultiPolygon, Feature, FeatureCollection, GeometryCollection), [x, y] "
+                         "pixel coordinates unless --aoi-geotransform is given: one file for every scene, or one per --images entry ('-' for a scene "
+                         "without one), overriding include of the config's SCENE_AOI; rasterised on the device and ANDed with the other masks")
+    ap.add_argument("--aoi-exclude", default=None, nargs="+", metavar="FILE",
+                    help="(extension) GeoJSON files whose polygons are cut out of every scene's area, overriding exclude of the config's SCENE_AOI")
+    ap.add_argument("--aoi-geotransform", default=None, nargs=6, type=float, metavar="G",
+                    help="(extension) the six numbers that map (col, row) to the polygons' map coordinates: X = G0 + col G1 + row G2, Y = G3 + col G4 + "
+                         "row G5, overriding geotransform of the config's SCENE_AOI")
+    ap.add_argument("--aoi-buffer", default=None, type=int, metavar="B",
+                    help="(extension) grow (B > 0) or shrink (B < 0) the area by |B| pixels (-16..16), overriding buffer of the config's SCENE_AOI")
     args = ap.parse_args(argv)
     config = load_config(args.config)
+    job_aois = None
+    if any(v is not None for v in (args.aoi, args.aoi_exclude, args.aoi_geotransform, args.aoi_buffer)):
+        if args.aoi is not None and len(args.aoi) > 1 and (args.images is None or len(args.aoi) != len(args.images)):
+            ap.error("--aoi takes one file for all scenes or exactly one entry per --images entry ('-' for a scene without one)")
+        exclude = None if args.aoi_exclude is None else [poly for path in args.aoi_exclude for poly in read_geojson(path)]
+        shared = read_geojson(args.aoi[0]) if args.aoi is not None and len(args.aoi) == 1 and args.aoi[0] != "-" else None
+        config.SCENE_AOI = scene_aoi_override(config, shared, exclude, args.aoi_geotransform, args.aoi_buffer)
+        if args.aoi is not None and len(args.aoi) > 1:       # a scene's own file takes the place of include for that scene
+            job_aois = [None if path == "-" else scene_aoi_override(config, read_geojson(path)) for path in args.aoi]
+            for a in job_aois:
+                aoi_key_of(a)
     if any(v is not None for v in (args.nodata, args.nodata_tolerance, args.nodata_match, args.nodata_min_area, args.nodata_grow)):
         config.SCENE_NODATA = scene_nodata_override(config, args.nodata, args.nodata_tolerance, args.nodata_match, args.nodata_min_area, args.nodata_grow)
     if args.bands is not None or args.stretch_range is not None or args.stretch_percentile is not None or args.gamma is not None:
@@ -2155,6 +2241,8 @@ def main(argv=None):
     scene_scale_key(config)                      # and a SCENE_SCALE that cannot be used (or that meets a SCENE_GROUP)
     mask_clean_plan(config)                      # and a MASK_CLEAN that cannot be used
     nodata = scene_nodata_key(config)            # and a SCENE_NODATA that cannot be used
+    if (scene_aoi_key(config) is not None or job_aois is not None) and scene_group_key(config) > 1:      # and a SCENE_AOI
+        raise ValueError("SCENE_AOI does not combine with SCENE_GROUP (the polygons are in the pixel frame of ONE scene)")
     if nodata is not None and nodata.min_area > 1 and scene_group_key(config) > MASK_CLEAN_MAX_IMAGES:
         raise ValueError(f"SCENE_NODATA: min_area does not combine with a SCENE_GROUP above {MASK_CLEAN_MAX_IMAGES}")
     if bands is not None and bands.percentile is not None and scene_group_key(config) > 1:
@@ -2195,6 +2283,7 @@ def main(argv=None):
     if by_scene:
         jobs = jobs[rank::world]                 # independent scenes: round-robin over the ranks, nothing to exchange
         job_masks = job_masks[rank::world]
+        job_aois = job_aois[rank::world] if job_aois is not None else None
     use_alpha = args.valid_masks is None and any(has_alpha(p) for _, p in jobs)      # headers only; mask files take precedence
     masked = args.valid_masks is not None or use_alpha
     import collections
@@ -2257,7 +2346,8 @@ def main(argv=None):
     # encoding and pickling (tens of ms per 2048^2 scene) run on two writer threads so that the loop goes straight back to the GPU.
     total_inference_seconds = 0.0
     results = infer_imgs(net, scenes(), config, device=device, tile_sharded=world > 1 and not by_scene,
-                         pipelined=True if args.shard == "tiles-pipelined" else None, **(dict(valids=valids()) if masked else {}))
+                         pipelined=True if args.shard == "tiles-pipelined" else None, **(dict(valids=valids()) if masked else {}),
+                         **(dict(aois=job_aois) if job_aois is not None else {}))
     with ThreadPoolExecutor(2) as writer:
         pending = []
         for img_id, path in jobs:

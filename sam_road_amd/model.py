@@ -977,3 +977,43 @@ class SAMRoad(nn.Module):
                                                     None if and_with is None else and_with.data_ptr(), 1 if invert else 0, self._stream(dev)),
                       "srh_scene_nodata_grow")
         return out
+
+    # ---- scene level, the validity mask from the polygons of an area of interest (SCENE_AOI) -------------------------------
+    @torch.no_grad()
+    def scene_aoi_fill(self, shape, edges, polys, n_include, n_exclude, and_with=None, invert=False, table_dev=None, out=None):
+        """The even-odd fill of include / exclude polygons over a scene of shape (H, W) (srh_scene_aoi_fill): edges int32 [E, 4] and polys
+        int32 [n_include + n_exclude + 1] on the HOST, the tables of aoi.aoi_edges -> a NEW uint8 [H, W] tensor of 0 / 1 on the model's
+        device (or `out`, a contiguous uint8 tensor of H W bytes there): (not aoi if invert else aoi) & (and_with != 0), and_with a uint8 /
+        bool tensor of one entry per pixel or None.  table_dev: aoi.aoi_pack(edges, polys) on the GPU (a flat int32 tensor at a 16-byte
+        aligned address) if the caller has uploaded it already.  One launch, no workspace of the library context, nothing read back."""
+        import numpy as np
+        from . import aoi as _aoi
+        dev = next(self.parameters()).device
+        ctx, _ = self._weights(dev)
+        H, W = int(shape[0]), int(shape[1])
+        if H < 1 or W < 1 or H * W > 2 ** 31 - 1:
+            raise ValueError(f"a scene has at least 1 x 1 and at most 2^31 - 1 pixels, got {(H, W)}")
+        e = torch.from_numpy(np.ascontiguousarray(edges, dtype=np.int32).reshape(-1, 4))
+        o = torch.from_numpy(np.ascontiguousarray(polys, dtype=np.int32).reshape(-1))
+        n_include, n_exclude = int(n_include), int(n_exclude)
+        if n_include < 0 or n_exclude < 0 or o.numel() != n_include + n_exclude + 1 or int(o[-1]) != e.shape[0]:
+            raise ValueError(f"polys holds n_include + n_exclude + 1 offsets that end at the number of edges, got {o.numel()} offsets for "
+                             f"{n_include} + {n_exclude} polygons and {e.shape[0]} edges")
+        packed = torch.from_numpy(_aoi.aoi_pack(e.numpy(), o.numpy()))
+        if table_dev is None:
+            table_dev = packed.to(dev)
+        if table_dev.device != dev or table_dev.dtype != torch.int32 or tuple(table_dev.shape) != tuple(packed.shape) or not table_dev.is_contiguous():
+            raise ValueError(f"table_dev must be aoi_pack(edges, polys) as a contiguous int32 {tuple(packed.shape)} tensor on {dev}")
+        n = H * W
+        and_with = self._nodata_and(and_with, n, dev)
+        if out is None:
+            out = torch.empty((H, W), dtype=torch.uint8, device=dev)
+        elif out.device != dev or out.dtype != torch.uint8 or out.numel() != n or not out.is_contiguous():
+            raise ValueError(f"out must be a contiguous uint8 tensor of {n} pixels on {dev}, got {out.dtype} {tuple(out.shape)} on {out.device}")
+        n_rows = max(int(e.shape[0]), 1)
+        with torch.cuda.device(dev):
+            ctx.check(ctx.lib.srh_scene_aoi_fill(ctx.handle, packed.data_ptr(), table_dev.data_ptr(), packed.data_ptr() + 16 * n_rows,
+                                                 table_dev.data_ptr() + 16 * n_rows, n_include, n_exclude, H, W,
+                                                 None if and_with is None else and_with.data_ptr(), 1 if invert else 0, out.data_ptr(),
+                                                 self._stream(dev)), "srh_scene_aoi_fill")
+        return out

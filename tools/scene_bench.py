@@ -38,6 +38,12 @@ The final map_decoder bias is lowered so that the random network yields sparse m
                                                                     # reports the device time of the nodata launches (match alone / the key as
                                                                     # given, per kernel), pass 1's, the pipelined loop unmasked / keyed / with the
                                                                     # identical mask passed as valid in turn, and the host time of nodata_ref
+    python tools/scene_bench.py --aoi-frac 0.4 [--scene 4096 --no-pipelined]    # SCENE_AOI: a star polygon that covers about 0.4 of the scene;
+                                                                    # "scene_aoi" compares the device mask with aoi_ref (the run ends if they
+                                                                    # differ) for the star, a hexagon, a 1000-vertex circle and a ring at the
+                                                                    # 16384-edge limit, and reports the device time of scene_aoi_fill alone for
+                                                                    # each, pass 1's, the pipelined loop unmasked / keyed / with the identical
+                                                                    # mask passed as valid in turn, and the host time of aoi_ref
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 tools/scene_bench.py    # N GPUs:
         tiles sharded over the ranks (RCCL: packed-weight broadcast, banded canvas reduce, point broadcast, vote gather);
         rank 0 prints ms/scene (max over ranks) and the per-rank stage times
@@ -403,6 +409,89 @@ def nodata_report(args, net, cfg, raw, iters=20):
     return rep
 
 
+def aoi_star(H, W, frac, points=7):
+    """The polygon of --aoi-frac: a star around the scene's centre, 2 * points vertices of alternating radii R and R / 2 (fractions of the half
+    axes), R such that its area n sin(pi / n) R (R / 2) (H / 2) (W / 2) is frac H W; tips that leave the scene are cut by it."""
+    n = points
+    R = np.sqrt(frac * 8.0 / (n * np.sin(np.pi / n)))
+    return [[[float(H / 2 * (1 + (R if i % 2 == 0 else R / 2) * np.sin(np.pi * i / n))), float(W / 2 * (1 + (R if i % 2 == 0 else R / 2) * np.cos(np.pi * i / n)))]
+             for i in range(2 * n)]]
+
+
+def aoi_report(args, net, cfg, img, iters=20):
+    """--aoi-frac: scene_aoi_fill against aoi_ref on this scene size (the run ends if they differ) and its device ms alone (events around each
+    of `iters` runs after a warm-up) for the star, a hexagon, a 1000-vertex circle and a zigzag ring of 16384 edges; device ms of pass 1 of
+    the same scene (from the lane's events); ms per scene of the pipelined loop without a mask / with the key / with the identical mask
+    passed as `valid`, alternated; host ms of aoi_ref for the star, the work the key takes off the feeding thread."""
+    import sam_road_amd.inferencer as inf
+    from sam_road_amd import Config
+    from sam_road_amd.aoi import aoi_edges, aoi_key_of, aoi_pack, aoi_ref, scene_aoi_key
+    dev = next(net.parameters()).device
+    H, W = img.shape[:2]
+    key = scene_aoi_key(cfg)
+    t0 = time.perf_counter()
+    want = aoi_ref((H, W), key)
+    host_ms = 1e3 * (time.perf_counter() - t0)
+    rep = {"aoi_frac_asked": args.aoi_frac, "valid_frac": round(float(want.mean()), 4), "host_ms_aoi_ref": round(host_ms, 1)}
+    n = 16384
+    polygons = {"star_14_vertices": cfg.SCENE_AOI["include"],
+                "hexagon_6_vertices": [[[[float(H / 2 * (1 + 0.8 * np.sin(np.pi * i / 3))), float(W / 2 * (1 + 0.8 * np.cos(np.pi * i / 3)))] for i in range(6)]]],
+                "circle_1000_vertices": [[[[float(H / 2 + 0.4 * H * np.sin(2 * np.pi * i / 1000)), float(W / 2 + 0.4 * W * np.cos(2 * np.pi * i / 1000))] for i in range(1000)]]],
+                "zigzag_16384_edges": [[[[(0.05 if i % 2 == 0 else 0.6) * H + (i % 7) / 256.0, (i + 0.5) * W / (n - 1)] for i in range(n - 1)] + [[0.9 * H, float(W)], [0.9 * H, 0.0]]]]}
+    fills = {}
+    for name, include in polygons.items():
+        k = aoi_key_of({"include": include})
+        tab = aoi_edges(k, H, W)
+        tab_d = torch.from_numpy(aoi_pack(*tab[:2])).to(dev)
+        run = lambda: net.scene_aoi_fill((H, W), *tab, table_dev=tab_d)
+        got, ref = run().cpu().numpy(), aoi_ref((H, W), k)
+        if not np.array_equal(got, ref):
+            bad = got != ref
+            raise SystemExit(f"{name}: the device mask differs from aoi_ref on {int(bad.sum())} px, rows {np.unique(np.nonzero(bad)[0])[:8].tolist()}")
+        evs = []
+        for _ in range(iters):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            run()
+            e1.record()
+            evs.append((e0, e1))
+        torch.cuda.synchronize()
+        ms = sorted(a.elapsed_time(b) for a, b in evs)
+        fills[name] = {"edges_in_table": int(tab[0].shape[0]), "inside_frac": round(float(ref.mean()), 4), "device_ms_median": round(ms[len(ms) // 2], 4),
+                       "device_ms_min_max": [round(ms[0], 4), round(ms[-1], 4)], "equals_aoi_ref": True}
+    rep["scene_aoi_fill_alone"] = fills
+    if args.no_pipelined:
+        return rep
+    plain = Config({k: v for k, v in cfg.items() if k != "SCENE_AOI"})
+    inf._Lane.times = []
+
+    def piped(c, valid, n=12):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in inf.infer_imgs(net, (img for _ in range(n)), c, **({} if valid is None else dict(valids=(valid for _ in range(n))))):
+            pass
+        torch.cuda.synchronize()
+        return round(1e3 * (time.perf_counter() - t0) / n, 2)
+
+    piped(plain, None, 3), piped(cfg, None, 3), piped(plain, want, 3)
+    inf._Lane.times.clear()
+    runs = {"unmasked": [], "keyed": [], "mask_passed_as_valid": []}
+    for _ in range(3):
+        runs["unmasked"].append(piped(plain, None))
+        runs["keyed"].append(piped(cfg, None))
+        runs["mask_passed_as_valid"].append(piped(plain, want))
+    rep["pipelined_ms_per_scene_runs_of_12_alternated"] = runs
+    p1 = sorted(t[1] for t in inf._Lane.times)
+    rep["pass1_device_ms_median_of_all_scenes_above"] = round(p1[len(p1) // 2], 2) if p1 else None
+    inf._Lane.times = None
+    rep["tiles_run_of_planned"] = [len(inf.scene_tiles(img.shape, cfg, net=net)), len(inf.scene_tiles(img.shape, plain))]
+    a = inf.infer_one_img(net, img, cfg)
+    b = inf.infer_one_img(net, img, plain, valid=want)
+    rep["keyed_equals_mask_passed"] = all(np.array_equal(x, y) for x, y in zip(a, b))
+    rep["graph_points"], rep["edges"] = int(a[0].shape[0]), int(a[1].shape[0])
+    return rep
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--bias", type=float, default=-2.2)
@@ -436,6 +525,9 @@ def main():
     ap.add_argument("--nodata-tolerance", type=int, default=None, metavar="T")
     ap.add_argument("--nodata-grow", type=int, default=None, metavar="R")
     ap.add_argument("--nodata-min-area", type=int, default=None, metavar="A")
+    ap.add_argument("--aoi-frac", type=float, default=None, metavar="F",
+                    help="SCENE_AOI: a star polygon that covers about F of the scene; the device mask is compared with aoi_ref, and scene_aoi_fill, pass 1 "
+                         "and the pipelined loop are timed (one GPU; --no-pipelined: the fill alone)")
     ap.add_argument("--no-pipelined", action="store_true", help="skip the infer_imgs runs (12- and 48-scene streams)")
     ap.add_argument("--patch", type=int, default=512, metavar="P", help="PATCH_SIZE (default 512)")
     ap.add_argument("--margin", type=int, default=64, metavar="M", help="SAMPLE_MARGIN (default 64)")
@@ -527,6 +619,12 @@ def main():
         raw = np.ascontiguousarray(nodata_paint(raw, args.nodata[0], rng))
         print(json.dumps({"scene": f"synthetic {H}x{W} {raw.dtype} x {raw.shape[2]} with a collar, a fringe and specks of {args.nodata[0]}",
                           "infer_batch_size": args.batch, "scene_nodata": nodata_report(args, net, cfg, raw)}))
+        return
+    if args.aoi_frac is not None:
+        if world > 1 or args.scenes is not None or args.valid_frac is not None or args.scale is not None or args.bands is not None or not 0.0 < args.aoi_frac <= 1.0:
+            ap.error("--aoi-frac F, 0 < F <= 1, times one unmasked u8 scene on one GPU (not with --scenes, --valid-frac, --scale or --bands)")
+        cfg.SCENE_AOI = {"include": [aoi_star(H, W, args.aoi_frac)]}
+        print(json.dumps({"scene": f"synthetic {H}x{W} under a star polygon", "infer_batch_size": args.batch, "scene_aoi": aoi_report(args, net, cfg, img)}))
         return
     bands_report = None
     if args.bands is not None:
