@@ -396,6 +396,38 @@ int srh_scene_nodata_grow(srh_ctx* ctx, const uint8_t* src, uint8_t* dst, int64_
 int srh_scene_aoi_fill(srh_ctx* ctx, const int32_t* edges_host, const int32_t* edges_dev, const int32_t* polys_host, const int32_t* polys_dev,
                        int n_include, int n_exclude, int H, int W, const uint8_t* and_with, int invert, uint8_t* out, void* stream);
 
+/* Float32 scenes (config key SCENE_FLOAT; an extension): a float32 scene of 1 to 16 bands becomes the u8 [n, 3] scene and
+ * its validity mask on the device, right behind the upload.  Three additive entries; the ABI number stays 11 because nothing existing
+ * changes, and a run without the key calls none of them.  A float is read as its 32-bit pattern b and compared through the ordered key:
+ * b = 0x80000000 reads as 0 (-0.0 is +0.0); key = ~b if the sign bit is set, else b | 0x80000000.  Integer compares only.
+ *
+ * Common: src f32 [n_pixels, C] on the device at any 4-byte-aligned address, 1 <= C <= 16, 1 <= n_pixels <= 2^31 - 1; select: a HOST
+ * array of three band indices in 0 .. C - 1.  The source is read (the selected bands only) and never written.  No entry knows of rows.
+ * srh_scene_float_valid: valid_out u8 [n_pixels] on the device (any byte address, overlapping neither src nor valid_in): 1 iff every
+ *   selected band is finite (exponent field not 0xff), has none of the n_nodata (0 .. 4) keys of the HOST array nodata_keys (NULL allowed
+ *   for 0), with log = 1 has a key above that of zero, and valid_in (u8 [n_pixels] on the device, or NULL) is non-zero there; else 0.
+ *   Every byte of valid_out is written exactly once and nothing else is.  No atomics, no LDS.
+ * srh_scene_float_hist: exact counts over the pixels whose valid byte (u8 [n_pixels] on the device, required) is non-zero.  targets NULL
+ *   (n_targets 0), pass 1: hist u32 [3, 65536], hist[b][v] = the pixels with key(band select[b]) >> 16 == v.  Otherwise pass 2: targets is
+ *   a HOST array u32 [n_targets, 2] of (band, prefix) pairs, 1 <= n_targets <= 6, and hist u32 [n_targets, 65536] with hist[t][v] = the
+ *   pixels with key(band) >> 16 == prefix and key(band) & 0xffff == v.  hist is on the device, 4-byte aligned, zeroed by the call itself.
+ *   Integer adds only: the counts are exact and do not depend on scheduling.
+ * srh_scene_float_apply: dst u8 [n_pixels, 3] on the device (any byte address, overlapping neither src nor valid): byte 3 i + b = the
+ *   number of j < 255 with thresholds[b][j] <= key(src[i][select[b]]) where valid[i] != 0, else 0.  thresholds: u32 [3, 256] on the device,
+ *   4-byte aligned, every row ascending, entry 255 = 0xffffffff.  Every byte of dst is written exactly once and nothing else is.  3 KiB
+ *   of LDS, no atomics.
+ * SRH_ERR_BAD_ARG, and nothing is launched, for a null pointer (valid_in, nodata_keys with n_nodata 0 and targets with n_targets 0
+ * excepted), C or n_pixels outside their range, a select entry or a target's band outside 0 .. C - 1, a prefix above 65535, n_nodata
+ * outside 0 .. 4, n_targets outside 0 .. 6, log outside 0 / 1, a source that is not 4-byte aligned, a misaligned hist or threshold table,
+ * or an output overlapping an input.  None touches a workspace of the context.  Profiler rows: scene_float_valid, scene_float_hist,
+ * scene_float_apply. */
+int srh_scene_float_valid(srh_ctx* ctx, const void* src, int64_t n_pixels, int C, const int32_t* select, const uint32_t* nodata_keys,
+                          int n_nodata, int log, const uint8_t* valid_in, uint8_t* valid_out, void* stream);
+int srh_scene_float_hist(srh_ctx* ctx, const void* src, int64_t n_pixels, int C, const int32_t* select, const uint8_t* valid,
+                         const uint32_t* targets, int n_targets, uint32_t* hist, void* stream);
+int srh_scene_float_apply(srh_ctx* ctx, const void* src, int64_t n_pixels, int C, const int32_t* select, const uint8_t* valid,
+                          const uint32_t* thresholds, uint8_t* dst, void* stream);
+
 /* op level (used by the parity tests to localise a failure; same kernels as above) ----------------- */
 
 /* out = act(A[M,K] W[N,K]^T + bias) (+resid); A,W fp16; N%128==0, K%64==0. act: 0/1 GELU/2 ReLU. */

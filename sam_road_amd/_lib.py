@@ -83,6 +83,9 @@ SYMBOLS = {
     "srh_scene_nodata_match": (_I, [_P, _P, _I, C.c_int64, _I, _P, _P, _I, _P, _I, _P, _P]),
     "srh_scene_nodata_grow": (_I, [_P, _P, _P, C.c_int64, _P, _P, _I, _I, _P, _I, _P]),
     "srh_scene_aoi_fill": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _I, _P, _P]),
+    "srh_scene_float_valid": (_I, [_P, _P, C.c_int64, _I, _P, _P, _I, _I, _P, _P, _P]),
+    "srh_scene_float_hist": (_I, [_P, _P, C.c_int64, _I, _P, _P, _P, _I, _P, _P]),
+    "srh_scene_float_apply": (_I, [_P, _P, C.c_int64, _I, _P, _P, _P, _P, _P]),
     "srh_op_patch_im2col": (_I, [_P, _P, _I, _I, _P, _I, _I, _I, _P, _P]),
     "srh_op_scores_unorient": (_I, [_P, _P, _I, _I, _I, _P, _P]),
     "srh_op_gemm": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P]),

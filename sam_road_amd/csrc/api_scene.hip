@@ -372,3 +372,71 @@ extern "C" int srh_scene_aoi_fill(srh_ctx* c, const int32_t* edges_host, const i
     TRYK(c, "scene_aoi_fill", 0, px * (and_with ? 2 : 1) + 16.0 * polys_host[n_include + n_exclude], s, launch_scene_aoi_fill(p, s));
     return 0;
 }
+
+// ---- scene level, float32 scenes (kernels in scene_float.hip, behaviour in DESIGN.md §6n) ----------------------------------------------------
+static int scene_float_params(srh_ctx* c, const char* who, const void* src, int64_t n_pixels, int C, const int32_t* select, SceneFloatParams& p) {
+    if (!c || !src || !select) return fail(c, SRH_ERR_BAD_ARG, std::string(who) + ": null argument");
+    if (C < 1 || C > FLOAT_MAX_C || n_pixels < 1 || n_pixels > FLOAT_MAX_PIXELS)
+        return fail(c, SRH_ERR_BAD_ARG, std::string(who) + ": 1 to 16 bands and 1 to 2^31 - 1 pixels");
+    for (int b = 0; b < 3; ++b)
+        if (select[b] < 0 || select[b] >= C) return fail(c, SRH_ERR_BAD_ARG, std::string(who) + ": a selected band is 0 to C - 1");
+    if (reinterpret_cast<uintptr_t>(src) & 3) return fail(c, SRH_ERR_BAD_ARG, std::string(who) + ": the f32 source is 4-byte aligned");
+    p.src = static_cast<const uint32_t*>(src); p.n = (long)n_pixels; p.C = C;
+    for (int b = 0; b < 3; ++b) p.sel[b] = select[b];
+    return 0;
+}
+
+extern "C" int srh_scene_float_valid(srh_ctx* c, const void* src, int64_t n_pixels, int C, const int32_t* select, const uint32_t* nodata_keys,
+                                     int n_nodata, int log, const uint8_t* valid_in, uint8_t* valid_out, void* stream) {
+    SceneFloatParams p;
+    TRY(scene_float_params(c, "srh_scene_float_valid", src, n_pixels, C, select, p));
+    if (!valid_out || n_nodata < 0 || n_nodata > FLOAT_MAX_NODATA || (n_nodata > 0 && !nodata_keys) || (log != 0 && log != 1))
+        return fail(c, SRH_ERR_BAD_ARG, "srh_scene_float_valid: null argument, more than 4 nodata keys or log outside 0 / 1");
+    const double src_bytes = (double)n_pixels * C * 4;
+    if (ranges_overlap(valid_out, (double)n_pixels, src, src_bytes) || (valid_in && ranges_overlap(valid_out, (double)n_pixels, valid_in, (double)n_pixels)))
+        return fail(c, SRH_ERR_BAD_ARG, "srh_scene_float_valid: valid_out overlaps src or valid_in");
+    p.valid_in = valid_in; p.valid_out = valid_out; p.n_nodata = n_nodata; p.log = log;
+    for (int j = 0; j < n_nodata; ++j) p.nodata[j] = nodata_keys[j];
+    hipSetDevice(c->device);
+    hipStream_t s = (hipStream_t)stream;
+    TRYK(c, "scene_float_valid", 0, (double)n_pixels * (12 + (valid_in ? 2 : 1)), s, launch_scene_float_valid(p, s));
+    return 0;
+}
+
+extern "C" int srh_scene_float_hist(srh_ctx* c, const void* src, int64_t n_pixels, int C, const int32_t* select, const uint8_t* valid,
+                                    const uint32_t* targets, int n_targets, uint32_t* hist, void* stream) {
+    SceneFloatParams p;
+    TRY(scene_float_params(c, "srh_scene_float_hist", src, n_pixels, C, select, p));
+    if (!valid || !hist || (reinterpret_cast<uintptr_t>(hist) & 3)) return fail(c, SRH_ERR_BAD_ARG, "srh_scene_float_hist: null valid, or null or misaligned hist");
+    if (n_targets < 0 || n_targets > FLOAT_MAX_TARGETS || (n_targets > 0) != (targets != nullptr))
+        return fail(c, SRH_ERR_BAD_ARG, "srh_scene_float_hist: 1 to 6 targets, or none and a null list for pass 1");
+    for (int t = 0; t < n_targets; ++t) {
+        if (targets[2 * t] >= (uint32_t)C || targets[2 * t + 1] > 0xffffu)
+            return fail(c, SRH_ERR_BAD_ARG, "srh_scene_float_hist: a target is (band 0 to C - 1, prefix 0 to 65535)");
+        p.tband[t] = (int)targets[2 * t]; p.tprefix[t] = targets[2 * t + 1];
+    }
+    const double src_bytes = (double)n_pixels * C * 4, hist_bytes = (double)(n_targets ? n_targets : 3) * 65536 * 4;
+    if (ranges_overlap(hist, hist_bytes, src, src_bytes) || ranges_overlap(hist, hist_bytes, valid, (double)n_pixels))
+        return fail(c, SRH_ERR_BAD_ARG, "srh_scene_float_hist: hist overlaps src or valid");
+    p.valid = valid; p.hist = hist; p.n_targets = n_targets;
+    hipSetDevice(c->device);
+    hipStream_t s = (hipStream_t)stream;
+    TRYK(c, "scene_float_hist", 0, (double)n_pixels * (n_targets ? 4 * n_targets + 1 : 13), s, launch_scene_float_hist(p, s));
+    return 0;
+}
+
+extern "C" int srh_scene_float_apply(srh_ctx* c, const void* src, int64_t n_pixels, int C, const int32_t* select, const uint8_t* valid,
+                                     const uint32_t* thresholds, uint8_t* dst, void* stream) {
+    SceneFloatParams p;
+    TRY(scene_float_params(c, "srh_scene_float_apply", src, n_pixels, C, select, p));
+    if (!valid || !thresholds || !dst || (reinterpret_cast<uintptr_t>(thresholds) & 3))
+        return fail(c, SRH_ERR_BAD_ARG, "srh_scene_float_apply: null argument or a misaligned threshold table");
+    const double src_bytes = (double)n_pixels * C * 4, dst_bytes = 3.0 * (double)n_pixels;
+    if (ranges_overlap(dst, dst_bytes, src, src_bytes) || ranges_overlap(dst, dst_bytes, valid, (double)n_pixels) || ranges_overlap(dst, dst_bytes, thresholds, 3072.0))
+        return fail(c, SRH_ERR_BAD_ARG, "srh_scene_float_apply: dst overlaps src, valid or the thresholds");
+    p.valid = valid; p.thr = thresholds; p.dst = dst;
+    hipSetDevice(c->device);
+    hipStream_t s = (hipStream_t)stream;
+    TRYK(c, "scene_float_apply", 0, (double)n_pixels * (12 + 1 + 3), s, launch_scene_float_apply(p, s));
+    return 0;
+}

@@ -10,6 +10,7 @@
 #include "mask_clean_piece.hpp"
 #include "scene_nodata_piece.hpp"
 #include "scene_aoi_piece.hpp"
+#include "scene_float_piece.hpp"
 
 namespace srh {
 
@@ -213,6 +214,12 @@ int launch_scene_nodata_grow(const SceneGrowParams& p, long max_blocks, hipStrea
 // fill of include / exclude polygons given as a device table of edges that has been checked on the host (aoi_table_ok); -2 for bad
 // parameters.
 int launch_scene_aoi_fill(const SceneAoiParams& p, hipStream_t s);
+// Float32 scenes (scene_float.hip; SceneFloatParams in scene_float_piece.hpp): the validity mask by rule 1, the exact
+// histograms of the ordered keys (pass 1 over key >> 16, with targets pass 2 over key & 0xffff; zeroed by the launch itself) and dst u8
+// [n,3] = the level of every selected value among 255 threshold keys; -2 for parameters outside their range.
+int launch_scene_float_valid(const SceneFloatParams& p, hipStream_t s);
+int launch_scene_float_hist(const SceneFloatParams& p, hipStream_t s);
+int launch_scene_float_apply(const SceneFloatParams& p, hipStream_t s);
 
 // Bilinear sampler (F.grid_sample, align_corners=False, zeros) on channels-last embeddings.
 struct SampleParams {

@@ -32,6 +32,8 @@ from .hostcpu import fill_threads, usable_cpus, worker_threads
 from .mask_clean import MaskRule, idle as _rule_idle, mask_clean_key, mask_clean_override, mask_clean_table
 from .nodata import nodata_table, scene_nodata_check, scene_nodata_key, scene_nodata_override
 from .resample import map_nodes, model_shape, scene_scale_key, scene_scale_override
+from .float_scene import (float_hist_targets, float_ranges_from_hists, float_thresholds, nodata_keys as float_nodata_keys, scene_float_check,
+                          scene_float_key, scene_float_override, threshold_keys)
 from .radiometry import band_luts, fixed_ranges, scene_bands_check, scene_bands_key, scene_bands_override, stretch_from_hist
 from .tiling import get_patch_info_hw, get_patch_info_one_img, patches_per_axis, shard_tiles
 
@@ -599,7 +601,10 @@ def _scene_plan(img, config):
     # the reference uses img.shape[0] for both axes (inferencer.py:63,67) and casts whatever it gets to f32: it would mis-stride a
     # non-square scene and silently convert a non-u8 one.  Here H and W are separate all the way down; non-u8 is refused
     bands = scene_bands_key(config)
-    if bands is not None:                                  # SCENE_BANDS: a raw u8 / u16 scene of 1 to 16 bands
+    flt = scene_float_plan(config)
+    if flt is not None:                                    # SCENE_FLOAT: a raw float32 scene of 1 to 16 bands
+        scene_float_check(img, flt)
+    elif bands is not None:                                # SCENE_BANDS: a raw u8 / u16 scene of 1 to 16 bands
         scene_bands_check(img, bands)
     elif img.ndim != 3 or img.shape[2] != 3 or img.dtype != np.uint8:
         raise ValueError(f"infer_one_img expects an HxWx3 uint8 scene, got {img.dtype} {tuple(img.shape)}")
@@ -615,6 +620,18 @@ def _scene_plan(img, config):
     # SCENE_PAD: the tiles are planned on the virtual (padded) scene; infos / origins are in ITS frame
     infos, all_xy = _tile_plan(Hm + top + bottom, Wm + left + right, config, padded=pad is not None)
     return img, infos, all_xy
+
+
+def scene_float_plan(config):
+    """config.SCENE_FLOAT parsed: a float_scene.SceneFloat, or None when the key is missing, None or empty — no scene takes a
+    step of it then.  ValueError, before the device is touched, for a key that cannot be used and for one that meets SCENE_BANDS (the key
+    of integer scenes) or SCENE_NODATA (its values are integer levels; SCENE_FLOAT.nodata is the float form)."""
+    flt = scene_float_key(config)
+    if flt is not None and scene_bands_key(config) is not None:
+        raise ValueError("SCENE_FLOAT does not combine with SCENE_BANDS (a scene is float32 or uint8 / uint16, not both): drop one of them")
+    if flt is not None and scene_nodata_key(config) is not None:
+        raise ValueError("SCENE_FLOAT does not combine with SCENE_NODATA (its values are integer levels): give the float values as nodata of SCENE_FLOAT")
+    return flt
 
 
 def _model_frame(shape, scale):
@@ -1192,7 +1209,7 @@ class _Lane:
 class _BlockingIO:
     """How infer_one_img and the tile-sharded loops move a scene's arrays: one blocking copy each way, pageable memory.  The other
     implementation of the same four operations is _LaneIO.  `lap` (a _Laps) names the steps of pass 1 for the profile."""
-    STEPS = {"upload": "scene upload", "aoi": "area of interest mask", "nodata": "nodata mask", "bands": "band select + stretch", "scale": "scene resample", "pad": "scene pad", "pack": "group pack", "select": "tile selection (count kernel + counts D2H)", "fill": "nodata fill",
+    STEPS = {"upload": "scene upload", "aoi": "area of interest mask", "nodata": "nodata mask", "bands": "band select + stretch", "float": "float scene -> u8 + mask", "scale": "scene resample", "pad": "scene pad", "pack": "group pack", "select": "tile selection (count kernel + counts D2H)", "fill": "nodata fill",
              "pass 1": "pass 1 (GPU)"}
     alloc = None                                       # the pass-2 collate fills plain numpy arrays
 
@@ -1219,7 +1236,7 @@ class _LaneIO:
     """The operations of _BlockingIO on infer_imgs' lane, for ONE scene in flight (`pool`: its page-locked staging): uploads are staged
     and stream-ordered, the counts come back over the copy stream, the pass-2 collate writes straight into the staging buffers.  With the
     profile on, five device events time the scene's pass 1, pass 2 and score download."""
-    STEPS = {"upload": "stage + queue scene upload", "aoi": "queue area of interest mask", "nodata": "queue nodata mask", "bands": "band select + stretch (upload lane)", "scale": "queue scene resample", "pad": "queue scene pad", "pack": "queue group pack", "select": "tile selection (upload lane)", "pass 1": "queue pass 1"}
+    STEPS = {"upload": "stage + queue scene upload", "aoi": "queue area of interest mask", "nodata": "queue nodata mask", "bands": "band select + stretch (upload lane)", "float": "float scene -> u8 + mask (upload lane)", "scale": "queue scene resample", "pad": "queue scene pad", "pack": "queue group pack", "select": "tile selection (upload lane)", "pass 1": "queue pass 1"}
     EVENTS = {"launch pass 1": 0, "normalised": 1, "pass 2 uploaded": 2, "pass 2 launched": 3, "pass 2 on its way back": 4}
 
     def __init__(self, lane, pool, lap):
@@ -1282,6 +1299,8 @@ class _SceneSetup:
         self.rank = torch.distributed.get_rank() if dist else 0
         self.bands = scene_bands_key(config)             # SCENE_BANDS, or None: no scene takes a step of it
         self.bands_luts = {}                             # levels -> the tables of a fixed range on the device, built once per call
+        self.float = scene_float_plan(config)            # SCENE_FLOAT as a SceneFloat, or None: no scene takes a step of it
+        self.float_thr = None                            # the threshold keys of a fixed range on the device, built once per call
         self.scale = scene_scale_key(config)             # SCENE_SCALE as (p, q), or None: no scene takes a step of it
         self.clean = mask_clean_plan(config)             # MASK_CLEAN as a MaskCleanPlan, or None: no scene takes a step of it
         self.nodata = scene_nodata_key(config)           # SCENE_NODATA as a SceneNodata, or None: no scene takes a step of it
@@ -1367,6 +1386,9 @@ def _pass1_front(ctx, io, img, valid=None, group=None, aoi=None):
     device rasterises from the polygons (_scene_aoi_mask: one launch, plus the grow for a buffer; `aoi`, a scene's own SCENE_AOI value, takes
     the place of the config's key), ANDed with the caller's mask, takes the place of the uploaded one; SCENE_NODATA then ANDs its own into it.
     The edge table travels with the scene's other uploads; no mask is staged or uploaded unless the caller gave one.
+    SCENE_FLOAT lives here and nowhere else: where SCENE_BANDS sits, behind SCENE_AOI and in front of SCENE_SCALE, the raw
+    f32 [H,W,C] scene becomes the u8 [H,W,3] scene AND its validity mask (_scene_float_front); a float scene is always a masked scene, and
+    nothing after that step knows of the key.
     group (SCENE_GROUP; img and valid are None then): a planned group, a list of _GroupScene, takes the place of the one
     scene — one ragged upload and one pack launch build the vertical stack of the scenes (each padded by its own pads) and of their masks,
     then the stack IS the scene of the code below, and one crop launch cuts every scene's window out of the stack's masks; the job
@@ -1395,7 +1417,7 @@ def _pass1_front(ctx, io, img, valid=None, group=None, aoi=None):
         shape = model_shape(scene_shape, ctx.scale)        # the frame of everything between the two resample steps (no key: the scene's)
         pad = scene_pad_plan(shape, config)
         pads = pad[:4] if pad is not None and any(pad[:4]) else None     # all four 0: the launches of a run without the key
-        masked, valid_d = valid is not None or ctx.nodata is not None or aoi is not None, None
+        masked, valid_d = valid is not None or ctx.nodata is not None or aoi is not None or ctx.float is not None, None
         if valid is not None:
             valid, min_frac, fill = _valid_plan(valid, scene_shape, config)
         elif masked:
@@ -1435,6 +1457,8 @@ def _pass1_front(ctx, io, img, valid=None, group=None, aoi=None):
             io.step("nodata")
         if ctx.bands is not None:                          # the raw scene -> the u8 [H,W,3] scene of every line below; the raw one is dropped
             scene = _scene_bands_front(ctx, io, scene, valid_d, after_compute=ctx.nodata is not None or aoi is not None)
+        if ctx.float is not None:                          # the raw f32 scene -> the u8 [H,W,3] scene and ITS mask; the raw one is dropped
+            scene, valid_d = _scene_float_front(ctx, io, scene, valid_d)
         if ctx.scale is not None:                          # the scene -> the model frame; the mask by the validity rule, and the scene-frame
             scene = net.scene_resample(scene, *ctx.scale)  # one is kept for the way back
             if masked:
@@ -1451,7 +1475,7 @@ def _pass1_front(ctx, io, img, valid=None, group=None, aoi=None):
     if masked:
         # every rank holds the scene and the mask, computes the same integer counts and therefore the same kept list: from here
         # on infos / all_xy / xy_dev ARE the kept tiles (a subsequence of an x-outer list is x-outer, so the banded reduce stays valid)
-        kept = select_tiles(io.counts(lambda: net.scene_tile_valid(valid_d, xy_dev), after_compute=pads is not None or group is not None or ctx.scale is not None or ctx.nodata is not None or aoi is not None),
+        kept = select_tiles(io.counts(lambda: net.scene_tile_valid(valid_d, xy_dev), after_compute=pads is not None or group is not None or ctx.scale is not None or ctx.nodata is not None or aoi is not None or ctx.float is not None),
                             config.PATCH_SIZE, min_frac)
         io.step("select")
         infos, all_xy = [infos[i] for i in kept], np.ascontiguousarray(all_xy[kept])
@@ -1523,6 +1547,30 @@ def _scene_bands_front(ctx, io, raw, valid_d=None, after_compute=False):
     scene = net.scene_bands_apply(raw, bands.select, lut_d)
     io.step("bands")
     return scene
+
+
+def _scene_float_front(ctx, io, raw, valid_d=None):
+    """SCENE_FLOAT lives here and nowhere else: the raw scene on the device (f32 [H,W,C]) and the mask so far (the caller's,
+    ANDed with SCENE_AOI's, or None) -> (the u8 [H,W,3] scene, the validity mask u8 [H,W] by rule 1 of float_scene.py).  Behind this point
+    the scene is an ordinary masked scene.  A percentile stretch counts the ordered keys of the selected bands over the valid pixels in two
+    exact 65536-bin passes, each fetched the way the tile selection fetches its counts, with the rank arithmetic on the host between and
+    after them (float_scene.py); the thresholds are built on the host in float64 — once per call for a fixed range — and the device only
+    compares integers against them.  Every rank of a tile-sharded run holds the scene and the mask, counts the same integers and builds
+    the same thresholds: no collective."""
+    net, key = ctx.net, ctx.float
+    valid_d = net.scene_float_valid(raw, key.select, [int(k) for k in float_nodata_keys(key)], key.log, valid_d)
+    thr_d = ctx.float_thr
+    if key.percentile is not None:
+        # after_compute: valid_d is what the compute stream just derived, so the upload lane waits for it first
+        hist1 = io.counts(lambda: net.scene_float_hist(raw, key.select, valid_d), name="float_hist", after_compute=True)
+        targets, picks = float_hist_targets(hist1, key)
+        hist2 = io.counts(lambda: net.scene_float_hist(raw, key.select, valid_d, targets), name="float_hist_low", after_compute=True) if targets else None
+        thr_d = io.upload("float_thr", threshold_keys(float_thresholds(float_ranges_from_hists(targets, picks, hist2, key), key)))
+    elif thr_d is None:
+        thr_d = ctx.float_thr = io.upload("float_thr", threshold_keys(float_thresholds(key.ranges, key)))
+    scene = net.scene_float_apply(raw, key.select, valid_d, thr_d)
+    io.step("float")
+    return scene, valid_d
 
 
 def _scene_nodata_mask(net, key, raw, lo, hi, and_with, table, table_d):
@@ -1686,8 +1734,11 @@ def infer_imgs(net, imgs, config, device=None, tile_sharded=None, pipelined=None
     tta_plan(config)
     scene_pad_key(config)
     bands = scene_bands_key(config)
+    flt = scene_float_plan(config)
     clean = mask_clean_plan(config)
     n_group = scene_group_key(config, group)
+    if flt is not None and n_group > 1:
+        raise ValueError(f"SCENE_FLOAT does not combine with SCENE_GROUP = {n_group} (float scenes run one by one): drop one of them")
     if clean is not None and 2 * n_group > MASK_CLEAN_MAX_IMAGES:
         raise ValueError(f"MASK_CLEAN filters the two masks of every scene of a group in one call of at most {MASK_CLEAN_MAX_IMAGES} images: "
                          f"SCENE_GROUP = {n_group} is too large, use at most {MASK_CLEAN_MAX_IMAGES // 2}")
@@ -2181,6 +2232,21 @@ def main(argv=None):
                          "(numpy.percentile, method lower), overriding stretch of the config's SCENE_BANDS; not with --scene-group")
     ap.add_argument("--gamma", default=None, type=float, metavar="G",
                     help="(extension) gamma of the stretch (out = 255 t^(1/G)), overriding gamma of the config's SCENE_BANDS")
+    ap.add_argument("--float-bands", default=None, metavar="I,J,K",
+                    help="(extension) the three bands of a float32 scene (.npy, float32 [H,W,C]) that become R, G, B, overriding select of the "
+                         "config's SCENE_FLOAT; repeats allowed")
+    ap.add_argument("--float-range", default=None, nargs=2, type=float, metavar=("LO", "HI"),
+                    help="(extension) the values that map to 0 and 255, overriding stretch of the config's SCENE_FLOAT")
+    ap.add_argument("--float-percentile", default=None, nargs=2, type=float, metavar=("PLO", "PHI"),
+                    help="(extension) stretch every selected band between these two percentiles of its valid pixels, per scene (the value at "
+                         "sorted index floor(p / 100 (N - 1))), overriding stretch of the config's SCENE_FLOAT")
+    ap.add_argument("--float-gamma", default=None, type=float, metavar="G",
+                    help="(extension) gamma of the stretch (out = 255 t^(1/G)), overriding gamma of the config's SCENE_FLOAT")
+    ap.add_argument("--float-transfer", default=None, choices=("linear", "log"),
+                    help="(extension) linear (default) or log (a stretch of log x; x <= 0 is nodata), overriding transfer of the config's SCENE_FLOAT")
+    ap.add_argument("--float-nodata", default=None, nargs="+", type=float, metavar="V",
+                    help="(extension) up to 4 values that mark nodata in a float32 scene (NaN and +-inf always do), overriding nodata of the "
+                         "config's SCENE_FLOAT; not with --scene-group")
     ap.add_argument("--nodata", default=None, nargs="+", type=int, metavar="V",
                     help="(extension) the nodata level of the raw scene, one for every band or one per band, overriding value of the config's "
                          "SCENE_NODATA: the validity mask is derived from it on the device (and ANDed with --valid-masks / alpha)")
@@ -2221,6 +2287,9 @@ def main(argv=None):
     if args.bands is not None or args.stretch_range is not None or args.stretch_percentile is not None or args.gamma is not None:
         config.SCENE_BANDS = scene_bands_override(config, None if args.bands is None else [int(b) for b in args.bands.split(",")],
                                                   args.stretch_range, args.stretch_percentile, args.gamma)
+    if any(v is not None for v in (args.float_bands, args.float_range, args.float_percentile, args.float_gamma, args.float_transfer, args.float_nodata)):
+        config.SCENE_FLOAT = scene_float_override(config, None if args.float_bands is None else [int(b) for b in args.float_bands.split(",")],
+                                                  args.float_range, args.float_percentile, args.float_gamma, args.float_transfer, args.float_nodata)
     if args.scene_group is not None:
         config.SCENE_GROUP = args.scene_group
     if args.scene_scale is not None or args.scene_gsd is not None or args.model_gsd is not None:
@@ -2241,6 +2310,8 @@ def main(argv=None):
     scene_scale_key(config)                      # and a SCENE_SCALE that cannot be used (or that meets a SCENE_GROUP)
     mask_clean_plan(config)                      # and a MASK_CLEAN that cannot be used
     nodata = scene_nodata_key(config)            # and a SCENE_NODATA that cannot be used
+    if scene_float_plan(config) is not None and scene_group_key(config) > 1:                             # and a SCENE_FLOAT
+        raise ValueError("SCENE_FLOAT does not combine with SCENE_GROUP (float scenes run one by one)")
     if (scene_aoi_key(config) is not None or job_aois is not None) and scene_group_key(config) > 1:      # and a SCENE_AOI
         raise ValueError("SCENE_AOI does not combine with SCENE_GROUP (the polygons are in the pixel frame of ONE scene)")
     if nodata is not None and nodata.min_area > 1 and scene_group_key(config) > MASK_CLEAN_MAX_IMAGES:

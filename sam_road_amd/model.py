@@ -751,6 +751,88 @@ class SAMRoad(nn.Module):
                                                     self._stream(dev)), "srh_scene_bands_apply")
         return out
 
+    # ---- scene level, float32 scenes (SCENE_FLOAT) ---------------------------------------------------------------------------
+    @staticmethod
+    def _float_src(src, select, dev):
+        """(pixels, C, select as a host int32[3]) of a raw float32 scene [..., C] (contiguous, 1 <= C <= 16)."""
+        import ctypes
+        if src.dtype != torch.float32 or src.dim() < 2 or not src.is_contiguous() or not 1 <= src.shape[-1] <= 16 or src.numel() < 1:
+            raise ValueError(f"a raw float scene is a contiguous float32 [..., C] tensor with 1 <= C <= 16, got {src.dtype} {tuple(src.shape)}")
+        C = int(src.shape[-1])
+        select = [int(b) for b in select]
+        if len(select) != 3 or not all(0 <= b < C for b in select):
+            raise ValueError(f"select must be three band indices in 0..{C - 1}, got {select!r}")
+        n = src.numel() // C
+        if n > 2 ** 31 - 1:
+            raise ValueError(f"a raw scene has at most 2^31 - 1 pixels, got {n}")
+        return n, C, (ctypes.c_int32 * 3)(*select)
+
+    @staticmethod
+    def _float_mask(valid, n, dev, what="valid"):
+        if valid.device != dev or valid.dtype not in (torch.uint8, torch.bool) or valid.numel() != n or not valid.is_contiguous():
+            raise ValueError(f"{what} must be a contiguous uint8 / bool tensor of {n} pixels on {dev}, got {valid.dtype} {tuple(valid.shape)} on {valid.device}")
+        return valid
+
+    @torch.no_grad()
+    def scene_float_valid(self, src, select, nodata_keys=(), log=False, valid=None):
+        """The validity mask of a float32 scene by rule 1 of float_scene.py (srh_scene_float_valid): src float32 [..., C] on the GPU,
+        select three band indices, nodata_keys up to 4 ordered keys (float_scene.nodata_keys), log: every selected band must be > 0,
+        valid: the caller's mask, uint8 / bool with one entry per pixel, or None -> a NEW uint8 tensor src.shape[:-1] of 0 / 1."""
+        import ctypes
+        dev = src.device
+        ctx, _ = self._weights(dev)
+        n, C, sel = self._float_src(src, select, dev)
+        keys = [int(k) for k in nodata_keys]
+        if len(keys) > 4 or not all(0 <= k <= 0xffffffff for k in keys):
+            raise ValueError(f"nodata_keys are up to 4 uint32 keys, got {nodata_keys!r}")
+        if valid is not None:
+            self._float_mask(valid, n, dev)
+        out = torch.empty(tuple(src.shape[:-1]), dtype=torch.uint8, device=dev)
+        with torch.cuda.device(dev):
+            ctx.check(ctx.lib.srh_scene_float_valid(ctx.handle, src.data_ptr(), n, C, sel, (ctypes.c_uint32 * len(keys))(*keys) if keys else None, len(keys),
+                                                    1 if log else 0, None if valid is None else valid.data_ptr(), out.data_ptr(), self._stream(dev)),
+                      "srh_scene_float_valid")
+        return out
+
+    @torch.no_grad()
+    def scene_float_hist(self, src, select, valid, targets=None):
+        """Exact counts of the ordered keys of a float32 scene over the pixels where valid is non-zero (srh_scene_float_hist).  targets
+        None: pass 1, uint32 [3, 65536] over key >> 16 of the three selected bands.  targets, 1 to 6 (band, prefix) pairs: pass 2, uint32
+        [len(targets), 65536] over key & 0xffff of the values of `band` whose key >> 16 is `prefix`.  The call uses no workspace."""
+        import ctypes
+        dev = src.device
+        ctx, _ = self._weights(dev)
+        n, C, sel = self._float_src(src, select, dev)
+        self._float_mask(valid, n, dev)
+        tg = None
+        if targets is not None:
+            flat = [int(v) for t in targets for v in t]
+            if not 1 <= len(targets) <= 6 or len(flat) != 2 * len(targets) or not all(0 <= b < C and 0 <= pre <= 0xffff for b, pre in zip(flat[::2], flat[1::2])):
+                raise ValueError(f"targets are 1 to 6 (band in 0..{C - 1}, prefix in 0..65535) pairs, got {targets!r}")
+            tg = (ctypes.c_uint32 * len(flat))(*flat)
+        hist = torch.empty((3 if tg is None else len(targets), 65536), dtype=torch.uint32, device=dev)
+        with torch.cuda.device(dev):
+            ctx.check(ctx.lib.srh_scene_float_hist(ctx.handle, src.data_ptr(), n, C, sel, valid.data_ptr(), tg, 0 if tg is None else len(targets),
+                                                   hist.data_ptr(), self._stream(dev)), "srh_scene_float_hist")
+        return hist
+
+    @torch.no_grad()
+    def scene_float_apply(self, src, select, valid, thresholds):
+        """src float32 [..., C] on the GPU -> a NEW uint8 tensor [..., 3]: channel b of a pixel with a non-zero valid byte = the number of
+        thresholds[b][:255] <= the ordered key of src[..., select[b]], of any other pixel 0 (srh_scene_float_apply).  thresholds: uint32
+        [3, 256] on the GPU (float_scene.threshold_keys).  The source is not written; it may be any contiguous 4-byte-aligned view."""
+        dev = src.device
+        ctx, _ = self._weights(dev)
+        n, C, sel = self._float_src(src, select, dev)
+        self._float_mask(valid, n, dev)
+        if thresholds.device != dev or thresholds.dtype != torch.uint32 or tuple(thresholds.shape) != (3, 256) or not thresholds.is_contiguous():
+            raise ValueError(f"thresholds must be a contiguous uint32 [3, 256] tensor on {dev}, got {thresholds.dtype} {tuple(thresholds.shape)} on {thresholds.device}")
+        out = torch.empty(tuple(src.shape[:-1]) + (3,), dtype=torch.uint8, device=dev)
+        with torch.cuda.device(dev):
+            ctx.check(ctx.lib.srh_scene_float_apply(ctx.handle, src.data_ptr(), n, C, sel, valid.data_ptr(), thresholds.data_ptr(), out.data_ptr(),
+                                                    self._stream(dev)), "srh_scene_float_apply")
+        return out
+
     # ---- scene level, another ground resolution (SCENE_SCALE, DESIGN.md §6j) -----------------------------------------------------------
     @staticmethod
     def _resample_tables(ctx, dev, n_in, n_out, p, q):

@@ -32,6 +32,9 @@ The final map_decoder bias is lowered so that the random network yields sparse m
                                                                     # scene's own masks and on a random mask at density 0.5, per kernel — next to
                                                                     # pass 1's, the pipelined loop with and without the key in turn, and the host
                                                                     # time of mask_clean_ref on the same masks
+    python tools/scene_bench.py --float 4 [--float-range LO HI] [--float-percentile P Q]    # SCENE_FLOAT: the scene arrives as float32 of 4 bands;
+                                                                    # "scene_float": the three launches alone, the pipelined loop handed
+                                                                    # float_scene_ref's outputs / keyed with a fixed range / with a percentile
     python tools/scene_bench.py --nodata 0 --nodata-tolerance 3 --nodata-min-area 50 --nodata-grow 2 [--bands 4 uint16]    # SCENE_NODATA: the scene
                                                                     # gets a collar, a fringe and interior specks of the value; "scene_nodata"
                                                                     # compares the derived mask with nodata_ref (the run ends if they differ) and
@@ -492,6 +495,106 @@ def aoi_report(args, net, cfg, img, iters=20):
     return rep
 
 
+def float_report(args, net, cfg, img, rng, iters=20):
+    """--float C [--float-range LO HI] [--float-percentile P Q]: the scene as a C-band float32 scene (bands 0..2 hold the synthetic RGB / 255,
+    the rest noise).  The device result against float_scene_ref for both keys (the run ends if they differ); device ms of each SCENE_FLOAT
+    launch alone (events around each of `iters` runs after a warm-up) with the bytes it moves; ms per scene of the pipelined loop handed
+    float_scene_ref's uint8 scene and mask / with the fixed-range key / with the percentile key, alternated; host ms of float_scene_ref,
+    the work the key takes off the feeding thread."""
+    import sam_road_amd.inferencer as inf
+    from sam_road_amd import Config
+    from sam_road_amd import float_scene as fs
+    dev = next(net.parameters()).device
+    H, W = img.shape[:2]
+    C = int(args.float)
+    if not 3 <= C <= 16:
+        raise SystemExit("--float takes C in 3..16")
+    raw = rng.normal(size=(H, W, C)).astype(np.float32)
+    raw[..., :3] = img.astype(np.float32) / np.float32(255)
+    lo, hi = args.float_range or (0.0, 1.0)
+    keys = {"fixed": {"select": [0, 1, 2], "stretch": [lo, hi]}, "percentile": {"select": [0, 1, 2], "stretch": {"percentile": list(args.float_percentile or (2.0, 98.0))}}}
+    n = H * W
+    rep = {"bands": C, "keys": keys, "upload_bytes": {"float_scene": int(raw.nbytes), "uint8_scene_and_mask": 4 * n}}
+    refs = {}
+    for name, key in keys.items():
+        t0 = time.perf_counter()
+        refs[name] = fs.float_scene_ref(raw, key)
+        rep[f"host_ms_float_scene_ref_{name}"] = round(1e3 * (time.perf_counter() - t0), 1)
+    raw_d = torch.from_numpy(raw).to(dev)
+    k = fs.as_key(keys["percentile"])
+
+    def device_ms(fn):
+        fn()
+        evs = []
+        for _ in range(iters):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fn()
+            e1.record()
+            evs.append((e0, e1))
+        torch.cuda.synchronize()
+        ms = sorted(a.elapsed_time(b) for a, b in evs)
+        return ms[len(ms) // 2], ms[0], ms[-1]
+
+    def row(ms, nbytes):
+        return {"device_us_median": round(1e3 * ms[0], 1), "device_us_min_max": [round(1e3 * ms[1], 1), round(1e3 * ms[2], 1)], "bytes": int(nbytes),
+                "GB_per_s_at_median": round(nbytes / ms[0] / 1e6, 1)}
+
+    valid_d = net.scene_float_valid(raw_d, k.select)
+    hist1 = net.scene_float_hist(raw_d, k.select, valid_d).cpu().numpy()
+    targets, picks = fs.float_hist_targets(hist1, k)
+    hist2 = net.scene_float_hist(raw_d, k.select, valid_d, targets).cpu().numpy()
+    ranges = fs.float_ranges_from_hists(targets, picks, hist2, k)
+    if [(a.tobytes(), b.tobytes()) for a, b in ranges] != [(a.tobytes(), b.tobytes()) for a, b in fs.float_ranges_ref(raw, k)]:
+        raise SystemExit("the ranges of the two device histograms differ from float_ranges_ref")
+    thr_d = torch.from_numpy(fs.threshold_keys(fs.float_thresholds(ranges, k))).to(dev)
+    got = net.scene_float_apply(raw_d, k.select, valid_d, thr_d).cpu().numpy()
+    if not np.array_equal(got, refs["percentile"][0]) or not np.array_equal(valid_d.cpu().numpy(), refs["percentile"][1]):
+        raise SystemExit("the device scene or mask differs from float_scene_ref")
+    line = 4 * C * n                                   # C <= 16: every 64-byte line of the source holds a selected band
+    const_d = torch.full_like(raw_d, 0.5)
+    rep["launches_alone"] = {
+        "scene_float_valid": row(device_ms(lambda: net.scene_float_valid(raw_d, k.select)), line + n),
+        "scene_float_hist_pass1": row(device_ms(lambda: net.scene_float_hist(raw_d, k.select, valid_d)), line + n + 3 * 65536 * 4),
+        "scene_float_hist_pass1_constant_scene": row(device_ms(lambda: net.scene_float_hist(const_d, k.select, valid_d)), line + n + 3 * 65536 * 4),
+        "scene_float_hist_pass2": dict(row(device_ms(lambda: net.scene_float_hist(raw_d, k.select, valid_d, targets)), line + n + len(targets) * 65536 * 4), targets=len(targets)),
+        "scene_float_apply": row(device_ms(lambda: net.scene_float_apply(raw_d, k.select, valid_d, thr_d)), line + n + 3 * n)}
+    rep["source_bytes_counted_as"] = "all C bands (whole cache lines), not only the 3 selected"
+    del const_d
+    if args.no_pipelined:
+        return rep
+    plain = Config({kk: v for kk, v in cfg.items() if kk != "SCENE_FLOAT"})
+    cfgs = {name: Config(dict(plain, SCENE_FLOAT=key)) for name, key in keys.items()}
+    u8, ok = refs["fixed"]
+    inf._Lane.times = []
+
+    def piped(c, scene, valid, n=12):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in inf.infer_imgs(net, (scene for _ in range(n)), c, **({} if valid is None else dict(valids=(valid for _ in range(n))))):
+            pass
+        torch.cuda.synchronize()
+        return round(1e3 * (time.perf_counter() - t0) / n, 2)
+
+    piped(plain, u8, ok, 3), piped(cfgs["fixed"], raw, None, 3), piped(cfgs["percentile"], raw, None, 3)
+    inf._Lane.times.clear()
+    runs = {"a_uint8_scene_and_mask_passed": [], "b_keyed_fixed_range": [], "c_keyed_percentile": []}
+    for _ in range(3):
+        runs["a_uint8_scene_and_mask_passed"].append(piped(plain, u8, ok))
+        runs["b_keyed_fixed_range"].append(piped(cfgs["fixed"], raw, None))
+        runs["c_keyed_percentile"].append(piped(cfgs["percentile"], raw, None))
+    rep["pipelined_ms_per_scene_runs_of_12_alternated"] = runs
+    p1 = sorted(t[1] for t in inf._Lane.times)
+    rep["pass1_device_ms_median_of_all_scenes_above"] = round(p1[len(p1) // 2], 2) if p1 else None
+    inf._Lane.times = None
+    for name in keys:
+        a = inf.infer_one_img(net, raw, cfgs[name])
+        b = inf.infer_one_img(net, refs[name][0], plain, valid=refs[name][1])
+        rep[f"keyed_equals_reference_passed_{name}"] = all(np.array_equal(x, y) for x, y in zip(a, b))
+    rep["graph_points"], rep["edges"] = int(a[0].shape[0]), int(a[1].shape[0])
+    return rep
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--bias", type=float, default=-2.2)
@@ -528,6 +631,11 @@ def main():
     ap.add_argument("--aoi-frac", type=float, default=None, metavar="F",
                     help="SCENE_AOI: a star polygon that covers about F of the scene; the device mask is compared with aoi_ref, and scene_aoi_fill, pass 1 "
                          "and the pipelined loop are timed (one GPU; --no-pipelined: the fill alone)")
+    ap.add_argument("--float", type=int, default=None, metavar="C",
+                    help="SCENE_FLOAT: the scene arrives as a float32 scene of C bands (bands 0..2 hold the synthetic RGB / 255, the rest noise); "
+                         "the three launches, the pipelined loop with a fixed range and with a percentile stretch and the host reference are timed")
+    ap.add_argument("--float-range", nargs=2, type=float, default=None, metavar=("LO", "HI"), help="with --float: the fixed range (default 0 1)")
+    ap.add_argument("--float-percentile", nargs=2, type=float, default=None, metavar=("P", "Q"), help="with --float: the percentiles (default 2 98)")
     ap.add_argument("--no-pipelined", action="store_true", help="skip the infer_imgs runs (12- and 48-scene streams)")
     ap.add_argument("--patch", type=int, default=512, metavar="P", help="PATCH_SIZE (default 512)")
     ap.add_argument("--margin", type=int, default=64, metavar="M", help="SAMPLE_MARGIN (default 64)")
@@ -625,6 +733,11 @@ def main():
             ap.error("--aoi-frac F, 0 < F <= 1, times one unmasked u8 scene on one GPU (not with --scenes, --valid-frac, --scale or --bands)")
         cfg.SCENE_AOI = {"include": [aoi_star(H, W, args.aoi_frac)]}
         print(json.dumps({"scene": f"synthetic {H}x{W} under a star polygon", "infer_batch_size": args.batch, "scene_aoi": aoi_report(args, net, cfg, img)}))
+        return
+    if args.float is not None:
+        if world > 1 or args.scenes is not None or args.valid_frac is not None or args.scale is not None or args.bands is not None:
+            ap.error("--float C times one unmasked float32 scene on one GPU (not with --scenes, --valid-frac, --scale or --bands)")
+        print(json.dumps({"scene": f"synthetic {H}x{W} float32 x {args.float}", "infer_batch_size": args.batch, "scene_float": float_report(args, net, cfg, img, rng)}))
         return
     bands_report = None
     if args.bands is not None:
