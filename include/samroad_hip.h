@@ -428,6 +428,46 @@ int srh_scene_float_hist(srh_ctx* ctx, const void* src, int64_t n_pixels, int C,
 int srh_scene_float_apply(srh_ctx* ctx, const void* src, int64_t n_pixels, int C, const int32_t* select, const uint8_t* valid,
                           const uint32_t* thresholds, uint8_t* dst, void* stream);
 
+/* The road graph as a raster (config key GRAPH_RASTER; an extension): the OUTPUT side.  The reference draws the graph
+ * over the scene with cv2.line / cv2.circle on the host (triage.py:8-35, inferencer.py:324-329) and carries, commented out, the pixel
+ * comparison with the ground truth (triage.py:38-71, inferencer.py:305-322); cv2's bytes are not reproduced, the rule is the integer one
+ * of sam_road_amd/graph_raster.py.  Three additive entries; the ABI number stays 11 because nothing existing changes, and a run
+ * without the key calls none of them.  None touches a workspace of the context and nothing is read back.
+ *
+ * srh_graph_raster: nodes int32 [N, 2] (row, col) and edges int32 [E, 2] (indices into nodes), each given twice as srh_scene_aoi_fill
+ *   takes its tables: the host copy is validated, the device copy (4-byte aligned) is what the kernels read, and it is never written.  A
+ *   pixel is the point at its integer coordinates.  For an edge a -> b of width t: d = b - a, p = x - a, u = p.d, L = d.d; x is covered
+ *   iff 4 p.p <= t^2 when L = 0 or u <= 0, 4 |p - d|^2 <= t^2 when u >= L, else 4 (p x d)^2 <= t^2 L — the pixels within t / 2 of the
+ *   segment.  A node mark covers the pixels with Chebyshev distance <= r (SRH_GRAPH_MARK_SQUARE) or p.p <= r^2 (SRH_GRAPH_MARK_DISC) of
+ *   the node; SRH_GRAPH_MARK_NONE draws none.  out u8 [H, W] on the device, any byte address: node_value on a node mark, else edge_value
+ *   on an edge, else 0 (the class map: edge_value 1, node_value 2).  Nodes may lie outside the image; everything is clipped.  N = 0 and
+ *   E = 0 are ordinary (the tables may then be NULL).  Every byte of out is defined after the call and nothing else is written: a clear,
+ *   then one wave per edge, then one wave per node, ordered by the stream; writers of one launch store the same byte, so the result does
+ *   not depend on scheduling.  No atomics.
+ * srh_graph_composite: cls u8 [H, W] and img u8 [H, W, 3] or NULL on the device; three HOST colours of three ints 0 .. 255.  out u8
+ *   [H, W, 3] on the device, any byte address: node_rgb where cls >= 2, edge_rgb where cls == 1, else img (background_rgb without one).
+ * srh_graph_compare: four class maps u8 [H, W] (non-zero = covered), valid u8 [H, W] or NULL, img u8 [H, W, 3] or NULL, on the device.
+ *   counts: four uint64 on the device, 8-byte aligned, written by the call: over the pixels with valid != 0 (all without valid)
+ *   {#(pred_thin), #(pred_thin & !gt_wide), #(gt_thin), #(gt_thin & !pred_wide)} — integer sums, the same numbers in any order.  diff u8
+ *   [H, W, 3] on the device or NULL, written in the same pass: img (black without one) with red (255, 0, 0) on a counted missed pixel,
+ *   else blue (0, 0, 255) on a counted false positive.
+ * SRH_ERR_BAD_ARG, and nothing is launched, for a null pointer (the tables of an empty graph, img, valid and diff excepted), a negative
+ * count, H or W < 1 or H W > 2^31 - 1, t outside 1 .. 255, an unknown mark, r outside 0 .. 127, a class value outside 1 .. 255, a
+ * coordinate outside +-2^28, an edge index outside [0, N), an edge spanning more than SRH_GRAPH_MAX_SPAN pixels on an axis (with it every
+ * product of the rule stays inside 64 bits), a colour outside 0 .. 255, a misaligned device table or counts, or an output overlapping an
+ * input.  Profiler rows: graph_clear, graph_edges, graph_nodes, graph_composite, graph_counts_zero, graph_compare. */
+#define SRH_GRAPH_MAX_SPAN 16383
+#define SRH_GRAPH_MARK_NONE 0
+#define SRH_GRAPH_MARK_SQUARE 1
+#define SRH_GRAPH_MARK_DISC 2
+int srh_graph_raster(srh_ctx* ctx, const int32_t* nodes_host, const int32_t* nodes_dev, int N, const int32_t* edges_host,
+                     const int32_t* edges_dev, int E, int H, int W, int t, int mark, int r, int edge_value, int node_value, uint8_t* out,
+                     void* stream);
+int srh_graph_composite(srh_ctx* ctx, const uint8_t* cls, const uint8_t* img, int H, int W, const int32_t* background_rgb,
+                        const int32_t* edge_rgb, const int32_t* node_rgb, uint8_t* out, void* stream);
+int srh_graph_compare(srh_ctx* ctx, const uint8_t* pred_thin, const uint8_t* pred_wide, const uint8_t* gt_thin, const uint8_t* gt_wide,
+                      const uint8_t* valid, const uint8_t* img, int H, int W, uint64_t* counts, uint8_t* diff, void* stream);
+
 /* op level (used by the parity tests to localise a failure; same kernels as above) ----------------- */
 
 /* out = act(A[M,K] W[N,K]^T + bias) (+resid); A,W fp16; N%128==0, K%64==0. act: 0/1 GELU/2 ReLU. */

@@ -16,6 +16,8 @@ SRH_GEMM_A_BLOCKED16, SRH_GEMM_OUT_BLOCKED16 = 1, 2       # srh_op_gemm_ex flags
 SRH_PAD_MODES = {"reflect": 0, "edge": 1, "constant": 2}  # srh_scene_pad modes (SRH_PAD_*)
 SRH_NODATA_MATCH = {"all": 0, "any": 1}                   # srh_scene_nodata_match modes (SRH_NODATA_*)
 
+SRH_GRAPH_MARKS = {"none": 0, "square": 1, "disc": 2}     # srh_graph_raster node marks (SRH_GRAPH_MARK_*)
+
 
 class SrhError(RuntimeError):
     pass
@@ -86,6 +88,9 @@ SYMBOLS = {
     "srh_scene_float_valid": (_I, [_P, _P, C.c_int64, _I, _P, _P, _I, _I, _P, _P, _P]),
     "srh_scene_float_hist": (_I, [_P, _P, C.c_int64, _I, _P, _P, _P, _I, _P, _P]),
     "srh_scene_float_apply": (_I, [_P, _P, C.c_int64, _I, _P, _P, _P, _P, _P]),
+    "srh_graph_raster": (_I, [_P, _P, _P, _I, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
+    "srh_graph_composite": (_I, [_P, _P, _P, _I, _I, _P, _P, _P, _P, _P]),
+    "srh_graph_compare": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P]),
     "srh_op_patch_im2col": (_I, [_P, _P, _I, _I, _P, _I, _I, _I, _P, _P]),
     "srh_op_scores_unorient": (_I, [_P, _P, _I, _I, _I, _P, _P]),
     "srh_op_gemm": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P]),

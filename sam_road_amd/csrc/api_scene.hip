@@ -440,3 +440,81 @@ extern "C" int srh_scene_float_apply(srh_ctx* c, const void* src, int64_t n_pixe
     TRYK(c, "scene_float_apply", 0, (double)n_pixels * (12 + 1 + 3), s, launch_scene_float_apply(p, s));
     return 0;
 }
+
+// ---- the road graph as a raster (kernels in graph_raster.hip, behaviour in DESIGN.md §6o) ----------------------------------------------------
+static_assert(SRH_GRAPH_MAX_SPAN == GR_MAX_SPAN && SRH_GRAPH_MARK_NONE == GR_MARK_NONE && SRH_GRAPH_MARK_SQUARE == GR_MARK_SQUARE &&
+              SRH_GRAPH_MARK_DISC == GR_MARK_DISC, "limits and marks of the header and the kernel");
+
+extern "C" int srh_graph_raster(srh_ctx* c, const int32_t* nodes_host, const int32_t* nodes_dev, int N, const int32_t* edges_host,
+                                const int32_t* edges_dev, int E, int H, int W, int t, int mark, int r, int edge_value, int node_value, uint8_t* out,
+                                void* stream) {
+    if (!c || !out || N < 0 || E < 0 || (N > 0 && (!nodes_host || !nodes_dev)) || (E > 0 && (!edges_host || !edges_dev)))
+        return fail(c, SRH_ERR_BAD_ARG, "srh_graph_raster: null argument or a negative count");
+    if (H < 1 || W < 1 || (double)H * W > (double)GR_MAX_PIXELS) return fail(c, SRH_ERR_BAD_ARG, "srh_graph_raster: H and W are at least 1 and H W at most 2^31 - 1");
+    if (t < 1 || t > GR_MAX_WIDTH || mark < GR_MARK_NONE || mark > GR_MARK_DISC || r < 0 || r > GR_MAX_RADIUS)
+        return fail(c, SRH_ERR_BAD_ARG, "srh_graph_raster: the width is 1 to 255, the mark SRH_GRAPH_MARK_NONE / SQUARE / DISC and its radius 0 to 127");
+    if (edge_value < 1 || edge_value > 255 || node_value < 1 || node_value > 255) return fail(c, SRH_ERR_BAD_ARG, "srh_graph_raster: a class value is 1 to 255");
+    if ((reinterpret_cast<uintptr_t>(nodes_dev) | reinterpret_cast<uintptr_t>(edges_dev)) & 3) return fail(c, SRH_ERR_BAD_ARG, "srh_graph_raster: the device tables are 4-byte aligned");
+    if (!gr_tables_ok(nodes_host, N, edges_host, E))
+        return fail(c, SRH_ERR_BAD_ARG, "srh_graph_raster: an inconsistent table (coordinates within +-2^28, edge indices in [0, N), an edge spans at most "
+                                        "16383 px per axis)");
+    const double px = (double)H * W;
+    if ((N > 0 && ranges_overlap(out, px, nodes_dev, 8.0 * N)) || (E > 0 && ranges_overlap(out, px, edges_dev, 8.0 * E)))
+        return fail(c, SRH_ERR_BAD_ARG, "srh_graph_raster: out overlaps a table");
+    GraphRasterParams p;
+    p.nodes = nodes_dev; p.edges = edges_dev; p.out = out; p.N = N; p.E = E; p.H = H; p.W = W; p.t = t; p.mark = mark; p.r = r;
+    p.edge_value = edge_value; p.node_value = node_value;
+    hipSetDevice(c->device);
+    hipStream_t s = (hipStream_t)stream;
+    TRYK(c, "graph_clear", 0, px, s, launch_graph_clear(p, s));
+    if (E > 0) TRYK(c, "graph_edges", 0, 24.0 * E, s, launch_graph_edges(p, s));
+    if (N > 0 && mark != GR_MARK_NONE) TRYK(c, "graph_nodes", 0, (8.0 + (2.0 * r + 1) * (2.0 * r + 1)) * N, s, launch_graph_nodes(p, s));
+    return 0;
+}
+
+static bool graph_colour(const int32_t* rgb, uint32_t& out) {
+    if (!rgb || ((rgb[0] | rgb[1] | rgb[2]) & ~255)) return false;
+    out = (uint32_t)rgb[0] | ((uint32_t)rgb[1] << 8) | ((uint32_t)rgb[2] << 16);
+    return true;
+}
+
+extern "C" int srh_graph_composite(srh_ctx* c, const uint8_t* cls, const uint8_t* img, int H, int W, const int32_t* background_rgb,
+                                   const int32_t* edge_rgb, const int32_t* node_rgb, uint8_t* out, void* stream) {
+    if (!c || !cls || !out) return fail(c, SRH_ERR_BAD_ARG, "srh_graph_composite: null argument");
+    if (H < 1 || W < 1 || (double)H * W > (double)GR_MAX_PIXELS) return fail(c, SRH_ERR_BAD_ARG, "srh_graph_composite: H and W are at least 1 and H W at most 2^31 - 1");
+    GraphCompositeParams p;
+    if (!graph_colour(background_rgb, p.colour[0]) || !graph_colour(edge_rgb, p.colour[1]) || !graph_colour(node_rgb, p.colour[2]))
+        return fail(c, SRH_ERR_BAD_ARG, "srh_graph_composite: a colour is three host ints 0 to 255");
+    const double px = (double)H * W;
+    if (ranges_overlap(out, 3 * px, cls, px) || (img && ranges_overlap(out, 3 * px, img, 3 * px)))
+        return fail(c, SRH_ERR_BAD_ARG, "srh_graph_composite: out overlaps the class map or the image");
+    p.cls = cls; p.img = img; p.out = out; p.n = (long)H * W;
+    hipSetDevice(c->device);
+    hipStream_t s = (hipStream_t)stream;
+    TRYK(c, "graph_composite", 0, px * (img ? 7 : 4), s, launch_graph_composite(p, s));
+    return 0;
+}
+
+extern "C" int srh_graph_compare(srh_ctx* c, const uint8_t* pred_thin, const uint8_t* pred_wide, const uint8_t* gt_thin, const uint8_t* gt_wide,
+                                 const uint8_t* valid, const uint8_t* img, int H, int W, uint64_t* counts, uint8_t* diff, void* stream) {
+    if (!c || !pred_thin || !pred_wide || !gt_thin || !gt_wide || !counts) return fail(c, SRH_ERR_BAD_ARG, "srh_graph_compare: null argument");
+    if (H < 1 || W < 1 || (double)H * W > (double)GR_MAX_PIXELS) return fail(c, SRH_ERR_BAD_ARG, "srh_graph_compare: H and W are at least 1 and H W at most 2^31 - 1");
+    if (reinterpret_cast<uintptr_t>(counts) & 7) return fail(c, SRH_ERR_BAD_ARG, "srh_graph_compare: counts is 8-byte aligned");
+    const double px = (double)H * W;
+    const void* ins[6] = {pred_thin, pred_wide, gt_thin, gt_wide, valid, img};
+    for (int k = 0; k < 6; ++k) {
+        if (!ins[k]) continue;
+        const double bytes = k == 5 ? 3 * px : px;
+        if (ranges_overlap(counts, 32.0, ins[k], bytes) || (diff && ranges_overlap(diff, 3 * px, ins[k], bytes)))
+            return fail(c, SRH_ERR_BAD_ARG, "srh_graph_compare: counts or diff overlaps an input");
+    }
+    if (diff && ranges_overlap(diff, 3 * px, counts, 32.0)) return fail(c, SRH_ERR_BAD_ARG, "srh_graph_compare: diff overlaps counts");
+    GraphCompareParams p;
+    p.pred_thin = pred_thin; p.pred_wide = pred_wide; p.gt_thin = gt_thin; p.gt_wide = gt_wide; p.valid = valid; p.img = img; p.diff = diff;
+    p.counts = reinterpret_cast<unsigned long long*>(counts); p.n = (long)H * W;
+    hipSetDevice(c->device);
+    hipStream_t s = (hipStream_t)stream;
+    TRYK(c, "graph_counts_zero", 0, 32.0, s, launch_graph_counts_zero(p, s));
+    TRYK(c, "graph_compare", 0, px * (4 + (valid ? 1 : 0) + (diff ? (img ? 6 : 3) : 0)), s, launch_graph_compare(p, s));
+    return 0;
+}

@@ -11,6 +11,7 @@
 #include "scene_nodata_piece.hpp"
 #include "scene_aoi_piece.hpp"
 #include "scene_float_piece.hpp"
+#include "graph_raster_piece.hpp"
 
 namespace srh {
 
@@ -220,6 +221,16 @@ int launch_scene_aoi_fill(const SceneAoiParams& p, hipStream_t s);
 int launch_scene_float_valid(const SceneFloatParams& p, hipStream_t s);
 int launch_scene_float_hist(const SceneFloatParams& p, hipStream_t s);
 int launch_scene_float_apply(const SceneFloatParams& p, hipStream_t s);
+// The road graph as a raster (graph_raster.hip; the parameters in graph_raster_piece.hpp).  The class map is three launches
+// that the caller orders on one stream: clear (always), edges (E > 0), nodes (N > 0 and a mark); the tables are on the device and have
+// been checked on the host (gr_tables_ok).  composite: the scene with the classes in colour.  compare: four counts (counts_zero in front)
+// and the optional diff image in one pass.  -2 for bad parameters.
+int launch_graph_clear(const GraphRasterParams& p, hipStream_t s);
+int launch_graph_edges(const GraphRasterParams& p, hipStream_t s);
+int launch_graph_nodes(const GraphRasterParams& p, hipStream_t s);
+int launch_graph_composite(const GraphCompositeParams& p, hipStream_t s);
+int launch_graph_counts_zero(const GraphCompareParams& p, hipStream_t s);
+int launch_graph_compare(const GraphCompareParams& p, hipStream_t s);
 
 // Bilinear sampler (F.grid_sample, align_corners=False, zeros) on channels-last embeddings.
 struct SampleParams {

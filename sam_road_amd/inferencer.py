@@ -28,6 +28,7 @@ from . import _lib
 from . import distributed as D
 from .aoi import aoi_edges, aoi_key_of, aoi_pack, aoi_ref, read_geojson, scene_aoi_key, scene_aoi_override
 from .graph_points import extract_graph_points
+from .graph_raster import graph_raster_key, graph_raster_override, read_gt_graph, render as render_graph, total_metrics
 from .hostcpu import fill_threads, usable_cpus, worker_threads
 from .mask_clean import MaskRule, idle as _rule_idle, mask_clean_key, mask_clean_override, mask_clean_table
 from .nodata import nodata_table, scene_nodata_check, scene_nodata_key, scene_nodata_override
@@ -2164,9 +2165,14 @@ def main(argv=None):
     inferencer.py:24-35,239-349), run from a sam_road checkout: enumerates the test split of config.DATASET
     (./cityscale/20cities/region_{}_sat.png or ./spacenet/RGB_1.0_meter/{}__rgb.png), runs the scenes through infer_imgs, writes
     save/<output_dir>/{config.yaml, mask/{id}_road.png, mask/{id}_itsc.png, graph/{id}.p, inference_time.txt} with the
-    reference's formats (8-bit grayscale PNG masks, sat2graph pickle, SpaceNet (400 - r, c) flip).  Not reproduced: the cv2
-    `viz/` renderings and the ground-truth pickle the reference loads but only uses in commented-out code (visualisation,
-    SURVEY §2 #17).  Extras: `--images a.png b.npy ...` runs explicit scene files instead of the dataset split; under torchrun
+    reference's formats (8-bit grayscale PNG masks, sat2graph pickle, SpaceNet (400 - r, c) flip).  The reference's `viz/` renderings
+    (inferencer.py:324-329) and the pred-against-gt comparison it carries commented out (inferencer.py:283-322) are opt-in here and are
+    NOT cv2's bytes: `--viz` writes viz/{id}.png, `--graph-mask RHO` graph_mask/{id}.png, `--diff [THIN WIDE]` diff/{id}.png and
+    diff/metrics.json (per-scene counts, relaxed pixel precision and recall, and the totals) against the ground-truth graphs —
+    the dataset's own sat2graph pickles, or `--gt-graphs g0.p g1.p ...` parallel to `--images` ('-' = none for that scene).  They lay
+    over the config's GRAPH_RASTER; the rule is sam_road_amd/graph_raster.py's, rasterised on the device on a stream of its own, encoded
+    on the writer threads.  Without them the run writes the files and bytes it always wrote.
+    Extras: `--images a.png b.npy ...` runs explicit scene files instead of the dataset split; under torchrun
     (one process per GPU) the scenes are dealt round-robin to the ranks (`--shard scenes`, default) or every scene's tiles are split
     over the ranks (`--shard tiles`; `tiles-pipelined` for the software-pipelined loop), all ranks writing into the one output directory.
     `--valid-masks m0.png m1.npy ...` (parallel to `--images`; `-` = no mask for that scene) gives every scene a validity mask
@@ -2269,8 +2275,27 @@ def main(argv=None):
                          "row G5, overriding geotransform of the config's SCENE_AOI")
     ap.add_argument("--aoi-buffer", default=None, type=int, metavar="B",
                     help="(extension) grow (B > 0) or shrink (B < 0) the area by |B| pixels (-16..16), overriding buffer of the config's SCENE_AOI")
+    ap.add_argument("--viz", action="store_true", default=None,
+                    help="(extension) write viz/{id}.png, the graph drawn over the scene (the reference's viz/, by the exact rule of "
+                         "GRAPH_RASTER, not cv2's bytes), switching on viz of the config's GRAPH_RASTER")
+    ap.add_argument("--graph-mask", default=None, type=int, metavar="RHO",
+                    help="(extension) write graph_mask/{id}.png, the graph as a 0 / 255 mask: edges of width 2 RHO, nodes as squares of half-side "
+                         "RHO (the reference's rasterize_graph), overriding mask of the config's GRAPH_RASTER")
+    ap.add_argument("--diff", default=None, nargs="*", type=int, metavar="N",
+                    help="(extension) [THIN WIDE] (default 1 5): write diff/{id}.png (false positives blue, missed ground truth red) and "
+                         "diff/metrics.json (n_pred, n_fp, n_gt, n_missed, precision, recall per scene and in total) against the ground-truth "
+                         "graphs, overriding diff of the config's GRAPH_RASTER")
+    ap.add_argument("--gt-graphs", default=None, nargs="*", metavar="FILE",
+                    help="(extension) one sat2graph pickle per --images entry ('-' = none) for --diff; without --images the dataset's own")
     args = ap.parse_args(argv)
     config = load_config(args.config)
+    if args.viz or args.graph_mask is not None or args.diff is not None:
+        config.GRAPH_RASTER = graph_raster_override(config, args.viz, args.graph_mask, True if args.diff == [] else args.diff)
+    raster = graph_raster_key(config)            # a GRAPH_RASTER that cannot be used fails here, before the model is built
+    if args.gt_graphs is not None and (args.images is None or len(args.gt_graphs) != len(args.images)):
+        ap.error("--gt-graphs takes exactly one entry per --images entry ('-' for a scene without a ground-truth graph)")
+    if raster is not None and raster.diff is not None and args.images is not None and args.gt_graphs is None:
+        raise ValueError("GRAPH_RASTER: diff needs ground-truth graphs: pass --gt-graphs with --images")
     job_aois = None
     if any(v is not None for v in (args.aoi, args.aoi_exclude, args.aoi_geotransform, args.aoi_buffer)):
         if args.aoi is not None and len(args.aoi) > 1 and (args.images is None or len(args.aoi) != len(args.images)):
@@ -2351,14 +2376,23 @@ def main(argv=None):
     else:
         raise ValueError(f"config.DATASET must be 'cityscale' or 'spacenet' (got {config.DATASET!r}), or pass --images")
     job_masks = [None if m == "-" else m for m in args.valid_masks] if args.valid_masks is not None else [None] * len(jobs)
+    job_gts = [None] * len(jobs)                 # the ground-truth graph of every scene, for GRAPH_RASTER's diff
+    if raster is not None and raster.diff is not None:
+        if args.images is not None:
+            job_gts = [None if g == "-" else g for g in args.gt_graphs]
+        else:                                    # the reference's gt_graph_pattern (inferencer.py:259,263)
+            pat = "cityscale/20cities/region_{}_graph_gt.pickle" if config.DATASET == "cityscale" else "./spacenet/RGB_1.0_meter/{}__gt_graph.p"
+            job_gts = [pat.format(i) for i, _ in jobs]
     if by_scene:
         jobs = jobs[rank::world]                 # independent scenes: round-robin over the ranks, nothing to exchange
         job_masks = job_masks[rank::world]
+        job_gts = job_gts[rank::world]
         job_aois = job_aois[rank::world] if job_aois is not None else None
     use_alpha = args.valid_masks is None and any(has_alpha(p) for _, p in jobs)      # headers only; mask files take precedence
     masked = args.valid_masks is not None or use_alpha
     import collections
     scene_valids = collections.deque()           # the masks of the scenes the loader has handed out, in the same order
+    render_inputs = collections.deque()          # GRAPH_RASTER: (scene, mask) of the scenes handed out, until their graphs come back
 
     output_dir_prefix = "./save/infer_"
     if world > 1:                                # one directory for all ranks: rank 0 creates it (and its timestamp), the others wait
@@ -2389,6 +2423,8 @@ def main(argv=None):
                         futs[k] = ex.submit(load, jobs[k][1], job_masks[k])
                 img, valid = futs.pop(j).result()
                 scene_valids.append(valid)
+                if raster is not None:
+                    render_inputs.append((img, valid))
                 yield img
 
     def valids():                                # infer_imgs reads a scene, then its mask
@@ -2412,6 +2448,25 @@ def main(argv=None):
             pickle.dump(convert_to_sat2graph_format(pred_nodes, pred_edges), f)
         print(f"Done for {img_id}.")
 
+    # GRAPH_RASTER: a scene's renders run on a writer thread, on a stream of their own — upload of the graph (and of the scene, once),
+    # the launches, the download, the PNG encoding — so the feeding thread hands the graph over and goes straight back to the GPU, and the
+    # wait for scene i's render does not queue behind scene i+1's pass 1.  The entries touch no workspace of the library context.
+    render_dirs = {} if raster is None else {k: os.path.join(output_dir, d) for k, d, on in (("viz", "viz", raster.viz), ("mask", "graph_mask", raster.mask),
+                                                                                          ("diff", "diff", raster.diff)) if on is not None}
+    for d in render_dirs.values():
+        os.makedirs(d, exist_ok=True)
+    render_stream = torch.cuda.Stream(device) if raster is not None and device.type == "cuda" else None
+
+    def render_scene(img_id, img, valid, pred_nodes, pred_edges, shape, gt_path):
+        import contextlib
+        gt = None if gt_path is None else read_gt_graph(gt_path, spacenet=args.images is None and config.DATASET == "spacenet")
+        with torch.cuda.stream(render_stream) if render_stream is not None else contextlib.nullcontext():
+            prod = render_graph(raster, pred_nodes, pred_edges, shape, img=img, gt=gt, valid=valid, net=net)
+        for k, d in render_dirs.items():
+            if k in prod:
+                Image.fromarray(prod[k]).save(os.path.join(d, f"{img_id}.png"), compress_level=1)
+        return img_id, prod.get("metrics")
+
     # the reference times infer_one_img per image (inferencer.py:292-296); the scenes are software-pipelined here (infer_imgs), so
     # the time reported is what the loop spends waiting for results — its sum over the images is the wall time of inference.  PNG
     # encoding and pickling (tens of ms per 2048^2 scene) run on two writer threads so that the loop goes straight back to the GPU.
@@ -2419,20 +2474,36 @@ def main(argv=None):
     results = infer_imgs(net, scenes(), config, device=device, tile_sharded=world > 1 and not by_scene,
                          pipelined=True if args.shard == "tiles-pipelined" else None, **(dict(valids=valids()) if masked else {}),
                          **(dict(aois=job_aois) if job_aois is not None else {}))
-    with ThreadPoolExecutor(2) as writer:
+    rendered = []
+    with ThreadPoolExecutor(2 + len(render_dirs)) as writer:
         pending = []
-        for img_id, path in jobs:
+        for (img_id, path), gt_path in zip(jobs, job_gts):
             print(f"Processing {img_id}")
             start_seconds = time.time()
             res = next(results)
             total_inference_seconds += time.time() - start_seconds
+            scene_img, scene_valid = render_inputs.popleft() if raster is not None else (None, None)
             if res is None:                      # non-zero rank of a tile-sharded run
                 continue
             pred_nodes, pred_edges, itsc_mask, road_mask = res
+            if raster is not None:               # rank 0 of a tile-sharded run, or this rank's own scene
+                rendered.append(writer.submit(render_scene, img_id, scene_img, scene_valid, pred_nodes, pred_edges, itsc_mask.shape, gt_path))
             pending += [writer.submit(write_png, road_mask, f"{img_id}_road.png"), writer.submit(write_png, itsc_mask, f"{img_id}_itsc.png"),
                         writer.submit(write_graph, img_id, pred_nodes, pred_edges)]
         for f in pending:
             f.result()
+        scene_metrics = [(str(i), m) for i, m in (f.result() for f in rendered) if m is not None]
+
+    if raster is not None and raster.diff is not None:
+        if by_scene:                             # every rank rendered its own scenes: rank 0 writes the one file
+            parts = [None] * world
+            dist.all_gather_object(parts, scene_metrics)
+            scene_metrics = [x for part in parts for x in part]
+        if rank == 0:
+            import json
+            with open(os.path.join(render_dirs["diff"], "metrics.json"), "w") as f:
+                json.dump({"thin": raster.diff[0], "wide": raster.diff[1], "scenes": dict(scene_metrics),
+                           "total": total_metrics([m for _, m in scene_metrics])}, f, indent=1)
 
     if world > 1:                                # the slowest rank is the wall time of the run
         t = torch.tensor([total_inference_seconds], dtype=torch.float64, device=device)

@@ -174,7 +174,116 @@ class _TopoNetParams(nn.Module):
         self.output_proj = nn.Linear(128, 1)
 
 
-class SAMRoad(nn.Module):
+class GraphRasterOps:
+    """The road graph as a raster on the device (GRAPH_RASTER; the rule in sam_road_amd/graph_raster.py): the three entries
+    srh_graph_raster / srh_graph_composite / srh_graph_compare on the device of `_graph_device()`, on torch's current stream.  They use
+    the library context for its device and its error text only — no weights, no workspace — so they may run on a stream of their own."""
+
+    def _graph_device(self):
+        raise NotImplementedError
+
+    def _graph_ctx(self):
+        dev = self._graph_device()
+        if dev.type != "cuda":
+            raise _lib.SrhError("the graph rasteriser runs on an MI355X only (device %s); there is no CPU fallback" % dev)
+        idx = dev.index if dev.index is not None else torch.cuda.current_device()
+        return _lib.Context.get(idx), torch.device("cuda", idx)
+
+    @staticmethod
+    def _graph_u8(name, t, shape, dev, optional=False):
+        if t is None and optional:
+            return None
+        if not torch.is_tensor(t) or t.device != dev or t.dtype not in (torch.uint8, torch.bool) or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous uint8 tensor of shape {tuple(shape)} on {dev}, got "
+                             f"{(t.dtype, tuple(t.shape), t.device) if torch.is_tensor(t) else type(t)}")
+        return t
+
+    @torch.no_grad()
+    def graph_raster(self, shape, nodes, edges, width, mark="none", radius=0, values=(1, 2), out=None):
+        """The class map of a graph over an image of shape (H, W) (srh_graph_raster): nodes int [N, 2] (row, col) and edges int [E, 2] on
+        the HOST, checked by graph_raster.check_graph -> a NEW uint8 [H, W] tensor on the device (or `out`, a contiguous uint8 tensor of
+        H W bytes there): values[1] on a node mark, else values[0] on an edge of `width`, else 0.  Three launches at most, no workspace of
+        the library context, nothing read back."""
+        from . import graph_raster as _gr
+        ctx, dev = self._graph_ctx()
+        H, W = int(shape[0]), int(shape[1])
+        if H < 1 or W < 1 or H * W > 2 ** 31 - 1:
+            raise ValueError(f"the image must have at least 1 x 1 and at most 2^31 - 1 pixels, got {H} x {W}")
+        n, e = _gr.check_graph(nodes, edges)
+        _gr.check_style(width, mark, radius)
+        if len(values) != 2 or not all(isinstance(v, int) and 1 <= v <= 255 for v in values):
+            raise ValueError(f"values must be two ints 1 .. 255 (edge, node), got {values!r}")
+        n_h, e_h = torch.from_numpy(n), torch.from_numpy(e)
+        n_d, e_d = n_h.to(dev), e_h.to(dev)
+        if out is None:
+            out = torch.empty((H, W), dtype=torch.uint8, device=dev)
+        elif out.device != dev or out.dtype != torch.uint8 or out.numel() != H * W or not out.is_contiguous():
+            raise ValueError(f"out must be a contiguous uint8 tensor of {H * W} pixels on {dev}, got {out.dtype} {tuple(out.shape)} on {out.device}")
+        N, E = int(n.shape[0]), int(e.shape[0])
+        with torch.cuda.device(dev):
+            ctx.check(ctx.lib.srh_graph_raster(ctx.handle, n_h.data_ptr() if N else None, n_d.data_ptr() if N else None, N,
+                                               e_h.data_ptr() if E else None, e_d.data_ptr() if E else None, E, H, W, int(width),
+                                               _lib.SRH_GRAPH_MARKS[mark], int(radius), values[0], values[1], out.data_ptr(),
+                                               SAMRoad._stream(dev)), "srh_graph_raster")
+        return out                                # the device tables were made on this stream and are read on it
+
+    @torch.no_grad()
+    def graph_composite(self, cls, img=None, edge_color=(253, 160, 15), node_color=(255, 255, 0), background=(0, 0, 0), out=None):
+        """The scene with the classes in colour (srh_graph_composite): cls uint8 [H, W] and img uint8 [H, W, 3] (or None: the background
+        colour) on the device -> a NEW uint8 [H, W, 3] tensor there (or `out`): node_color where cls >= 2, edge_color where cls == 1."""
+        import numpy as np
+        ctx, dev = self._graph_ctx()
+        if not torch.is_tensor(cls) or cls.dim() != 2:
+            raise ValueError("cls must be a uint8 [H, W] tensor")
+        H, W = cls.shape
+        cls = self._graph_u8("cls", cls, (H, W), dev)
+        img = self._graph_u8("img", img, (H, W, 3), dev, optional=True)
+        if img is not None and img.dtype != torch.uint8:
+            raise ValueError("img must be uint8")
+        cols = []
+        for name, c in (("background", background), ("edge_color", edge_color), ("node_color", node_color)):
+            if len(c) != 3 or not all(isinstance(v, (int, np.integer)) and not isinstance(v, bool) and 0 <= v <= 255 for v in c):
+                raise ValueError(f"{name} must be three ints 0 .. 255, got {c!r}")
+            cols.append((C.c_int32 * 3)(*[int(v) for v in c]))
+        out = torch.empty((H, W, 3), dtype=torch.uint8, device=dev) if out is None else self._graph_u8("out", out, (H, W, 3), dev)
+        with torch.cuda.device(dev):
+            ctx.check(ctx.lib.srh_graph_composite(ctx.handle, cls.data_ptr(), None if img is None else img.data_ptr(), H, W,
+                                                  C.addressof(cols[0]), C.addressof(cols[1]), C.addressof(cols[2]), out.data_ptr(),
+                                                  SAMRoad._stream(dev)), "srh_graph_composite")
+        return out
+
+    @torch.no_grad()
+    def graph_compare(self, pred_thin, pred_wide, gt_thin, gt_wide, valid=None, img=None, diff=False):
+        """Four class maps uint8 [H, W] on the device against each other (srh_graph_compare) -> (counts, diff image or None): counts an
+        int64 [4] tensor ON THE DEVICE, {n_pred, n_fp, n_gt, n_missed} over the pixels with valid != 0 (valid uint8 / bool [H, W] or
+        None); with diff=True the uint8 [H, W, 3] image, img (or black) with missed pixels red and false positives blue, from the same pass."""
+        ctx, dev = self._graph_ctx()
+        if not torch.is_tensor(pred_thin) or pred_thin.dim() != 2:
+            raise ValueError("the class maps must be uint8 [H, W] tensors")
+        H, W = pred_thin.shape
+        maps = [self._graph_u8(n, t, (H, W), dev) for n, t in (("pred_thin", pred_thin), ("pred_wide", pred_wide), ("gt_thin", gt_thin), ("gt_wide", gt_wide))]
+        valid = self._graph_u8("valid", valid, (H, W), dev, optional=True)
+        img = self._graph_u8("img", img, (H, W, 3), dev, optional=True)
+        counts = torch.empty(4, dtype=torch.int64, device=dev)
+        out = torch.empty((H, W, 3), dtype=torch.uint8, device=dev) if diff else None
+        with torch.cuda.device(dev):
+            ctx.check(ctx.lib.srh_graph_compare(ctx.handle, *[m.data_ptr() for m in maps], None if valid is None else valid.data_ptr(),
+                                                None if img is None else img.data_ptr(), H, W, counts.data_ptr(),
+                                                None if out is None else out.data_ptr(), SAMRoad._stream(dev)), "srh_graph_compare")
+        return counts, out
+
+
+class DeviceGraphOps(GraphRasterOps):
+    """GraphRasterOps without a model: the entries need a device, not weights."""
+
+    def __init__(self, device):
+        self.device = torch.device(device)
+
+    def _graph_device(self):
+        return self.device
+
+
+class SAMRoad(nn.Module, GraphRasterOps):
     def __init__(self, config):
         super().__init__()
         self.config = config
@@ -379,6 +488,9 @@ class SAMRoad(nn.Module):
                   "srh_weights_pack")
         self._packed[idx] = (ctx, handle)
         return self._packed[idx]
+
+    def _graph_device(self):                      # GraphRasterOps: the renders run where the model is
+        return next(self.parameters()).device
 
     # ---- entry points -------------------------------------------------------------------------------------------
     @staticmethod

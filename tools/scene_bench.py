@@ -41,6 +41,10 @@ The final map_decoder bias is lowered so that the random network yields sparse m
                                                                     # reports the device time of the nodata launches (match alone / the key as
                                                                     # given, per kernel), pass 1's, the pipelined loop unmasked / keyed / with the
                                                                     # identical mask passed as valid in turn, and the host time of nodata_ref
+    python tools/scene_bench.py --viz [--scene 4096 --tiles 32]     # GRAPH_RASTER: "graph_raster" compares the device class map with graph_raster_ref
+                                                                    # (the run ends if they differ), reports the device time of raster, composite and
+                                                                    # compare beside pass 1 and the host reference, and the pipelined loop with PNG
+                                                                    # writers without renders / with viz / with diff, alternated
     python tools/scene_bench.py --aoi-frac 0.4 [--scene 4096 --no-pipelined]    # SCENE_AOI: a star polygon that covers about 0.4 of the scene;
                                                                     # "scene_aoi" compares the device mask with aoi_ref (the run ends if they
                                                                     # differ) for the star, a hexagon, a 1000-vertex circle and a ring at the
@@ -495,6 +499,135 @@ def aoi_report(args, net, cfg, img, iters=20):
     return rep
 
 
+def road_grid(H, W, step, seed):
+    """A synthetic road-grid graph: nodes on a lattice of `step` pixels with a jitter of a quarter step, edges to the right and the lower neighbour."""
+    rng = np.random.default_rng(seed)
+    rr, cc = np.meshgrid(np.arange(step // 2, H, step), np.arange(step // 2, W, step), indexing="ij")
+    j = step // 4
+    nodes = np.stack([rr + rng.integers(-j, j + 1, rr.shape), cc + rng.integers(-j, j + 1, cc.shape)], axis=-1).reshape(-1, 2)
+    idx = np.arange(nodes.shape[0]).reshape(rr.shape)
+    edges = np.concatenate([np.stack([idx[:, :-1].ravel(), idx[:, 1:].ravel()], axis=1), np.stack([idx[:-1].ravel(), idx[1:].ravel()], axis=1)])
+    return nodes.astype(np.int64), edges.astype(np.int64)
+
+
+def graph_report(args, net, cfg, img, iters=20):
+    """--viz / --diff (GRAPH_RASTER): the class map against graph_raster_ref on this scene size (the run ends if they differ); device ms (events
+    around each of `iters` runs after a warm-up) of the raster at the viz style and at the diff's four styles, of the composite and of the
+    compare; host ms of graph_raster_ref; device ms of pass 1 of the same scene; and ms per scene of the pipelined loop as the CLI runs it —
+    mask PNGs on writer threads — without renders, with viz and with diff, alternated.  The graph is the scene's own if the stand-in weights
+    yield at least 1000 edges, else a synthetic road grid of 32-px cells; the ground truth is another grid."""
+    import sam_road_amd.inferencer as inf
+    from concurrent.futures import ThreadPoolExecutor
+    from PIL import Image
+    import io
+    from sam_road_amd import graph_raster as gr
+    dev = next(net.parameters()).device
+    H, W = img.shape[:2]
+    nodes, edges, _, _ = inf.infer_one_img(net, img, cfg)
+    own = edges.shape[0] >= 1000
+    if not own:
+        nodes, edges = road_grid(H, W, 32, 1)
+    gt = road_grid(H, W, 32, 2)
+    rep = {"graph": "the scene's own" if own else "synthetic road grid, 32-px cells", "nodes": int(nodes.shape[0]), "edges": int(edges.shape[0])}
+    t0 = time.perf_counter()
+    want = gr.graph_raster_ref(nodes, edges, (H, W), 4, "disc", 4)
+    rep["host_ms_graph_raster_ref"] = round(1e3 * (time.perf_counter() - t0), 1)
+    got = net.graph_raster((H, W), nodes, edges, 4, "disc", 4)
+    if not np.array_equal(got.cpu().numpy(), want):
+        raise SystemExit(f"the device class map differs from graph_raster_ref on {int((got.cpu().numpy() != want).sum())} px")
+    rep["equals_graph_raster_ref"], rep["covered_frac"] = True, round(float((want != 0).mean()), 4)
+    img_d = torch.from_numpy(img).to(dev)
+    maps = [net.graph_raster((H, W), *g, 2 * r, "square", r, values=(255, 255)) for g, r in (((nodes, edges), 1), ((nodes, edges), 5), (gt, 1), (gt, 5))]
+    m_dev, _ = gr.compare_graphs((nodes, edges), gt, (H, W), 1, 5, net=net)
+    t0 = time.perf_counter()
+    m_ref, _ = gr.compare_ref((nodes, edges), gt, (H, W), 1, 5, diff=False)
+    rep["host_ms_compare_ref"] = round(1e3 * (time.perf_counter() - t0), 1)
+    if m_dev != m_ref:
+        raise SystemExit(f"the device counts {m_dev} differ from compare_ref's {m_ref}")
+    rep["metrics"] = m_dev
+
+    def device_ms(fn):
+        fn()
+        evs = []
+        for _ in range(iters):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fn()
+            e1.record()
+            evs.append((e0, e1))
+        torch.cuda.synchronize()
+        ms = sorted(a.elapsed_time(b) for a, b in evs)
+        return {"median": round(ms[len(ms) // 2], 4), "min_max": [round(ms[0], 4), round(ms[-1], 4)]}
+
+    out3 = torch.empty((H, W, 3), dtype=torch.uint8, device=dev)
+    rep["device_ms"] = {"raster_viz_style_with_table_upload": device_ms(lambda: net.graph_raster((H, W), nodes, edges, 4, "disc", 4, out=got)),
+                        "raster_width_10_squares_5": device_ms(lambda: net.graph_raster((H, W), nodes, edges, 10, "square", 5, out=got)),
+                        "composite": device_ms(lambda: net.graph_composite(got, img_d, out=out3)),
+                        "compare_with_diff_image": device_ms(lambda: net.graph_compare(*maps, img=img_d, diff=True)),
+                        "compare_counts_only": device_ms(lambda: net.graph_compare(*maps))}
+    ctx, _ = net._weights(dev)
+    ctx.profile_read()
+    ctx.profile_enable(True)
+    for _ in range(iters):
+        net.graph_raster((H, W), nodes, edges, 4, "disc", 4, out=got)
+    torch.cuda.synchronize()
+    rep["raster_kernels_ms_per_call"] = {r["name"]: round(r["ms"] / r["launches"], 4) for r in ctx.profile_read() if r["launches"]}
+    ctx.profile_enable(False)
+    if args.no_pipelined:
+        return rep
+    inf._Lane.times = []
+    stream = torch.cuda.Stream(dev)
+
+    def png(a):
+        Image.fromarray(a).save(io.BytesIO(), format="PNG", compress_level=1)
+
+    stages = {}                                            # per product: (ms until the product is on the host, ms of its PNG encoding) per scene
+
+    def render(key, res):
+        t0 = time.perf_counter()
+        with torch.cuda.stream(stream):
+            prod = gr.render(key, res[0], res[1], (H, W), img=img, gt=gt, net=net)
+        t1 = time.perf_counter()
+        for k in ("viz", "mask", "diff"):
+            if k in prod:
+                png(prod[k])
+        stages.setdefault("viz" if key.viz is not None else "diff", []).append((1e3 * (t1 - t0), 1e3 * (time.perf_counter() - t1)))
+
+    def piped(key, n=12):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        waits = 0.0
+        with ThreadPoolExecutor(2 + (0 if key is None else 1)) as pool:
+            futs = []
+            for res in inf.infer_imgs(net, (img for _ in range(n)), cfg):
+                futs += [pool.submit(png, res[2]), pool.submit(png, res[3])]
+                if key is not None:
+                    futs.append(pool.submit(render, key, res))
+            t1 = time.perf_counter()
+            for f in futs:
+                f.result()
+            waits = time.perf_counter() - t1
+        torch.cuda.synchronize()
+        return round(1e3 * (time.perf_counter() - t0) / n, 2), round(1e3 * waits / n, 2)
+
+    keys = {"without": None, "viz": gr.graph_raster_key_of({"viz": True}), "diff": gr.graph_raster_key_of({"diff": True})}
+    for k in keys.values():
+        piped(k, 3)
+    inf._Lane.times.clear()
+    stages.clear()
+    runs = {k: [] for k in keys}
+    for _ in range(3):
+        for name, k in keys.items():
+            runs[name].append(piped(k))
+    rep["pipelined_ms_per_scene_and_writer_drain_ms_runs_of_12_alternated"] = runs
+    med = lambda v: round(sorted(v)[len(v) // 2], 2)
+    rep["writer_thread_ms_per_scene_median"] = {k: {"upload_launch_wait_download": med([a for a, _ in v]), "png_encode": med([b for _, b in v])} for k, v in stages.items()}
+    p1 = sorted(t[1] for t in inf._Lane.times)
+    rep["pass1_device_ms_median_of_all_scenes_above"] = round(p1[len(p1) // 2], 2) if p1 else None
+    inf._Lane.times = None
+    return rep
+
+
 def float_report(args, net, cfg, img, rng, iters=20):
     """--float C [--float-range LO HI] [--float-percentile P Q]: the scene as a C-band float32 scene (bands 0..2 hold the synthetic RGB / 255,
     the rest noise).  The device result against float_scene_ref for both keys (the run ends if they differ); device ms of each SCENE_FLOAT
@@ -631,6 +764,9 @@ def main():
     ap.add_argument("--aoi-frac", type=float, default=None, metavar="F",
                     help="SCENE_AOI: a star polygon that covers about F of the scene; the device mask is compared with aoi_ref, and scene_aoi_fill, pass 1 "
                          "and the pipelined loop are timed (one GPU; --no-pipelined: the fill alone)")
+    ap.add_argument("--viz", action="store_true", help="GRAPH_RASTER: time the graph's renders (raster, composite, compare) on this scene and the pipelined "
+                                                       "loop with and without them (the same leg as --diff)")
+    ap.add_argument("--diff", action="store_true", help="GRAPH_RASTER: the same leg as --viz")
     ap.add_argument("--float", type=int, default=None, metavar="C",
                     help="SCENE_FLOAT: the scene arrives as a float32 scene of C bands (bands 0..2 hold the synthetic RGB / 255, the rest noise); "
                          "the three launches, the pipelined loop with a fixed range and with a percentile stretch and the host reference are timed")
@@ -733,6 +869,11 @@ def main():
             ap.error("--aoi-frac F, 0 < F <= 1, times one unmasked u8 scene on one GPU (not with --scenes, --valid-frac, --scale or --bands)")
         cfg.SCENE_AOI = {"include": [aoi_star(H, W, args.aoi_frac)]}
         print(json.dumps({"scene": f"synthetic {H}x{W} under a star polygon", "infer_batch_size": args.batch, "scene_aoi": aoi_report(args, net, cfg, img)}))
+        return
+    if args.viz or args.diff:
+        if world > 1 or args.scenes is not None or args.valid_frac is not None or args.scale is not None or args.bands is not None:
+            ap.error("--viz / --diff time one unmasked u8 scene on one GPU (not with --scenes, --valid-frac, --scale or --bands)")
+        print(json.dumps({"scene": f"synthetic {H}x{W}", "infer_batch_size": args.batch, "graph_raster": graph_report(args, net, cfg, img)}))
         return
     if args.float is not None:
         if world > 1 or args.scenes is not None or args.valid_frac is not None or args.scale is not None or args.bands is not None:
