@@ -548,12 +548,19 @@ int srh_op_attention_hd(srh_ctx* ctx, const void* qkv_f16, const void* relpos_h_
  *     pixels of a `patch`-px tile; point_tile i32 [B*N] (nullable: point i samples tile i / N, B <= n_tiles; else clamped into
  *     [0, n_tiles)) -> out_f32 / out_f16 [B*N, C] (at least one);
  *   srh_op_pair_gather: pair rows [B*Ns*K, ld] fp16 = src | tgt features of pf_f16 [B*N,128] | dx dy (0 with zero_offset) | 0, pairs
- *     [B,Ns,K,2] (SRH_I32 / SRH_I64) minus index_base; a negative index wraps python-style only when index_base == 0. */
+ *     [B,Ns,K,2] (SRH_I32 / SRH_I64) minus index_base; a negative index wraps python-style only when index_base == 0;
+ *   srh_op_topo_trunk (additive, the ABI stays 11): the fused TopoNet trunk of `w` alone (pair_proj, the encoder layers of its
+ *     TOPONET_VERSION, output_proj, sigmoid: srh_toponet's last launch and its parameter block) on pair rows pair_f16 [nseq*K, ld] fp16
+ *     (16-byte aligned; ld >= 320, ld % 8 == 0; columns 258 .. 319 are read against zero weights and must be finite) and valid u8
+ *     [nseq, K] (4-byte aligned; any non-zero byte counts) -> logits / scores f32 [nseq*K], both nullable.  SRH_ERR_BAD_ARG for a bad ld,
+ *     a null or misaligned input; SRH_ERR_UNSUPPORTED for K outside 1 .. 64; nseq == 0 is a no-op.  Nothing is launched in these cases. */
 int srh_op_map_decoder(srh_ctx* ctx, const srh_weights* w, const void* emb_f16, int B, float* mask_logits, float* mask_scores, void* stream);
 int srh_op_sample(srh_ctx* ctx, const float* emb_f32, int n_tiles, int h, int w, int C, const void* points, int points_dtype,
                   const int32_t* point_tile, int B, int N, float patch, float* out_f32, void* out_f16, void* stream);
 int srh_op_pair_gather(srh_ctx* ctx, const void* pf_f16, const void* points, int points_dtype, const void* pairs, int pairs_dtype,
                        int B, int N, int Ns, int K, int zero_offset, int64_t index_base, void* out_f16, int ld, void* stream);
+int srh_op_topo_trunk(srh_ctx* ctx, const srh_weights* w, const void* pair_f16, int ld, const uint8_t* valid, int nseq, int K,
+                      float* logits, float* scores, void* stream);
 
 /* profiling --------------------------------------------------------------------------------------- */
 

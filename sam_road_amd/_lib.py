@@ -106,6 +106,7 @@ SYMBOLS = {
     "srh_op_map_decoder": (_I, [_P, _P, _P, _I, _P, _P, _P]),
     "srh_op_sample": (_I, [_P, _P, _I, _I, _I, _I, _P, _I, _P, _I, _I, _F, _P, _P, _P]),
     "srh_op_pair_gather": (_I, [_P, _P, _P, _I, _P, _I, _I, _I, _I, _I, _I, C.c_int64, _P, _I, _P]),
+    "srh_op_topo_trunk": (_I, [_P, _P, _P, _I, _P, _I, _I, _P, _P, _P]),
     "srh_nms_points_host": (_I, [_P, _P, C.c_int64, C.c_int32, _P]),
     "srh_pass2_count": (_I, [_P, C.c_int64, _P, C.c_int32, _P]),
     "srh_pass2_fill": (_I, [_P, C.c_int64, _P, C.c_int32, C.c_int32, C.c_int64, _P, _P, _P, _P, _P, C.c_int32]),

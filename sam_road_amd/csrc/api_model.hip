@@ -318,9 +318,7 @@ static int toponet_impl(srh_ctx* c, const srh_weights* w, const float* embedding
     TRYK(c, "pair_gather", 0, (double)R * (512 + 640), s, launch_pair_gather(pg, s));
     {
         // pair_proj + encoder layers + output_proj in one register-resident kernel (topo_fused.hip)
-        TopoFusedParams tf;
-        tf.pair = c->t_pair16.as<f16>(); tf.ld_pair = 320; tf.valid = valid; tf.stream = w->tp_stream; tf.params = w->tp_params;
-        tf.nlayers = w->tp_layers; tf.nseq = B * Ns; tf.K = K; tf.logits = logits; tf.scores = scores;
+        const TopoFusedParams tf = topo_fused_params(w, c->t_pair16.as<f16>(), 320, valid, B * Ns, K, logits, scores);
         const double fl = (double)R * (2.0 * 320 * 128 + tf.nlayers * (2.0 * 128 * 768 + 4.0 * K * 128) + 256);
         TRYK(c, "topo_fused", fl, 0, s, launch_topo_fused(tf, s));
         return 0;

@@ -129,6 +129,25 @@ extern "C" int srh_op_pair_gather(srh_ctx* c, const void* pf_f16, const void* po
     return 0;
 }
 
+// The fused TopoNet trunk alone (topo_fused.hip: pair_proj, the encoder layers, output_proj, sigmoid) on caller-supplied pair rows.
+// The kernel reads rows as 16-byte vectors up to column 320 and, at K = 16, the valid bytes four at a time: hence the alignment rules.
+extern "C" int srh_op_topo_trunk(srh_ctx* c, const srh_weights* w, const void* pair_f16, int ld, const uint8_t* valid, int nseq, int K,
+                                 float* logits, float* scores, void* stream) {
+    if (!c || !w || !pair_f16 || !valid) return fail(c, SRH_ERR_BAD_ARG, "srh_op_topo_trunk: null argument");
+    if (ld < 320 || ld % 8 != 0) return fail(c, SRH_ERR_BAD_ARG, "srh_op_topo_trunk: ld must be a multiple of 8 and at least 320");
+    if (((uintptr_t)pair_f16 & 15) || ((uintptr_t)valid & 3))
+        return fail(c, SRH_ERR_BAD_ARG, "srh_op_topo_trunk: pair rows must be 16-byte aligned and valid 4-byte aligned");
+    if (K < 1 || K > 64) return fail(c, SRH_ERR_UNSUPPORTED, "srh_op_topo_trunk: K (MAX_NEIGHBOR_QUERIES) must be 1 to 64");
+    if (nseq < 0 || (int64_t)nseq * K > 0x7fffffffLL) return fail(c, SRH_ERR_BAD_ARG, "srh_op_topo_trunk: bad sequence count");
+    if (!w->tp_stream || !w->tp_params) return fail(c, SRH_ERR_UNSUPPORTED, "srh_op_topo_trunk: the weights have no packed trunk");
+    if (nseq == 0 || (!logits && !scores)) return 0;
+    hipSetDevice(c->device);
+    hipStream_t s = (hipStream_t)stream;
+    const TopoFusedParams tf = topo_fused_params(w, (const f16*)pair_f16, ld, valid, nseq, K, logits, scores);
+    TRYK(c, "topo_fused", 0, 0, s, launch_topo_fused(tf, s));
+    return 0;
+}
+
 static int op_attention_impl(srh_ctx* c, const char* who, const void* qkv, const void* rel_h, const void* rel_w, const void* bias_qkv,
                              int B, int S, int heads, int hd, int win, void* out, void* stream) {
     if (!c || !qkv || !rel_h || !rel_w || !bias_qkv || !out) return fail(c, SRH_ERR_BAD_ARG, std::string(who) + ": null argument");

@@ -167,3 +167,11 @@ static PairGatherParams pair_gather_params(const f16* pf, const void* points, in
     pg.zero_offset = zero_offset; pg.out = out; pg.ld = ld; pg.index_base = index_base;
     return pg;
 }
+// the fused trunk on the packed stream / parameter block / layer count of `w`
+static TopoFusedParams topo_fused_params(const srh_weights* w, const f16* pair, int ld, const uint8_t* valid, int nseq, int K, float* logits,
+                                         float* scores) {
+    TopoFusedParams tf;
+    tf.pair = pair; tf.ld_pair = ld; tf.valid = valid; tf.stream = w->tp_stream; tf.params = w->tp_params;
+    tf.nlayers = w->tp_layers; tf.nseq = nseq; tf.K = K; tf.logits = logits; tf.scores = scores;
+    return tf;
+}

@@ -62,6 +62,26 @@ RESID_LN_F16 = 5e-3          # measured 1.9e-3 .. 3.91e-3 (half an fp16 ulp in [
 # (its coefficient there is 2e-4, against a float32 product; against float64, with f32 accumulation of K <= 5120 terms of O(0.03):)
 RESID_GEMM_F32 = 1e-7        # measured 1.8e-8 .. 2.3e-8 (split-K chain), 2.5e-8 .. 3.7e-8 (pos epilogue), 8.2e-9 .. 8.7e-9 (pos against a host-side add)
 
+# ---- the fused TopoNet trunk at op level (tests/test_gpu_topo_trunk.py, against tests/heads_ref.py topo_trunk_ref / toponet_ref in float64;
+# the record of the measured values is profiles/parity_measured_op_topo.json) ---------------------------------------------------------
+# heads_ref.topo_fill's model (fp16-representable matrices, biases and betas ~ N(0, 1), gammas in +-[1, 2], peaked and flat softmax rows;
+# logits of O(1..5)), max-abs over the defined slots of every sequence count of a case.  A priori: the kernel's fp16 roundings (every
+# MFMA operand: the pair_proj and LayerNorm outputs, q, k, v, the unnormalised P, O, the FFN's hidden activation) simulated in float64
+# on the same inputs (topo_trunk_ref round_points=True) give logits 1.35e-3 .. 2.07e-3 and scores 2.8e-4 .. 4.4e-4 over the 13 K; the
+# kernel lands on them (K = 1: 1.353e-3 simulated and measured), so its f32 arithmetic, exp2 and rsqrt add nothing visible.
+TOPO_OP_LOGIT = 4.5e-3       # measured 1.35e-3 .. 2.19e-3 (K = 1 .. 64: packed slots, one wave, wave groups of 2 .. 4)
+TOPO_OP_SCORE = 9.5e-4       # measured 2.8e-4 .. 4.6e-4
+# TOPONET_VERSION no_transformer: pair_proj, ReLU and output_proj only; the fp16 inputs and weights are exact, the rest is f32.  A priori:
+# f32 accumulation of 258 products of O(1) and of 128 of O(1): a few 1e-7 of logits of O(5) (round_points changes nothing here).
+TOPO_OP_NOATT_LOGIT = 2.5e-6 # measured 6.8e-7 .. 9.5e-7
+TOPO_OP_NOATT_SCORE = 5e-7   # measured 1.3e-7 .. 1.8e-7
+# srh_toponet (sampler, feature_proj, pair gather, trunk) on the same model against toponet_ref, which rounds the three fp16 buffers
+# between the launches as the library does.  A priori (the trunk's roundings on top): logits 9.2e-4 .. 1.42e-3, scores 2.0e-4 .. 3.1e-4;
+# the measured values reach 1.4x that: the library rounds f32 sampler and GEMM results to fp16, the reference float64 ones, and a value
+# that falls on the other side of a rounding boundary enters the trunk one fp16 ulp off.
+TOPO_CHAIN_LOGIT = 5e-3      # measured 8.7e-4 .. 2.03e-3 (K = 5, 16, 33; f32 and i64 points)
+TOPO_CHAIN_SCORE = 1e-3      # measured 1.7e-4 .. 4.3e-4
+
 _REC = {}
 
 
