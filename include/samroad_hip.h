@@ -553,7 +553,13 @@ int srh_op_attention_hd(srh_ctx* ctx, const void* qkv_f16, const void* relpos_h_
  *     TOPONET_VERSION, output_proj, sigmoid: srh_toponet's last launch and its parameter block) on pair rows pair_f16 [nseq*K, ld] fp16
  *     (16-byte aligned; ld >= 320, ld % 8 == 0; columns 258 .. 319 are read against zero weights and must be finite) and valid u8
  *     [nseq, K] (4-byte aligned; any non-zero byte counts) -> logits / scores f32 [nseq*K], both nullable.  SRH_ERR_BAD_ARG for a bad ld,
- *     a null or misaligned input; SRH_ERR_UNSUPPORTED for K outside 1 .. 64; nseq == 0 is a no-op.  Nothing is launched in these cases. */
+ *     a null or misaligned input; SRH_ERR_UNSUPPORTED for K outside 1 .. 64; nseq == 0 is a no-op.  Nothing is launched in these cases.
+ *   srh_op_sam_decoder (additive, the ABI stays 11): the SAM MaskDecoder branch of `w` alone (USE_SAM_DECODER: the launch sequence
+ *     srh_encode_decode runs after the neck, the same function) on a neck output emb_f32 [B*S*S, 256] f32, token-major -> mask_logits /
+ *     mask_scores [B,P,P,2] f32, and two intermediates copied out of the context's workspace on the same stream: tokens_out [B,4,256]
+ *     (the IoU token and the three mask tokens after norm_final_attn) and low_res [B,2,4S,4S] (the logits of mask tokens 1 and 2 before
+ *     the bilinear x4 upsample).  All four outputs are nullable; with none it is a no-op.  SRH_ERR_UNSUPPORTED for weights packed without
+ *     use_sam_decoder, SRH_ERR_BAD_ARG for a null ctx / weights / input or B <= 0; nothing is launched in these cases. */
 int srh_op_map_decoder(srh_ctx* ctx, const srh_weights* w, const void* emb_f16, int B, float* mask_logits, float* mask_scores, void* stream);
 int srh_op_sample(srh_ctx* ctx, const float* emb_f32, int n_tiles, int h, int w, int C, const void* points, int points_dtype,
                   const int32_t* point_tile, int B, int N, float patch, float* out_f32, void* out_f16, void* stream);
@@ -561,6 +567,8 @@ int srh_op_pair_gather(srh_ctx* ctx, const void* pf_f16, const void* points, int
                        int B, int N, int Ns, int K, int zero_offset, int64_t index_base, void* out_f16, int ld, void* stream);
 int srh_op_topo_trunk(srh_ctx* ctx, const srh_weights* w, const void* pair_f16, int ld, const uint8_t* valid, int nseq, int K,
                       float* logits, float* scores, void* stream);
+int srh_op_sam_decoder(srh_ctx* ctx, const srh_weights* w, const float* emb_f32, int B, float* mask_logits, float* mask_scores,
+                       float* tokens_out, float* low_res, void* stream);
 
 /* profiling --------------------------------------------------------------------------------------- */
 

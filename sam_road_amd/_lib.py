@@ -104,6 +104,7 @@ SYMBOLS = {
     "srh_op_attention": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P]),
     "srh_op_attention_hd": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P]),
     "srh_op_map_decoder": (_I, [_P, _P, _P, _I, _P, _P, _P]),
+    "srh_op_sam_decoder": (_I, [_P, _P, _P, _I, _P, _P, _P, _P, _P]),
     "srh_op_sample": (_I, [_P, _P, _I, _I, _I, _I, _P, _I, _P, _I, _I, _F, _P, _P, _P]),
     "srh_op_pair_gather": (_I, [_P, _P, _P, _I, _P, _I, _I, _I, _I, _I, _I, C.c_int64, _P, _I, _P]),
     "srh_op_topo_trunk": (_I, [_P, _P, _P, _I, _P, _I, _I, _P, _P, _P]),

@@ -32,7 +32,7 @@ static int ensure_encoder_ws(srh_ctx* c, const srh_weights* w, int B) {
 }
 
 // ---- SAM MaskDecoder branch (model.py:426-443 / :471-488; kernels in sam_decoder.hip, semantics in oracle/sam_decoder.py) ----
-static int sam_decode(srh_ctx* c, const srh_weights* w, int B, const float* emb, float* logits, float* scores, hipStream_t s) {
+int sam_decode(srh_ctx* c, const srh_weights* w, int B, const float* emb, float* logits, float* scores, hipStream_t s) {
     const int S = w->S, HW = S * S, R = B * 4, P = w->cfg.patch_size;
     const size_t T = (size_t)B * HW;
     const SdW& d = w->sd;

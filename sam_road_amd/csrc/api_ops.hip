@@ -101,6 +101,23 @@ extern "C" int srh_op_map_decoder(srh_ctx* c, const srh_weights* w, const void* 
     return 0;
 }
 
+// The SAM MaskDecoder branch alone: encode_batch's sam_decode() on a caller-supplied neck output, plus two of its intermediates copied
+// out of the workspace behind it on the same stream (the queries after norm_final_attn, sd_mask's low-res logits before the upsample).
+extern "C" int srh_op_sam_decoder(srh_ctx* c, const srh_weights* w, const float* emb_f32, int B, float* mask_logits, float* mask_scores,
+                                  float* tokens_out, float* low_res, void* stream) {
+    if (!c || !w || !emb_f32 || B <= 0) return fail(c, SRH_ERR_BAD_ARG, "srh_op_sam_decoder: bad argument");
+    if (!w->cfg.use_sam_decoder) return fail(c, SRH_ERR_UNSUPPORTED, "srh_op_sam_decoder: the weights were packed without use_sam_decoder");
+    if (!mask_logits && !mask_scores && !tokens_out && !low_res) return 0;
+    hipSetDevice(c->device);
+    hipStream_t s = (hipStream_t)stream;
+    TRY(sam_decode(c, w, B, emb_f32, mask_logits, mask_scores, s));
+    hipError_t e = hipSuccess;
+    if (tokens_out) e = hipMemcpyAsync(tokens_out, c->sd_tok.as<float>(), (size_t)B * 4 * 256 * 4, hipMemcpyDeviceToDevice, s);
+    if (e == hipSuccess && low_res)
+        e = hipMemcpyAsync(low_res, c->sd_low.as<float>(), (size_t)B * 2 * 16 * w->S * w->S * 4, hipMemcpyDeviceToDevice, s);
+    return e == hipSuccess ? 0 : hip_fail(c, e, "srh_op_sam_decoder");
+}
+
 extern "C" int srh_op_sample(srh_ctx* c, const float* emb_f32, int n_tiles, int h, int w, int C, const void* points, int points_dtype,
                              const int32_t* point_tile, int B, int N, float patch, float* out_f32, void* out_f16, void* stream) {
     if (!c || !emb_f32 || !points || (!out_f32 && !out_f16)) return fail(c, SRH_ERR_BAD_ARG, "srh_op_sample: null argument");

@@ -125,6 +125,9 @@ static bool tile_size_ok(int P) { return P >= 128 && P <= 1024 && P % 16 == 0; }
 SRH_INTERNAL double attn_flops(int B, int S, int heads, int hd, int win);
 SRH_INTERNAL int encode_batch(srh_ctx* c, const srh_weights* w, PatchParams pp, int B, float* logits, float* scores, float* emb, hipStream_t s,
                               int orient = 0, int scene_H = 0);
+// api_model.hip: the SAM MaskDecoder branch of encode_batch on a neck output emb f32 [B*S*S, 256] (srh_op_sam_decoder runs the same call).
+// It leaves the queries after norm_final_attn [B,4,256] at the start of c->sd_tok and sd_mask's output [B,2,4S,4S] in c->sd_low.
+SRH_INTERNAL int sam_decode(srh_ctx* c, const srh_weights* w, int B, const float* emb, float* logits, float* scores, hipStream_t s);
 
 // ---- parameter blocks: the model path and the srh_op_* entry of the same kernel build them here, so an op test runs the model's pattern
 // plain [M,K] . [N,K]^T: both operands dense; outputs, epilogue and a conv's lda / ldw are set by the caller

@@ -12,6 +12,10 @@
 //   * the two attentions are tiny per head (4 x HW scores): one workgroup per (tile, head) with the scores in LDS
 //     (token -> image), one thread per (image token, head) over the 4 token keys (image -> token).
 // Archived configs only: built for parity, not tuned.
+// Tested at op level through srh_op_sam_decoder (tests/test_gpu_samdec.py, against a float64 reference): S = 8 (HW = 64: three of the four
+// waves of sd_t2i_attn_kernel own no key; their maxima stay at -3e38 and their partial sums at zero), S = 9 and 25 (odd grids: ragged
+// GEMM M, HW no multiple of 64), S = 16, 32, and S = 64, where sd_t2i_attn_kernel needs (4 * 4096 + 16 + 272) * 4 = 66,688 bytes of dynamic
+// LDS: above 64 KiB, so the hipFuncSetAttribute opt-in of launch_sd_t2i_attn (80 KiB) is what lets PATCH_SIZE 1024 launch.
 #include <atomic>
 
 #include "common.hpp"

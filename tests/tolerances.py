@@ -82,6 +82,33 @@ TOPO_OP_NOATT_SCORE = 5e-7   # measured 1.3e-7 .. 1.8e-7
 TOPO_CHAIN_LOGIT = 5e-3      # measured 8.7e-4 .. 2.03e-3 (K = 5, 16, 33; f32 and i64 points)
 TOPO_CHAIN_SCORE = 1e-3      # measured 1.7e-4 .. 4.3e-4
 
+# ---- the SAM MaskDecoder branch at op level (tests/test_gpu_samdec.py, against tests/samdec_ref.py samdec_ref in float64; the record of
+# the measured values is profiles/parity_measured_op_samdec.json) ------------------------------------------------------------------------
+# samdec_ref.samdec_fill's model (fp16-representable image-side matrices, biases and betas ~ N(0, 1), gammas in +-[1, 2], peaked, in-between
+# and flat heads in every attention; mask logits up to +-20, projected keys up to +-130), max-abs over every element, seven shapes from
+# S = 8 to 64.  A priori: the library's fp16 roundings (the fp16 copy of the keys, the projected K / V / Q of the image side, the
+# image -> token attention output, the two upscaling activations) simulated in float64 on the same inputs (samdec_ref round_points=True;
+# tests/test_samdec_ref.py test_round_points_is_the_a_priori_error) give logits 7.5e-3 .. 9.1e-3, scores 1.7e-3 .. 2.1e-3, tokens_out
+# 9.7e-4 .. 2.4e-3 and low_res 9.8e-3 .. 1.12e-2 over the seven shapes.  The kernels land on the logits, scores and low_res (worst over
+# worst 1.04 x, 1.12 x, 1.06 x; per shape at most 1.2 x).  tokens_out: worst over worst 1.18 x, but 1.6 x at S = 64 and 1.45 x at S = 32.
+# Both figures are the largest of 1 k .. 5 k values and hang on a handful of projected keys of |k| ~ 100 (fp16 spacing 0.0625) in the
+# peaked token -> image heads, where the library rounds an f32 GEMM result and the simulation a float64 one: with f32-level noise
+# (+-2^-23) put on every value before its simulated fp16 rounding, the simulated tokens_out error itself moves between 0.9 x and 1.7 x
+# (1.8e-3 -> 3.0e-3 at S = 16, B = 5) and the logits' by up to 1.15 x.  So the same mechanism as the TopoNet chain's 1.4 x, nothing added
+# by the kernels' f32 arithmetic, __expf or gelu_fast.
+SAMDEC_OP_LOGIT = 1.4e-2     # measured 7.2e-3 .. 9.4e-3 (S = 8 .. 64)
+SAMDEC_OP_SCORE = 3.5e-3     # measured 1.5e-3 .. 2.3e-3
+SAMDEC_OP_TOKENS = 4.5e-3    # measured 1.4e-3 .. 2.9e-3 (values of O(3))
+SAMDEC_OP_LOWRES = 1.8e-2    # measured 8.8e-3 .. 1.19e-2 (values up to +-24)
+# sd_upsample_kernel on the low_res the device returned: f32 arithmetic on given inputs, max-abs error / max|low_res|.  A priori: the
+# source coordinates and weights are exact (multiples of 1/8); two lerps = four products and two sums, each rounded once: at most
+# 4 x 2^-24 = 2.4e-7 of max|low_res|, the result's own rounding included.
+SAMDEC_UPSAMPLE_F32 = 3e-7   # measured 1.08e-7 .. 1.37e-7 (every pixel; 3.9e-8 .. 6.8e-8 on the rows and columns with clamped taps)
+# the scores against the float64 sigmoid of the returned logits, max-abs.  A priori: 1 / (1 + __expf(-x)): the exponent's argument and
+# exp2 round once each (relative (1 + |x|) 6e-8 on e, times the slope s (1 - s) <= 1/4), 1 + e, the division and the result round once
+# each (6e-8, 6e-8 and 3e-8 of s <= 1): about 1.2e-7.
+SAMDEC_SIGMOID_F32 = 2.5e-7  # measured 9.0e-8 .. 9.3e-8
+
 _REC = {}
 
 
