@@ -468,6 +468,26 @@ int srh_graph_composite(srh_ctx* ctx, const uint8_t* cls, const uint8_t* img, in
 int srh_graph_compare(srh_ctx* ctx, const uint8_t* pred_thin, const uint8_t* pred_wide, const uint8_t* gt_thin, const uint8_t* gt_wide,
                       const uint8_t* valid, const uint8_t* img, int H, int W, uint64_t* counts, uint8_t* diff, void* stream);
 
+/* The road-mask evidence under every edge of a graph (config key EDGE_SUPPORT; an extension): the graph-domain post-check.
+ * The reference has none: its graph leaves as the votes produced it.  One additive entry; the ABI number stays 11 because nothing
+ * existing changes, and a run without the key does not call it.  It touches no workspace of the context and nothing is read back.
+ *
+ * Tables as srh_graph_raster takes them: nodes int32 [N, 2] (row, col) and edges int32 [E, 2], each given twice — the host copy is
+ * validated, the device copy (4-byte aligned) is what the kernel reads, and it is never written.  The covered set C_e of edge e is the
+ * set of pixels of [0, H) x [0, W) that srh_graph_raster's rule covers for this edge alone at width t.  mask u8 [H, W] and valid u8
+ * [H, W] or NULL on the device.  out int32 [E, 4] on the device, 16-byte aligned, per edge
+ *   {n = |C_e|, s = sum of mask over C_e, n_on = #(mask > on_level in C_e), n_invalid = #(valid == 0 in C_e), 0 without valid}
+ * — integer sums, the same numbers in any order; n < 6.0e6 and 255 n < 2^31 for every edge the tables admit.  An edge wholly outside
+ * the image gives {0, 0, 0, 0}.  Every element of out is defined after the call and nothing else is written: one launch, a wave per
+ * edge, one 16-byte store per edge, no atomics.  E = 0 is SRH_OK and launches nothing (mask and out may then be NULL).
+ * SRH_ERR_BAD_ARG, and nothing is launched, for every condition srh_graph_raster refuses (a null table of a non-empty graph, a negative
+ * count, H or W < 1 or H W > 2^31 - 1, t outside 1 .. 255, a coordinate outside +-2^28, an edge index outside [0, N), an edge spanning
+ * more than SRH_GRAPH_MAX_SPAN pixels on an axis, a misaligned device table), on_level outside 0 .. 255, a null mask or out with E > 0,
+ * an out that is not 16-byte aligned, or an out overlapping an input.  Profiler row: graph_edge_stats. */
+int srh_graph_edge_stats(srh_ctx* ctx, const int32_t* nodes_host, const int32_t* nodes_dev, int N, const int32_t* edges_host,
+                         const int32_t* edges_dev, int E, int H, int W, int t, const uint8_t* mask, const uint8_t* valid, int on_level,
+                         int32_t* out, void* stream);
+
 /* op level (used by the parity tests to localise a failure; same kernels as above) ----------------- */
 
 /* out = act(A[M,K] W[N,K]^T + bias) (+resid); A,W fp16; N%128==0, K%64==0. act: 0/1 GELU/2 ReLU. */

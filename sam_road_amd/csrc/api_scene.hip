@@ -518,3 +518,31 @@ extern "C" int srh_graph_compare(srh_ctx* c, const uint8_t* pred_thin, const uin
     TRYK(c, "graph_compare", 0, px * (4 + (valid ? 1 : 0) + (diff ? (img ? 6 : 3) : 0)), s, launch_graph_compare(p, s));
     return 0;
 }
+
+// ---- the road-mask evidence under every edge (kernel in edge_support.hip, behaviour in DESIGN.md §6p) ------------------------------------------
+extern "C" int srh_graph_edge_stats(srh_ctx* c, const int32_t* nodes_host, const int32_t* nodes_dev, int N, const int32_t* edges_host,
+                                    const int32_t* edges_dev, int E, int H, int W, int t, const uint8_t* mask, const uint8_t* valid, int on_level,
+                                    int32_t* out, void* stream) {
+    if (!c || N < 0 || E < 0 || (N > 0 && (!nodes_host || !nodes_dev)) || (E > 0 && (!edges_host || !edges_dev || !mask || !out)))
+        return fail(c, SRH_ERR_BAD_ARG, "srh_graph_edge_stats: null argument or a negative count");
+    if (H < 1 || W < 1 || (double)H * W > (double)GR_MAX_PIXELS) return fail(c, SRH_ERR_BAD_ARG, "srh_graph_edge_stats: H and W are at least 1 and H W at most 2^31 - 1");
+    if (t < 1 || t > GR_MAX_WIDTH) return fail(c, SRH_ERR_BAD_ARG, "srh_graph_edge_stats: the width is 1 to 255");
+    if (on_level < 0 || on_level > 255) return fail(c, SRH_ERR_BAD_ARG, "srh_graph_edge_stats: on_level is 0 to 255");
+    if ((reinterpret_cast<uintptr_t>(nodes_dev) | reinterpret_cast<uintptr_t>(edges_dev)) & 3) return fail(c, SRH_ERR_BAD_ARG, "srh_graph_edge_stats: the device tables are 4-byte aligned");
+    if (reinterpret_cast<uintptr_t>(out) & 15) return fail(c, SRH_ERR_BAD_ARG, "srh_graph_edge_stats: out is 16-byte aligned");
+    if (!gr_tables_ok(nodes_host, N, edges_host, E))
+        return fail(c, SRH_ERR_BAD_ARG, "srh_graph_edge_stats: an inconsistent table (coordinates within +-2^28, edge indices in [0, N), an edge spans at most "
+                                        "16383 px per axis)");
+    if (E == 0) return 0;                        // nothing to write, nothing launched
+    const double px = (double)H * W, ob = 16.0 * E;
+    if (ranges_overlap(out, ob, nodes_dev, 8.0 * N) || ranges_overlap(out, ob, edges_dev, 8.0 * E) || ranges_overlap(out, ob, mask, px) ||
+        (valid && ranges_overlap(out, ob, valid, px)))
+        return fail(c, SRH_ERR_BAD_ARG, "srh_graph_edge_stats: out overlaps an input");
+    EdgeStatsParams p;
+    p.g.nodes = nodes_dev; p.g.edges = edges_dev; p.g.N = N; p.g.E = E; p.g.H = H; p.g.W = W; p.g.t = t;
+    p.mask = mask; p.valid = valid; p.on_level = on_level; p.out = out;
+    hipSetDevice(c->device);
+    hipStream_t s = (hipStream_t)stream;
+    TRYK(c, "graph_edge_stats", 0, 40.0 * E, s, launch_graph_edge_stats(p, s));
+    return 0;
+}

@@ -12,6 +12,7 @@
 #include "scene_aoi_piece.hpp"
 #include "scene_float_piece.hpp"
 #include "graph_raster_piece.hpp"
+#include "edge_support_piece.hpp"
 
 namespace srh {
 
@@ -231,6 +232,9 @@ int launch_graph_nodes(const GraphRasterParams& p, hipStream_t s);
 int launch_graph_composite(const GraphCompositeParams& p, hipStream_t s);
 int launch_graph_counts_zero(const GraphCompareParams& p, hipStream_t s);
 int launch_graph_compare(const GraphCompareParams& p, hipStream_t s);
+// The road-mask evidence under every edge (edge_support.hip; the parameters in edge_support_piece.hpp): one launch, a wave
+// per edge, four int32 per edge.  E >= 1; the tables are on the device and have been checked on the host (gr_tables_ok).  -2 for bad parameters.
+int launch_graph_edge_stats(const EdgeStatsParams& p, hipStream_t s);
 
 // Bilinear sampler (F.grid_sample, align_corners=False, zeros) on channels-last embeddings.
 struct SampleParams {

@@ -28,6 +28,7 @@ from . import _lib
 from . import distributed as D
 from .aoi import aoi_edges, aoi_key_of, aoi_pack, aoi_ref, read_geojson, scene_aoi_key, scene_aoi_override
 from .graph_points import extract_graph_points
+from .edge_support import apply as apply_edge_support, edge_support_key, edge_support_override, write_geojson
 from .graph_raster import graph_raster_key, graph_raster_override, read_gt_graph, render as render_graph, total_metrics
 from .hostcpu import fill_threads, usable_cpus, worker_threads
 from .mask_clean import MaskRule, idle as _rule_idle, mask_clean_key, mask_clean_override, mask_clean_table
@@ -2172,6 +2173,11 @@ def main(argv=None):
     the dataset's own sat2graph pickles, or `--gt-graphs g0.p g1.p ...` parallel to `--images` ('-' = none for that scene).  They lay
     over the config's GRAPH_RASTER; the rule is sam_road_amd/graph_raster.py's, rasterised on the device on a stream of its own, encoded
     on the writer threads.  Without them the run writes the files and bytes it always wrote.
+    `--edge-min-mean M`, `--edge-min-on F`, `--edge-max-invalid K` (with `--edge-support-width T`, `--edge-on T`, `--drop-isolated-nodes`)
+    lay over the config's EDGE_SUPPORT (sam_road_amd/edge_support.py): the road mask under every edge is counted on the device and the
+    edges it does not support are dropped before the pickle, the renders and diff/metrics.json are written; `--graph-geojson` writes
+    graph_geojson/{id}.geojson, one LineString per edge with its evidence as properties, through `--geotransform G0 .. G5` into map
+    coordinates.  Without them nothing of this runs.
     Extras: `--images a.png b.npy ...` runs explicit scene files instead of the dataset split; under torchrun
     (one process per GPU) the scenes are dealt round-robin to the ranks (`--shard scenes`, default) or every scene's tiles are split
     over the ranks (`--shard tiles`; `tiles-pipelined` for the software-pipelined loop), all ranks writing into the one output directory.
@@ -2287,8 +2293,35 @@ def main(argv=None):
                          "graphs, overriding diff of the config's GRAPH_RASTER")
     ap.add_argument("--gt-graphs", default=None, nargs="*", metavar="FILE",
                     help="(extension) one sat2graph pickle per --images entry ('-' = none) for --diff; without --images the dataset's own")
+    ap.add_argument("--edge-support-width", default=None, type=int, metavar="T",
+                    help="(extension) the width 1..255 of the line under which an edge's road-mask evidence is counted (default 1: the "
+                         "8-connected centre line), overriding width of the config's EDGE_SUPPORT")
+    ap.add_argument("--edge-on", default=None, type=float, metavar="T",
+                    help="(extension) a pixel of the road mask is 'on' above floor(T * 255) (default ROAD_THRESHOLD), overriding on of the config's EDGE_SUPPORT")
+    ap.add_argument("--edge-min-mean", default=None, type=float, metavar="M",
+                    help="(extension) drop the edges whose mean road-mask value under the line is not above M (0..1), overriding min_mean of the "
+                         "config's EDGE_SUPPORT; the pickle, the renders, diff/metrics.json and the GeoJSON show the filtered graph")
+    ap.add_argument("--edge-min-on", default=None, type=float, metavar="F",
+                    help="(extension) drop the edges with less than the fraction F (0..1) of their pixels 'on', overriding min_on of the config's EDGE_SUPPORT")
+    ap.add_argument("--edge-max-invalid", default=None, type=int, metavar="K",
+                    help="(extension) drop the edges with more than K pixels on nodata or outside the area of interest (the scene's validity mask), "
+                         "overriding max_invalid of the config's EDGE_SUPPORT")
+    ap.add_argument("--drop-isolated-nodes", action="store_true", default=None,
+                    help="(extension) after the edge filter, drop the nodes without an edge (drop_isolated of the config's EDGE_SUPPORT)")
+    ap.add_argument("--graph-geojson", action="store_true", default=None,
+                    help="(extension) write graph_geojson/{id}.geojson: one LineString per edge, [x, y] = [col + 1/2, row + 1/2], with the "
+                         "edge's attributes of EDGE_SUPPORT as properties where the key is given")
+    ap.add_argument("--geotransform", default=None, nargs=6, type=float, metavar="G",
+                    help="(extension) G0 .. G5 of the GeoJSON export: X = G0 + x G1 + y G2, Y = G3 + x G4 + y G5 (the forward of --aoi-geotransform, "
+                         "whose value it takes when only that one is given)")
     args = ap.parse_args(argv)
     config = load_config(args.config)
+    if any(v is not None for v in (args.edge_support_width, args.edge_on, args.edge_min_mean, args.edge_min_on, args.edge_max_invalid, args.drop_isolated_nodes)):
+        config.EDGE_SUPPORT = edge_support_override(config, args.edge_support_width, args.edge_on, args.edge_min_mean, args.edge_min_on,
+                                                    args.edge_max_invalid, args.drop_isolated_nodes, attributes_only=bool(args.graph_geojson))
+    support = edge_support_key(config, attributes_only=bool(args.graph_geojson))      # an EDGE_SUPPORT that cannot be used fails here, before the model is built
+    export_gt = args.geotransform if args.geotransform is not None else args.aoi_geotransform
+    post = support is not None or bool(args.graph_geojson)                           # a step between a scene's result and its files
     if args.viz or args.graph_mask is not None or args.diff is not None:
         config.GRAPH_RASTER = graph_raster_override(config, args.viz, args.graph_mask, True if args.diff == [] else args.diff)
     raster = graph_raster_key(config)            # a GRAPH_RASTER that cannot be used fails here, before the model is built
@@ -2423,7 +2456,7 @@ def main(argv=None):
                         futs[k] = ex.submit(load, jobs[k][1], job_masks[k])
                 img, valid = futs.pop(j).result()
                 scene_valids.append(valid)
-                if raster is not None:
+                if raster is not None or post:
                     render_inputs.append((img, valid))
                 yield img
 
@@ -2455,7 +2488,10 @@ def main(argv=None):
                                                                                           ("diff", "diff", raster.diff)) if on is not None}
     for d in render_dirs.values():
         os.makedirs(d, exist_ok=True)
-    render_stream = torch.cuda.Stream(device) if raster is not None and device.type == "cuda" else None
+    render_stream = torch.cuda.Stream(device) if (raster is not None or support is not None) and device.type == "cuda" else None
+    geojson_dir = os.path.join(output_dir, "graph_geojson") if args.graph_geojson else None
+    if geojson_dir is not None:
+        os.makedirs(geojson_dir, exist_ok=True)
 
     def render_scene(img_id, img, valid, pred_nodes, pred_edges, shape, gt_path):
         import contextlib
@@ -2467,6 +2503,18 @@ def main(argv=None):
                 Image.fromarray(prod[k]).save(os.path.join(d, f"{img_id}.png"), compress_level=1)
         return img_id, prod.get("metrics")
 
+    # EDGE_SUPPORT: a scene's filter runs on a writer thread, on the render stream, IN FRONT of write_graph and render_scene,
+    # so the pickle, the renders, diff/metrics.json and the GeoJSON all show the filtered graph.  It is applied to a result: infer_imgs
+    # does not read the key.
+    def finish_scene(img_id, img, valid, res, gt_path):
+        import contextlib
+        with torch.cuda.stream(render_stream) if render_stream is not None else contextlib.nullcontext():
+            (pred_nodes, pred_edges, itsc_mask, _), attrs = apply_edge_support(support, res, valid=valid, net=net)
+        write_graph(img_id, pred_nodes, pred_edges)
+        if geojson_dir is not None:
+            write_geojson(os.path.join(geojson_dir, f"{img_id}.geojson"), pred_nodes, pred_edges, attrs, export_gt)
+        return render_scene(img_id, img, valid, pred_nodes, pred_edges, itsc_mask.shape, gt_path) if raster is not None else (img_id, None)
+
     # the reference times infer_one_img per image (inferencer.py:292-296); the scenes are software-pipelined here (infer_imgs), so
     # the time reported is what the loop spends waiting for results — its sum over the images is the wall time of inference.  PNG
     # encoding and pickling (tens of ms per 2048^2 scene) run on two writer threads so that the loop goes straight back to the GPU.
@@ -2475,17 +2523,21 @@ def main(argv=None):
                          pipelined=True if args.shard == "tiles-pipelined" else None, **(dict(valids=valids()) if masked else {}),
                          **(dict(aois=job_aois) if job_aois is not None else {}))
     rendered = []
-    with ThreadPoolExecutor(2 + len(render_dirs)) as writer:
+    with ThreadPoolExecutor(2 + len(render_dirs) + int(post)) as writer:
         pending = []
         for (img_id, path), gt_path in zip(jobs, job_gts):
             print(f"Processing {img_id}")
             start_seconds = time.time()
             res = next(results)
             total_inference_seconds += time.time() - start_seconds
-            scene_img, scene_valid = render_inputs.popleft() if raster is not None else (None, None)
+            scene_img, scene_valid = render_inputs.popleft() if raster is not None or post else (None, None)
             if res is None:                      # non-zero rank of a tile-sharded run
                 continue
             pred_nodes, pred_edges, itsc_mask, road_mask = res
+            if post:                             # the graph's files follow the filter; the masks are what they were
+                rendered.append(writer.submit(finish_scene, img_id, scene_img, scene_valid, res, gt_path))
+                pending += [writer.submit(write_png, road_mask, f"{img_id}_road.png"), writer.submit(write_png, itsc_mask, f"{img_id}_itsc.png")]
+                continue
             if raster is not None:               # rank 0 of a tile-sharded run, or this rank's own scene
                 rendered.append(writer.submit(render_scene, img_id, scene_img, scene_valid, pred_nodes, pred_edges, itsc_mask.shape, gt_path))
             pending += [writer.submit(write_png, road_mask, f"{img_id}_road.png"), writer.submit(write_png, itsc_mask, f"{img_id}_itsc.png"),

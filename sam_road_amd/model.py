@@ -272,6 +272,48 @@ class GraphRasterOps:
                                                 None if out is None else out.data_ptr(), SAMRoad._stream(dev)), "srh_graph_compare")
         return counts, out
 
+    @torch.no_grad()
+    def graph_edge_stats(self, nodes, edges, mask, width=1, on_level=127, valid=None):
+        """The mask under every edge (srh_graph_edge_stats; EDGE_SUPPORT, DESIGN.md §6p, the rule in sam_road_amd/edge_support.py): nodes
+        int [N, 2] (row, col) and edges int [E, 2] on the HOST, checked by graph_raster.check_graph; mask uint8 [H, W] and valid uint8 /
+        bool [H, W] or None, numpy arrays or tensors on the device -> a NEW int32 [E, 4] tensor on the device, rows {n, s, n_on,
+        n_invalid} over the pixels GRAPH_RASTER's rule covers for the edge at `width`.  One launch (none for E = 0), no workspace of the
+        library context, nothing read back."""
+        import numpy as np
+        from . import edge_support as _es
+        from . import graph_raster as _gr
+        ctx, dev = self._graph_ctx()
+        t, level = _es.check_width(width), _es.check_on_level(on_level)
+        n, e = _gr.check_graph(nodes, edges)
+        if not torch.is_tensor(mask):
+            mask = np.asarray(mask)
+            if mask.dtype != np.uint8 or mask.ndim != 2:
+                raise ValueError(f"mask must be uint8 [H, W], got {mask.dtype} {mask.shape}")
+            mask = torch.from_numpy(np.ascontiguousarray(mask)).to(dev)
+        if mask.dim() != 2 or mask.dtype != torch.uint8:
+            raise ValueError(f"mask must be uint8 [H, W], got {mask.dtype} {tuple(mask.shape)}")
+        H, W = mask.shape
+        if H < 1 or W < 1 or H * W > 2 ** 31 - 1:
+            raise ValueError(f"the image must have at least 1 x 1 and at most 2^31 - 1 pixels, got {H} x {W}")
+        mask = self._graph_u8("mask", mask, (H, W), dev)
+        if valid is not None and not torch.is_tensor(valid):
+            valid = np.asarray(valid)
+            if valid.dtype not in (np.uint8, np.bool_) or valid.shape != (H, W):
+                raise ValueError(f"valid must be uint8 / bool [{H}, {W}], got {valid.dtype} {valid.shape}")
+            valid = torch.from_numpy(np.ascontiguousarray(valid)).to(dev)
+        valid = self._graph_u8("valid", valid, (H, W), dev, optional=True)
+        N, E = int(n.shape[0]), int(e.shape[0])
+        out = torch.empty((E, 4), dtype=torch.int32, device=dev)
+        if E == 0:
+            return out
+        n_h, e_h = torch.from_numpy(n), torch.from_numpy(e)
+        n_d, e_d = n_h.to(dev), e_h.to(dev)
+        with torch.cuda.device(dev):
+            ctx.check(ctx.lib.srh_graph_edge_stats(ctx.handle, n_h.data_ptr(), n_d.data_ptr(), N, e_h.data_ptr(), e_d.data_ptr(), E, H, W, t,
+                                                   mask.data_ptr(), None if valid is None else valid.data_ptr(), level, out.data_ptr(),
+                                                   SAMRoad._stream(dev)), "srh_graph_edge_stats")
+        return out                                # the device tables were made on this stream and are read on it
+
 
 class DeviceGraphOps(GraphRasterOps):
     """GraphRasterOps without a model: the entries need a device, not weights."""
