@@ -85,6 +85,17 @@ const char* srh_last_error(const srh_ctx* ctx);
  * the first stage that saw it ("encoder block 7, norm2 ..."); reporting clears it.  synchronize != 0: wait for `stream` first (the
  * answer then covers every call issued so far); 0: only what has already completed. */
 int srh_ctx_check(srh_ctx* ctx, void* stream, int synchronize);
+/* Lanes (two entries added to ABI 11; the version number is unchanged because nothing that existed changed).  srh_encode_decode and the
+ * srh_scene_pass1* calls can run the encoder of a batch as TWO half-batch chains of the same kernels — tiles [0, B/2) on the caller's
+ * stream, tiles [B/2, B) on one stream the context owns — joined before the neck; tiles never interact in the encoder, so the outputs
+ * are those of one chain bit for bit, and the caller still sees one stream (outputs ordered on it, the input free to be overwritten on
+ * it right after the call; no additional device memory).  mode 0 = auto (the default): two lanes when B is even, profiling is off and a
+ * HALF batch still runs the patch embed and every block GEMM on the persistent 256 x 192 kernel with enough tiles (ViT-B, B/2 *
+ * (patch_size/16)^2 >= 8192: B >= 16 at 512 px, B >= 4 at 1024 px); 1 = always one lane; 2 = two lanes whenever B is even and profiling
+ * is off (for tests at small shapes; no promise about speed).  While srh_profile_enable is on every call runs one lane.
+ * srh_ctx_last_lanes: how many lanes the last such call ran (1 before any). */
+int srh_ctx_set_lanes(srh_ctx* ctx, int mode);
+int srh_ctx_last_lanes(const srh_ctx* ctx);
 
 /* Packs `net.load_state_dict(ckpt["state_dict"])` + `net.to(device)` (inferencer.py:250-254):
  * fp16 MFMA operand copies of every matmul weight (conv kernels re-ordered to the GEMM K order),

@@ -119,6 +119,8 @@ SYMBOLS = {
     "srh_pass2_pack_ragged": (_I, [_P, _P, _P, C.c_int32, C.c_int32, _P, _P, _P, _P]),
     "srh_toponet_ragged": (_I, [_P, _P, _P, _I, _P, _P, _P, _P, C.c_int64, _I, _P, _P, _P]),
     "srh_ctx_check": (_I, [_P, _P, _I]),
+    "srh_ctx_set_lanes": (_I, [_P, _I]),
+    "srh_ctx_last_lanes": (_I, [_P]),
     "srh_kdtree_knn_host": (_I, [_P, C.c_int64, C.c_int32, _P, C.c_int64, C.c_int32, C.c_double, _P, _P]),
     "srh_mask_candidates": (_I, [_P, C.c_int32, C.c_int32, C.c_float, _P, _P, C.c_int64, _P, C.c_int32]),
     "srh_nms_merge_points": (_I, [_P, _P, C.c_int64, _P, _P, C.c_int64, _P, C.c_int32, _P, _P]),
@@ -159,7 +161,9 @@ def load():
 class Context:
     """One per (process, device).  A context is SINGLE-STREAM: its workspaces (activations, split-K partials, TopoNet
     scratch) are shared by every call, so calls on the same context must be issued on one HIP stream at a time (the
-    reference is single-threaded on the default stream too, inferencer.py:93,200); use one process per GPU for more."""
+    reference is single-threaded on the default stream too, inferencer.py:93,200); use one process per GPU for more.
+    Inside a call the library may run the two halves of a batch on the caller's stream and on one stream of its own (set_lanes);
+    it forks and joins them itself, so the caller still sees one stream."""
     _by_device = {}
 
     def __init__(self, device_index):
@@ -184,6 +188,13 @@ class Context:
         if rc != 0:
             msg = self.lib.srh_last_error(self.handle)
             raise SrhError(f"{what} failed (status {rc}): {msg.decode() if msg else ''}")
+
+    def set_lanes(self, mode):
+        """srh_ctx_set_lanes: 0 auto, 1 one lane, 2 two half-batch lanes whenever the batch is even (include/samroad_hip.h)."""
+        self.check(self.lib.srh_ctx_set_lanes(self.handle, int(mode)), "srh_ctx_set_lanes")
+
+    def last_lanes(self):
+        return int(self.lib.srh_ctx_last_lanes(self.handle))
 
     def profile_enable(self, on=True):
         self.check(self.lib.srh_profile_enable(self.handle, 1 if on else 0), "srh_profile_enable")

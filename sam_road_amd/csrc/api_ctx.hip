@@ -56,6 +56,9 @@ extern "C" int srh_ctx_create(int device, srh_ctx** out) {
 extern "C" void srh_ctx_destroy(srh_ctx* c) {
     if (!c) return;
     hipSetDevice(c->device);
+    if (c->lane_stream) hipStreamDestroy(c->lane_stream);   // every call joined it to its caller's stream; what is queued still completes
+    if (c->lane_fork) hipEventDestroy(c->lane_fork);
+    if (c->lane_join) hipEventDestroy(c->lane_join);
     for (DevBuf* b : c->bufs) b->release();
     c->ztab.release();
     if (c->nf_host) hipHostFree(c->nf_host);
@@ -69,6 +72,14 @@ extern "C" size_t srh_ctx_device_bytes(const srh_ctx* c) {
     for (const DevBuf* b : c->bufs) n += b->cap;
     return n;
 }
+
+extern "C" int srh_ctx_set_lanes(srh_ctx* c, int mode) {
+    if (!c) return SRH_ERR_BAD_ARG;
+    if (mode < 0 || mode > 2) return fail(c, SRH_ERR_BAD_ARG, "srh_ctx_set_lanes: mode must be 0 (auto), 1 (one lane) or 2 (two lanes whenever B is even)");
+    c->lanes_mode = mode;
+    return 0;
+}
+extern "C" int srh_ctx_last_lanes(const srh_ctx* c) { return c ? c->last_lanes : 0; }
 
 extern "C" const char* srh_last_error(const srh_ctx* c) { return c ? c->err.c_str() : "null ctx"; }
 

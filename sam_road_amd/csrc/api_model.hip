@@ -127,16 +127,61 @@ int sam_decode(srh_ctx* c, const srh_weights* w, int B, const float* emb, float*
     return 0;
 }
 
-int encode_batch(srh_ctx* c, const srh_weights* w, PatchParams pp, int B, float* logits, float* scores, float* emb, hipStream_t s, int orient,
-                 int scene_H) {
-    const int S = w->S, D = w->D, heads = w->heads, hd = w->hd;
-    const int T = B * S * S;
-    TRY(ensure_encoder_ws(c, w, B));
-    pp.B = B; pp.P = w->cfg.patch_size; pp.out = c->a0.as<f16>();
+// One lane of encode_batch's encoder: tiles [b0, b0 + B) of the batch as a chain of its own on stream s, from the patch im2col to the cast
+// in front of the neck.  A lane is a view of the context's workspaces — every pointer starts at the lane's first token row, nothing is
+// allocated per lane — with its own pending-branch state.  encode_batch runs ONE lane (the whole batch on the caller's stream: the launch
+// sequence as it always was) or TWO half-batch lanes issued alternately, kernel by kernel (tiles never interact in the encoder).
+struct EncLane {
+    srh_ctx* c; const srh_weights* w; hipStream_t s;
+    int idx, lanes;                                       // this lane / how many are in flight (the split-K workspace is shared out by it)
+    int b0, B, T;                                         // first tile, tiles, token rows
+    f16 *a0, *xn16, *delta16, *delta16b, *qkv16, *attn16, *hid16;
+    float* x;
+    bool pend_a = false, pend_b = false;                  // delta16 (patch embed / proj) / delta16b (fc2) hold a branch output not yet added to x
+    bool x_is_pos = false;                                // x has not been written yet: its value is pos_embed (block 0's first pass)
+    int pend_slices = 0; const float* pend_bias = nullptr; // split-K partials of the last branch GEMM wait in the lane's part of c->split_ws
+    bool defer_x = false;                                 // both branch GEMMs of the blocks take z192 (same shapes in every block)
+
+    EncLane(srh_ctx* c_, const srh_weights* w_, hipStream_t s_, int idx_, int lanes_, int b0_, int B_)
+        : c(c_), w(w_), s(s_), idx(idx_), lanes(lanes_), b0(b0_), B(B_), T(B_ * w_->S * w_->S) {
+        const size_t r0 = (size_t)b0 * w->S * w->S, D = w->D;       // blocked-16 hid16: 32-row blocks, so a row offset is the same bytes
+        a0 = c->a0.as<f16>() + r0 * 768;       x = c->x.as<float>() + r0 * D;            xn16 = c->xn16.as<f16>() + r0 * D;
+        delta16 = c->delta16.as<f16>() + r0 * D; delta16b = c->delta16b.as<f16>() + r0 * D; qkv16 = c->qkv16.as<f16>() + r0 * 3 * D;
+        attn16 = c->attn16.as<f16>() + r0 * D;  hid16 = c->hid16.as<f16>() + r0 * 4 * D;
+        GemmParams gq = gemm_nt(attn16, w->blocks.empty() ? nullptr : w->blocks[0].proj_w, T, (int)D, (int)D);
+        gq.ldc16 = (int)D; gq.out_f16 = delta16; gq.bias = w->blocks.empty() ? nullptr : w->blocks[0].proj_b;
+        GemmParams g2 = gq;
+        g2.K = 4 * (int)D; g2.lda = 4 * (int)D; g2.ldw = 4 * (int)D;
+        defer_x = !w->blocks.empty() && z192_preferred(gq) && z192_preferred(g2);
+    }
+    int im2col(PatchParams pp, int orient, int scene_H);
+    int patch_embed();
+    int branch_gemm(const char* cls, const f16* A, int lda, const f16* W, int K, const float* bias, bool second, int a_blocked = 0);
+    int fold_pending(NormParams& ln, int& reads);
+    int block_ln(const float* gamma, const float* beta, bool write_x, int nf_tag);
+    int qkv(const BlockW& b);
+    int attention(const BlockW& b);
+    int hid_blocked = 0;                                  // fc1 -> fc2: the hidden activation is in the blocked-16 layout
+    int fc1(const BlockW& b);
+    int fc2(const BlockW& b);
+    int neck_cast();
+    int n_stages() const;
+    int stage(int k, const PatchParams& pp, int orient, int scene_H);
+};
+
+int EncLane::im2col(PatchParams pp, int orient, int scene_H) {
+    pp.B = B; pp.P = w->cfg.patch_size; pp.out = a0;
+    if (pp.scene_W > 0) pp.tile_xy += 2 * b0;            // tiles cropped out of a resident scene
+    else pp.src = (const char*)pp.src + (size_t)b0 * pp.P * pp.P * 3 * (pp.src_is_u8 ? 1 : 4);
     if (orient)          // TTA (scene_tta.hip): the crop is read through the orientation; everything after it is the same calls
         TRYK(c, "patch_im2col_oriented", 0, (double)T * 768 * 3, s, launch_patch_im2col_oriented(pp, scene_H, orient, s));
     else
     TRYK(c, "patch_im2col", 0, (double)T * 768 * (pp.src_is_u8 ? 3 : 6), s, launch_patch_im2col(pp, s));
+    return 0;
+}
+
+int EncLane::patch_embed() {
+    const int S = w->S, D = w->D;
     // Residual stream: x stays fp32.  Where the persistent z192 GEMM applies (gemm_z192.hip: fp16 output only), proj / fc2
     // write their branch output (bias included) as fp16 into delta16 and the NEXT LayerNorm pass folds "x += delta" into
     // its read of x — the same HBM bytes as the GEMM-epilogue residual add, but moved out of the GEMM's exposed epilogue
@@ -151,106 +196,205 @@ int encode_batch(srh_ctx* c, const srh_weights* w, PatchParams pp, int B, float*
     // Patch embedding: where z192 applies (ViT-B widths, enough tiles) it is just another fp16 branch output — conv + bias into delta16 —
     // and block 0's first LayerNorm pass computes the initial residual x = pos_embed[token] + delta16 (a row-modulo read of the
     // [S*S, D] table, NormParams::x_period) and writes x: the proj-shaped GEMM takes 22 instead of 51 us on the f32 + pos epilogue.
-    bool pend_a = false, pend_b = false;                  // delta16 (patch embed / proj) / delta16b (fc2) hold a branch output not yet added to x
-    bool x_is_pos = false;                                // x has not been written yet: its value is pos_embed (block 0's first pass)
-    {
-        GemmParams g = gemm_nt(c->a0.as<f16>(), w->patch_w, T, D, 768);
-        g.bias = w->patch_b;
-        GemmParams gz = g;
-        gz.out_f16 = c->delta16.as<f16>(); gz.ldc16 = D;
-        if (!w->blocks.empty() && z192_preferred(gz)) {
-            TRY(gemm(c, "gemm_patch_embed", gz, s));
-            pend_a = true; x_is_pos = true;
-        } else {
-            g.pos = w->pos; g.pos_rows = S * S; g.out_f32 = c->x.as<float>(); g.ldc = D;
-            TRY(gemm(c, "gemm_patch_embed", g, s));
-        }
+    GemmParams g = gemm_nt(a0, w->patch_w, T, D, 768);
+    g.bias = w->patch_b;
+    GemmParams gz = g;
+    gz.out_f16 = delta16; gz.ldc16 = D;
+    if (!w->blocks.empty() && z192_preferred(gz)) {
+        TRY(gemm(c, "gemm_patch_embed", gz, s, idx, lanes));
+        pend_a = true; x_is_pos = true;
+    } else {
+        g.pos = w->pos; g.pos_rows = S * S; g.out_f32 = x; g.ldc = D;
+        TRY(gemm(c, "gemm_patch_embed", g, s, idx, lanes));
     }
-    int pend_slices = 0; const float* pend_bias = nullptr; // split-K partials of the last branch GEMM wait in c->split_ws
-    auto branch_gemm = [&](const char* cls, const f16* A, int lda, const f16* W, int K, const float* bias, bool second, int a_blocked = 0) -> int {
+    return 0;
+}
+
+int EncLane::branch_gemm(const char* cls, const f16* A, int lda, const f16* W, int K, const float* bias, bool second, int a_blocked) {
+    const int D = w->D;
+    {
         GemmParams gq = gemm_nt(A, W, T, D, K);
         gq.lda = lda; gq.bias = bias; gq.a_blocked16 = a_blocked;
-        gq.out_f16 = second ? c->delta16b.as<f16>() : c->delta16.as<f16>(); gq.ldc16 = D;
-        if (z192_preferred(gq)) { (second ? pend_b : pend_a) = true; return gemm(c, cls, gq, s); }
+        gq.out_f16 = second ? delta16b : delta16; gq.ldc16 = D;
+        if (z192_preferred(gq)) { (second ? pend_b : pend_a) = true; return gemm(c, cls, gq, s, idx, lanes); }
         // Small-M models (ViT-L / ViT-H at 256 px), the attention branch: proj runs unsplit on 128 x 128 ring tiles with ~9 us of fixed cost
         // on a ~9 us loop, and its f32 read-modify-write of x sat in that exposed epilogue.  Its output goes out as fp16 instead (half the
         // store instructions) and the LayerNorm pass that follows anyway folds it into x — the same bytes, moved into the streaming kernel
         // (what the z192 path does for ViT-B).
-        if (!second && !pend_a && !pend_slices && (D == 1024 || D == 1280) && gemm_splitk_factor(gq) <= 1) { pend_a = true; return gemm(c, cls, gq, s); }
+        if (!second && !pend_a && !pend_slices && (D == 1024 || D == 1280) && gemm_splitk_factor(gq) <= 1) { pend_a = true; return gemm(c, cls, gq, s, idx, lanes); }
         GemmParams gp = gq;
-        gp.out_f16 = nullptr; gp.resid = c->x.as<float>(); gp.ldr = D; gp.out_f32 = c->x.as<float>(); gp.ldc = D;
+        gp.out_f16 = nullptr; gp.resid = x; gp.ldr = D; gp.out_f32 = x; gp.ldc = D;
         if (const int sk = gemm_splitk_factor(gp); sk > 1 && bias && (D == 1024 || D == 1280) && !pend_slices && !pend_a && !pend_b) {
             gp.defer_reduce = 1;
             pend_slices = sk; pend_bias = bias;
         }
-        return gemm(c, cls, gp, s);
-    };
-    auto fold_pending = [&](NormParams& ln, int& reads) -> int {  // what the pass has to add to x before normalising / casting
-        if (pend_slices && (pend_a || pend_b))            // never both: the fp16 branch would be dropped (branch_gemm defers only when neither is pending)
-            return fail(c, SRH_ERR_HIP, "internal: split-K partials and an fp16 branch output pending at the same LayerNorm pass");
-        if (pend_slices) {
-            ln.slices = c->split_ws.as<float>(); ln.nslices = pend_slices; ln.slice_stride = (size_t)T * D; ln.slice_bias = pend_bias;
-            reads = 2 * pend_slices;                      // in units of 2 bytes per element, as the fp16 branches
-        } else if (pend_a && pend_b) { ln.delta16 = c->delta16.as<f16>(); ln.delta16b = c->delta16b.as<f16>(); reads = 2; }
-        else if (pend_a) { ln.delta16 = c->delta16.as<f16>(); reads = 1; }
-        else if (pend_b) { ln.delta16 = c->delta16b.as<f16>(); reads = 1; }
-        return 0;
-    };
-    bool defer_x = false;                                 // both branch GEMMs of the blocks take z192 (same shapes in every block)
-    {
-        GemmParams gq = gemm_nt(c->attn16.as<f16>(), w->blocks.empty() ? nullptr : w->blocks[0].proj_w, T, D, D);
-        gq.ldc16 = D; gq.out_f16 = c->delta16.as<f16>(); gq.bias = w->blocks.empty() ? nullptr : w->blocks[0].proj_b;
-        GemmParams g2 = gq;
-        g2.K = 4 * D; g2.lda = 4 * D; g2.ldw = 4 * D;
-        defer_x = !w->blocks.empty() && z192_preferred(gq) && z192_preferred(g2);
+        return gemm(c, cls, gp, s, idx, lanes);
     }
-    // a LayerNorm pass over x (+ pending branches).  write_x: fold the pending branches into x for good.
-    auto block_ln = [&](const float* gamma, const float* beta, bool write_x, int nf_tag) -> int {
-        NormParams ln;
-        ln.x = c->x.as<float>(); ln.M = T; ln.D = D; ln.eps = 1e-6f; ln.out_f16 = c->xn16.as<f16>();
-        ln.gamma = gamma; ln.beta = beta; ln.nf = c->nf_dev; ln.nf_tag = std::min(nf_tag, NF_NECK - 1);
-        if (x_is_pos) { ln.x = w->pos; ln.x_period = S * S; }
-        int reads = 0;
-        TRY(fold_pending(ln, reads));
-        const bool wr = (write_x || pend_slices || x_is_pos) && reads > 0;   // partials cannot wait: the next split-K GEMM overwrites the workspace
-        ln.x_out = wr ? c->x.as<float>() : nullptr;
-        TRYK(c, "layernorm", 0, (double)T * D * (4 + 2 + 2 * reads + (wr ? 4 : 0)), s, launch_layernorm(ln, s));
-        if (wr) { pend_a = pend_b = false; pend_slices = 0; x_is_pos = false; }
-        return 0;
+}
+
+int EncLane::fold_pending(NormParams& ln, int& reads) {   // what the pass has to add to x before normalising / casting
+    const int D = w->D;
+    if (pend_slices && (pend_a || pend_b))            // never both: the fp16 branch would be dropped (branch_gemm defers only when neither is pending)
+        return fail(c, SRH_ERR_HIP, "internal: split-K partials and an fp16 branch output pending at the same LayerNorm pass");
+    if (pend_slices) {                                // the lane's part of the workspace, as gemm() (ctx.hpp) shared it out
+        ln.slices = c->split_ws.as<float>() + (size_t)pend_slices * T * D * idx;
+        ln.nslices = pend_slices; ln.slice_stride = (size_t)T * D; ln.slice_bias = pend_bias;
+        reads = 2 * pend_slices;                      // in units of 2 bytes per element, as the fp16 branches
+    } else if (pend_a && pend_b) { ln.delta16 = delta16; ln.delta16b = delta16b; reads = 2; }
+    else if (pend_a) { ln.delta16 = delta16; reads = 1; }
+    else if (pend_b) { ln.delta16 = delta16b; reads = 1; }
+    return 0;
+}
+
+// a LayerNorm pass over x (+ pending branches).  write_x: fold the pending branches into x for good.
+int EncLane::block_ln(const float* gamma, const float* beta, bool write_x, int nf_tag) {
+    const int S = w->S, D = w->D;
+    NormParams ln;
+    ln.x = x; ln.M = T; ln.D = D; ln.eps = 1e-6f; ln.out_f16 = xn16;
+    ln.gamma = gamma; ln.beta = beta; ln.nf = c->nf_dev; ln.nf_tag = std::min(nf_tag, NF_NECK - 1);
+    if (x_is_pos) { ln.x = w->pos; ln.x_period = S * S; }
+    int reads = 0;
+    TRY(fold_pending(ln, reads));
+    const bool wr = (write_x || pend_slices || x_is_pos) && reads > 0;   // partials cannot wait: the next split-K GEMM overwrites the workspace
+    ln.x_out = wr ? x : nullptr;
+    TRYK(c, "layernorm", 0, (double)T * D * (4 + 2 + 2 * reads + (wr ? 4 : 0)), s, launch_layernorm(ln, s));
+    if (wr) { pend_a = pend_b = false; pend_slices = 0; x_is_pos = false; }
+    return 0;
+}
+
+int EncLane::qkv(const BlockW& b) {
+    const int D = w->D;
+    GemmParams g = gemm_nt(xn16, b.qkv_w, T, 3 * D, D);
+    g.bias = b.qkv_b; g.out_f16 = qkv16; g.ldc16 = 3 * D;
+    return gemm(c, "gemm_qkv", g, s, idx, lanes);
+}
+
+int EncLane::attention(const BlockW& b) {
+    const int S = w->S, heads = w->heads, hd = w->hd;
+    const AttnParams ap = attn_params(qkv16, b.rel_h, b.rel_w, b.qkv_b16, attn16, B, S, heads, hd, b.win);
+    TRYK(c, b.win == S ? "attn_global" : "attn_window", attn_flops(B, S, heads, hd, b.win), 0, s, launch_attention(ap, s));
+    return 0;
+}
+
+int EncLane::fc1(const BlockW& b) {
+    const int D = w->D;
+    GemmParams g1 = gemm_nt(xn16, b.fc1_w, T, 4 * D, D);
+    g1.bias = b.fc1_b; g1.act = 1; g1.out_f16 = hid16; g1.ldc16 = 4 * D;
+    // the hidden activation lives only between these two launches: when both take gemm_z192 it is kept in the blocked-16 layout
+    // (fc1 stores 1 KiB contiguous per instruction, no LDS transposition; fc2's LDS-DMA reads it through per-lane addresses)
+    {
+        GemmParams t1 = g1, t2 = gemm_nt(hid16, b.fc2_w, T, D, 4 * D);
+        t1.out_blocked16 = 1; t2.bias = b.fc2_b;
+        t2.out_f16 = delta16b; t2.ldc16 = D; t2.a_blocked16 = 1;
+        hid_blocked = z192_preferred(t1) && z192_preferred(t2);
+    }
+    g1.out_blocked16 = hid_blocked;
+    return gemm(c, "gemm_fc1", g1, s, idx, lanes);
+}
+
+int EncLane::fc2(const BlockW& b) {
+    const int D = w->D;
+    return branch_gemm("gemm_fc2", hid16, 4 * D, b.fc2_w, 4 * D, b.fc2_b, true, hid_blocked);
+}
+
+int EncLane::neck_cast() {           // x (+ the last block's branch outputs, if still pending) as fp16 for the neck's 1x1 conv
+    const int D = w->D;
+    NormParams cast;
+    cast.x = x; cast.M = T; cast.D = D; cast.out_f16 = xn16;
+    int reads = 0;
+    TRY(fold_pending(cast, reads));
+    TRYK(c, "layernorm", 0, (double)T * D * (6 + 2 * reads), s, launch_layernorm(cast, s));
+    return 0;
+}
+
+// Auto's shape rule: two lanes only where a HALF batch still runs the patch embed and every block GEMM on gemm_z192 with enough tiles to
+// occupy the chip (ViT-B with B/2 * S * S >= 8192) — then no lane touches split-K partials, and every kernel of a lane is the kernel the
+// whole batch would run, on half the rows.
+static bool lanes_pay(srh_ctx* c, const srh_weights* w, int B) {
+    if (B < 2 || B % 2 || w->blocks.empty()) return false;
+    const int D = w->D, T = B / 2 * w->S * w->S;
+    const BlockW& b = w->blocks[0];
+    f16* o = c->delta16.as<f16>();                        // any non-null output: only the shapes are looked at
+    auto z = [&](const f16* W, const float* bias, int N, int K, int act) {
+        GemmParams g = gemm_nt(o, W, T, N, K);
+        g.bias = bias; g.act = act; g.out_f16 = o; g.ldc16 = N;
+        return z192_preferred(g);
     };
-    int blk = -1;
-    for (const BlockW& b : w->blocks) {
-        ++blk;
-        TRY(block_ln(b.ln1_g, b.ln1_b, true, 2 * blk));
-        GemmParams g = gemm_nt(c->xn16.as<f16>(), b.qkv_w, T, 3 * D, D);
-        g.bias = b.qkv_b; g.out_f16 = c->qkv16.as<f16>(); g.ldc16 = 3 * D;
-        TRY(gemm(c, "gemm_qkv", g, s));
-        const AttnParams ap = attn_params(c->qkv16.as<f16>(), b.rel_h, b.rel_w, b.qkv_b16, c->attn16.as<f16>(), B, S, heads, hd, b.win);
-        TRYK(c, b.win == S ? "attn_global" : "attn_window", attn_flops(B, S, heads, hd, b.win), 0, s, launch_attention(ap, s));
-        TRY(branch_gemm("gemm_proj", c->attn16.as<f16>(), D, b.proj_w, D, b.proj_b, false));
-        TRY(block_ln(b.ln2_g, b.ln2_b, !defer_x, 2 * blk + 1));
-        GemmParams g1 = gemm_nt(c->xn16.as<f16>(), b.fc1_w, T, 4 * D, D);
-        g1.bias = b.fc1_b; g1.act = 1; g1.out_f16 = c->hid16.as<f16>(); g1.ldc16 = 4 * D;
-        // the hidden activation lives only between these two launches: when both take gemm_z192 it is kept in the blocked-16 layout
-        // (fc1 stores 1 KiB contiguous per instruction, no LDS transposition; fc2's LDS-DMA reads it through per-lane addresses)
-        int hid_blocked = 0;
-        {
-            GemmParams t1 = g1, t2 = gemm_nt(c->hid16.as<f16>(), b.fc2_w, T, D, 4 * D);
-            t1.out_blocked16 = 1; t2.bias = b.fc2_b;
-            t2.out_f16 = c->delta16b.as<f16>(); t2.ldc16 = D; t2.a_blocked16 = 1;
-            hid_blocked = z192_preferred(t1) && z192_preferred(t2);
+    return z(w->patch_w, w->patch_b, D, 768, 0) && z(b.qkv_w, b.qkv_b, 3 * D, D, 0) && z(b.proj_w, b.proj_b, D, D, 0) &&
+           z(b.fc1_w, b.fc1_b, 4 * D, D, 1) && z(b.fc2_w, b.fc2_b, D, 4 * D, 0);
+}
+
+// Lane 1's stream and the two events that tie it to the caller's stream; made at the first two-lane call of the context.
+static int ensure_lane_stream(srh_ctx* c) {
+    if (!c->lane_stream && hipStreamCreateWithFlags(&c->lane_stream, hipStreamNonBlocking) != hipSuccess) { c->lane_stream = nullptr; return fail(c, SRH_ERR_HIP, "lane stream creation failed"); }
+    if (!c->lane_fork && hipEventCreateWithFlags(&c->lane_fork, hipEventDisableTiming) != hipSuccess) { c->lane_fork = nullptr; return fail(c, SRH_ERR_HIP, "lane event creation failed"); }
+    if (!c->lane_join && hipEventCreateWithFlags(&c->lane_join, hipEventDisableTiming) != hipSuccess) { c->lane_join = nullptr; return fail(c, SRH_ERR_HIP, "lane event creation failed"); }
+    return 0;
+}
+
+// A lane's chain as numbered stages, one launch each: 0 patch im2col, 1 patch embed, then per block norm1, qkv, attention, proj, norm2,
+// fc1, fc2, and last the cast in front of the neck.
+int EncLane::n_stages() const { return 2 + 7 * (int)w->blocks.size() + 1; }
+int EncLane::stage(int k, const PatchParams& pp, int orient, int scene_H) {
+    if (k == 0) return im2col(pp, orient, scene_H);
+    if (k == 1) return patch_embed();
+    const int blk = (k - 2) / 7, D = w->D;
+    if (blk >= (int)w->blocks.size()) return neck_cast();
+    const BlockW& b = w->blocks[blk];
+    switch ((k - 2) % 7) {
+        case 0: return block_ln(b.ln1_g, b.ln1_b, true, 2 * blk);
+        case 1: return qkv(b);
+        case 2: return attention(b);
+        case 3: return branch_gemm("gemm_proj", attn16, D, b.proj_w, D, b.proj_b, false);
+        case 4: return block_ln(b.ln2_g, b.ln2_b, !defer_x, 2 * blk + 1);
+        case 5: return fc1(b);
+        default: return fc2(b);
+    }
+}
+
+// How far lane 0 runs ahead: lane 1 is forked behind lane 0's first SRH_LANE_LAG stages and is issued that many launches behind.  3 = behind
+// block 0's norm1, one stage out of step: whenever a lane is in a LayerNorm pass (HBM-bound, no LDS) the other one is in a GEMM (one
+// wave per SIMD, the LDS), and the two share the CUs.  Measured same-box against one lane at ViT-B 512 px B = 16: lag 0 (lockstep) +0.9 %,
+// 3 +2.1 %, 4 (behind qkv) +1.3 %, 5 +0.8 %, 6 / 7 +0.4 % tiles/s (profiles/lanes_ab_same_box.txt).
+#ifndef SRH_LANE_LAG
+#define SRH_LANE_LAG 3
+#endif
+
+int encode_batch(srh_ctx* c, const srh_weights* w, PatchParams pp, int B, float* logits, float* scores, float* emb, hipStream_t s, int orient,
+                 int scene_H) {
+    const int S = w->S, D = w->D;
+    const int T = B * S * S;
+    TRY(ensure_encoder_ws(c, w, B));
+    // Lanes: srh_ctx_set_lanes' mode; profiling is always one lane, so that the event pairs around a launch time that launch alone
+    int nl = 1;
+    if (!c->profiling && B % 2 == 0 && (c->lanes_mode == 2 || (c->lanes_mode == 0 && lanes_pay(c, w, B)))) nl = 2;
+    c->last_lanes = nl;
+    if (nl == 1) {
+        EncLane one(c, w, s, 0, 1, 0, B);
+        for (int k = 0, n = one.n_stages(); k < n; ++k) TRY(one.stage(k, pp, orient, scene_H));
+    } else {
+        // Two lanes, their launches issued alternately so that both queues stay fed.  Fork: lane 1 starts behind what is queued on the
+        // caller's stream (lane 0's first stages included).  Join: the caller's stream goes on behind lane 1 — on every return path
+        // after the fork, so that the caller sees one stream: outputs ordered on it, the input free to be overwritten on it after the call.
+        TRY(ensure_lane_stream(c));
+        EncLane lane[2] = {EncLane(c, w, s, 0, 2, 0, B / 2), EncLane(c, w, c->lane_stream, 1, 2, B / 2, B / 2)};
+        const int n = lane[0].n_stages(), lag = std::min(SRH_LANE_LAG, n);
+        for (int k = 0; k < lag; ++k) TRY(lane[0].stage(k, pp, orient, scene_H));
+        if (hipEventRecord(c->lane_fork, s) != hipSuccess || hipStreamWaitEvent(c->lane_stream, c->lane_fork, 0) != hipSuccess)
+            return fail(c, SRH_ERR_HIP, "lane fork failed");
+        int rc = 0;
+        for (int k = 0; k < n && !rc; ++k) {
+            rc = lane[1].stage(k, pp, orient, scene_H);
+            if (!rc && k + lag < n) rc = lane[0].stage(k + lag, pp, orient, scene_H);
         }
-        g1.out_blocked16 = hid_blocked;
-        TRY(gemm(c, "gemm_fc1", g1, s));
-        TRY(branch_gemm("gemm_fc2", c->hid16.as<f16>(), 4 * D, b.fc2_w, 4 * D, b.fc2_b, true, hid_blocked));
+        if (hipEventRecord(c->lane_join, c->lane_stream) != hipSuccess || hipStreamWaitEvent(s, c->lane_join, 0) != hipSuccess) {
+            hipStreamSynchronize(c->lane_stream);         // the join could not be queued: wait for lane 1 here instead
+            if (!rc) return fail(c, SRH_ERR_HIP, "lane join failed");
+        }
+        if (rc) return rc;
     }
-    // neck: 1x1 conv -> LN2d -> 3x3 conv -> LN2d  (channels-last: LN2d is a row LN)
+    // neck: 1x1 conv -> LN2d -> 3x3 conv -> LN2d  (channels-last: LN2d is a row LN), on the whole batch
     {
-        NormParams cast;
-        cast.x = c->x.as<float>(); cast.M = T; cast.D = D; cast.out_f16 = c->xn16.as<f16>();
-        int reads = 0;                                               // the last block's branch outputs, if still pending
-        TRY(fold_pending(cast, reads));
-        TRYK(c, "layernorm", 0, (double)T * D * (6 + 2 * reads), s, launch_layernorm(cast, s));
         GemmParams g = gemm_nt(c->xn16.as<f16>(), w->neck0_w, T, 256, D);
         g.out_f32 = c->n1.as<float>(); g.ldc = 256;
         TRY(gemm(c, "gemm_neck", g, s));

@@ -66,6 +66,11 @@ struct SRH_INTERNAL srh_ctx {
     std::vector<ProfEntry> prof;
     std::vector<hipEvent_t> ev_pool;
     size_t ev_used = 0;
+    // lanes (api_model.hip encode_batch): a batch as two half-batch chains, lane 0 on the caller's stream and lane 1 on this one
+    int lanes_mode = 0;          // srh_ctx_set_lanes: 0 auto, 1 one lane, 2 two lanes whenever B is even
+    int last_lanes = 1;          // what the last encode_batch ran
+    hipStream_t lane_stream = nullptr;                      // created at the first two-lane call, destroyed with the context
+    hipEvent_t lane_fork = nullptr, lane_join = nullptr;    // caller's stream -> lane 1 -> caller's stream
 };
 
 constexpr int NF_SLOTS = 128, NF_NECK = 64, NF_DECODER = 66;   // tags: 2 * block + (0 norm1 | 1 norm2), neck LN2d 64 / 65, map_decoder LN2d 66
@@ -99,13 +104,15 @@ static int run(srh_ctx* c, const char* cls, double flops, double bytes, hipStrea
     return rc;
 }
 
-static int gemm(srh_ctx* c, const char* cls, const GemmParams& p_in, hipStream_t s) {
+// lane / lanes: the caller is chain `lane` of `lanes` equal ones in flight at once (encode_batch); each has its own part of the split-K workspace
+static int gemm(srh_ctx* c, const char* cls, const GemmParams& p_in, hipStream_t s, int lane = 0, int lanes = 1) {
     GemmParams p = p_in;
     p.ztab = &c->ztab;
     const int sk = gemm_splitk_factor(p);
     if (sk > 1) {       // small-M layers (ViT-L / ViT-H at 256 px): deterministic split-K through a ctx-owned f32 workspace
-        if (c->split_ws.ensure((size_t)sk * p.M * p.N * 4)) return fail(c, SRH_ERR_HIP, "split-K workspace allocation failed");
-        p.splitk = sk; p.split_ws = c->split_ws.as<float>();
+        const size_t part = (size_t)sk * p.M * p.N;
+        if (c->split_ws.ensure(part * 4 * lanes)) return fail(c, SRH_ERR_HIP, "split-K workspace allocation failed");
+        p.splitk = sk; p.split_ws = c->split_ws.as<float>() + part * lane;
     }
     const double fl = 2.0 * p.M * (double)p.N * p.K;
     const int rc = run(c, cls, fl, 0.0, s, [&] { return launch_gemm(p, s); });

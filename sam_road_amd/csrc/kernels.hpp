@@ -45,8 +45,12 @@ struct ZTileTables {
     int* host = nullptr;                      // pinned image of the slab: the source of the asynchronous uploads (must outlive them)
     Key key[SLOTS];
     unsigned long long stamp[SLOTS] = {}, clock = 0;
-    hipStream_t used_on[SLOTS] = {};          // the stream a slot's table was uploaded on / last launched on
-    hipEvent_t ready[SLOTS] = {};             // recorded behind a slot's upload: launches from another stream wait for it
+    hipStream_t used_on[SLOTS] = {};          // the stream a slot's table was uploaded on
+    hipEvent_t ready[SLOTS] = {};             // recorded behind a slot's upload: the first launch from another stream waits for it
+    static constexpr int SEEN = 4;
+    hipStream_t seen[SLOTS][SEEN] = {};       // other streams that have waited for the upload already: a one-time dependency per stream
+    bool settled[SLOTS] = {};                 // the upload is known to be complete: no stream has to wait any more
+    bool shared[SLOTS] = {};                  // launched from more than the upload stream: replacing the slot drains the device
     int used = 0, n_cu = 0;
     const int* get(int M, int N, int lda, int ldw, int ldc, int blocked, hipStream_t stream, int* ntiles_out);
     void release();

@@ -639,6 +639,16 @@ class SAMRoad(nn.Module, GraphRasterOps):
                                                      scores.data_ptr(), self._stream(dev)), "srh_toponet_ragged")
         return scores
 
+    def set_lanes(self, mode, device=None):
+        """How this device's context runs the encoder of a batch (srh_ctx_set_lanes): 0 auto, 1 one lane, 2 two half-batch lanes on two
+        streams whenever the batch is even.  Same outputs bit for bit.  last_lanes() tells what the last call ran."""
+        dev = torch.device(device) if device is not None else next(self.parameters()).device
+        _lib.Context.get(dev.index if dev.index is not None else torch.cuda.current_device()).set_lanes(mode)
+
+    def last_lanes(self, device=None):
+        dev = torch.device(device) if device is not None else next(self.parameters()).device
+        return _lib.Context.get(dev.index if dev.index is not None else torch.cuda.current_device()).last_lanes()
+
     def check_finite(self, device=None, synchronize=True):
         """Raise SrhError if a LayerNorm pass of any earlier call on this device's context saw an Inf / NaN (an fp16 overflow in the
         encoder: srh_ctx_check, SRH_ERR_NONFINITE) — the masks / embeddings of that call are invalid.  synchronize=True waits for the
