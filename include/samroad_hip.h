@@ -499,7 +499,36 @@ int srh_graph_edge_stats(srh_ctx* ctx, const int32_t* nodes_host, const int32_t*
                          const int32_t* edges_dev, int E, int H, int W, int t, const uint8_t* mask, const uint8_t* valid, int on_level,
                          int32_t* out, void* stream);
 
-/* op level (used by the parity tests to localise a failure; same kernels as above) ----------------- */
+/* The road width under every edge of a graph (config key ROAD_WIDTH; an extension).  Two additive entries; the ABI number
+ * stays 11 because nothing existing changes, and a run without the key calls neither.  Nothing is read back.
+ *
+ * srh_road_dist: the capped squared Euclidean distance map of a thresholded mask.  mask u8 [H, W] on the device; F = {mask > on_level};
+ * d2_out u16 [H, W] on the device, 8-BYTE ALIGNED (pixel i of the flat image lies at d2_out + i; the row pass stores four pixels of the
+ * flat index as one 8-byte word):
+ *   d2_out[x] = 0 for x outside F, else min(R^2, min over the pixels y OF THE IMAGE outside F of |x - y|^2)
+ * — pixels outside the image are not background.  R is 1 .. SRH_ROAD_MAX_RADIUS, so R^2 fits 16 bits.  Exact integers: it equals
+ * road_dist_ref of sam_road_amd/road_width.py.  Two launches whatever the mask holds (a column pass into H W bytes of the context's
+ * workspace, a row pass out of it; the entry holds a lock of the context from the workspace's growth to the second launch, so it may
+ * be called from several threads), no atomics, no workgroup waits for another.  Every element of d2_out is defined after the call and
+ * nothing else is written.  SRH_ERR_BAD_ARG, and nothing is launched, for a null argument, H or W < 1 or H W > 2^31 - 1, on_level
+ * outside 0 .. 255, R outside 1 .. 254, a d2_out that is not 8-byte aligned or overlaps the mask.  Profiler rows: road_dist_cols,
+ * road_dist_rows.
+ *
+ * srh_graph_edge_widths: tables as srh_graph_edge_stats takes them; the covered set C_e of edge e is that entry's at t = 1, the
+ * 8-connected centre line.  d2 u16 [H, W] on the device (2-byte aligned), the map of srh_road_dist at the same R.  out int32 [E, 8] on
+ * the device, 16-byte aligned, per edge
+ *   {n = |C_e|, n_in = #(d2 > 0), s_q = sum of floor(16 sqrt(d2)), n_cap = #(d2 == R^2), d2_min over the pixels with d2 > 0 (0 when
+ *    n_in = 0), d2_max, 0, 0}
+ * — n <= 46343 and s_q <= 4064 n < 2^31 for every edge the tables admit.  An edge wholly outside the image gives eight zeros.  One
+ * launch, 16 lanes per edge, two 16-byte stores per edge, no atomics.  E = 0 is SRH_OK and launches nothing (d2 and out may then be
+ * NULL).  SRH_ERR_BAD_ARG, and nothing is launched, for every condition srh_graph_edge_stats refuses of its tables, H and W, R outside
+ * 1 .. 254, a null d2 or out with E > 0, a misaligned d2 or out, or an out overlapping an input.  Profiler row: graph_edge_widths. */
+#define SRH_ROAD_MAX_RADIUS 254
+int srh_road_dist(srh_ctx* ctx, const uint8_t* mask, int H, int W, int on_level, int R, uint16_t* d2_out, void* stream);
+int srh_graph_edge_widths(srh_ctx* ctx, const int32_t* nodes_host, const int32_t* nodes_dev, int N, const int32_t* edges_host,
+                          const int32_t* edges_dev, int E, int H, int W, const uint16_t* d2, int R, int32_t* out, void* stream);
+
+/* op level(used by the parity tests to localise a failure; same kernels as above) ----------------- */
 
 /* out = act(A[M,K] W[N,K]^T + bias) (+resid); A,W fp16; N%128==0, K%64==0. act: 0/1 GELU/2 ReLU. */
 int srh_op_gemm(srh_ctx* ctx, const void* A_f16, const void* W_f16, const float* bias, const float* resid,

@@ -92,6 +92,8 @@ SYMBOLS = {
     "srh_graph_composite": (_I, [_P, _P, _P, _I, _I, _P, _P, _P, _P, _P]),
     "srh_graph_compare": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P]),
     "srh_graph_edge_stats": (_I, [_P, _P, _P, _I, _P, _P, _I, _I, _I, _I, _P, _P, _I, _P, _P]),
+    "srh_road_dist": (_I, [_P, _P, _I, _I, _I, _I, _P, _P]),
+    "srh_graph_edge_widths": (_I, [_P, _P, _P, _I, _P, _P, _I, _I, _I, _P, _I, _P, _P]),
     "srh_op_patch_im2col": (_I, [_P, _P, _I, _I, _P, _I, _I, _I, _P, _P]),
     "srh_op_scores_unorient": (_I, [_P, _P, _I, _I, _I, _P, _P]),
     "srh_op_gemm": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P]),

@@ -546,3 +546,50 @@ extern "C" int srh_graph_edge_stats(srh_ctx* c, const int32_t* nodes_host, const
     TRYK(c, "graph_edge_stats", 0, 40.0 * E, s, launch_graph_edge_stats(p, s));
     return 0;
 }
+
+// ---- the road width under every edge (kernels in road_width.hip, behaviour in DESIGN.md §6q) ---------------------------------------------------
+extern "C" int srh_road_dist(srh_ctx* c, const uint8_t* mask, int H, int W, int on_level, int R, uint16_t* d2_out, void* stream) {
+    if (!c || !mask || !d2_out) return fail(c, SRH_ERR_BAD_ARG, "srh_road_dist: null argument");
+    if (H < 1 || W < 1 || (double)H * W > (double)GR_MAX_PIXELS) return fail(c, SRH_ERR_BAD_ARG, "srh_road_dist: H and W are at least 1 and H W at most 2^31 - 1");
+    if (on_level < 0 || on_level > 255) return fail(c, SRH_ERR_BAD_ARG, "srh_road_dist: on_level is 0 to 255");
+    if (R < 1 || R > RW_MAX_R) return fail(c, SRH_ERR_BAD_ARG, "srh_road_dist: the radius is 1 to 254");
+    if (reinterpret_cast<uintptr_t>(d2_out) & 7) return fail(c, SRH_ERR_BAD_ARG, "srh_road_dist: d2_out is 8-byte aligned");
+    const double px = (double)H * W;
+    if (ranges_overlap(d2_out, 2 * px, mask, px)) return fail(c, SRH_ERR_BAD_ARG, "srh_road_dist: d2_out overlaps the mask");
+    hipSetDevice(c->device);
+    hipStream_t s = (hipStream_t)stream;
+    std::lock_guard<std::mutex> lock(c->road_mu);
+    if (c->road_g.ensure((size_t)H * W)) return fail(c, SRH_ERR_HIP, "road distance workspace allocation failed");
+    if (ranges_overlap(d2_out, 2 * px, c->road_g.p, px)) return fail(c, SRH_ERR_BAD_ARG, "srh_road_dist: d2_out overlaps the workspace");
+    RoadDistParams p;
+    p.mask = mask; p.g = c->road_g.as<uint8_t>(); p.d2 = d2_out; p.H = H; p.W = W; p.on_level = on_level; p.R = R;
+    const double rows = (double)(RW_COL_ROWS + 2 * R) / RW_COL_ROWS;       // the rows a chunk reads for each row it writes
+    TRYK(c, "road_dist_cols", 0, px * (rows + 1), s, launch_road_dist(p, 0, s));
+    TRYK(c, "road_dist_rows", 0, px * 3, s, launch_road_dist(p, 1, s));
+    return 0;
+}
+
+extern "C" int srh_graph_edge_widths(srh_ctx* c, const int32_t* nodes_host, const int32_t* nodes_dev, int N, const int32_t* edges_host,
+                                     const int32_t* edges_dev, int E, int H, int W, const uint16_t* d2, int R, int32_t* out, void* stream) {
+    if (!c || N < 0 || E < 0 || (N > 0 && (!nodes_host || !nodes_dev)) || (E > 0 && (!edges_host || !edges_dev || !d2 || !out)))
+        return fail(c, SRH_ERR_BAD_ARG, "srh_graph_edge_widths: null argument or a negative count");
+    if (H < 1 || W < 1 || (double)H * W > (double)GR_MAX_PIXELS) return fail(c, SRH_ERR_BAD_ARG, "srh_graph_edge_widths: H and W are at least 1 and H W at most 2^31 - 1");
+    if (R < 1 || R > RW_MAX_R) return fail(c, SRH_ERR_BAD_ARG, "srh_graph_edge_widths: the radius is 1 to 254");
+    if ((reinterpret_cast<uintptr_t>(nodes_dev) | reinterpret_cast<uintptr_t>(edges_dev)) & 3) return fail(c, SRH_ERR_BAD_ARG, "srh_graph_edge_widths: the device tables are 4-byte aligned");
+    if (reinterpret_cast<uintptr_t>(d2) & 1) return fail(c, SRH_ERR_BAD_ARG, "srh_graph_edge_widths: d2 is 2-byte aligned");
+    if (reinterpret_cast<uintptr_t>(out) & 15) return fail(c, SRH_ERR_BAD_ARG, "srh_graph_edge_widths: out is 16-byte aligned");
+    if (!gr_tables_ok(nodes_host, N, edges_host, E))
+        return fail(c, SRH_ERR_BAD_ARG, "srh_graph_edge_widths: an inconsistent table (coordinates within +-2^28, edge indices in [0, N), an edge spans at most "
+                                        "16383 px per axis)");
+    if (E == 0) return 0;                        // nothing to write, nothing launched
+    const double px = (double)H * W, ob = 32.0 * E;
+    if (ranges_overlap(out, ob, nodes_dev, 8.0 * N) || ranges_overlap(out, ob, edges_dev, 8.0 * E) || ranges_overlap(out, ob, d2, 2 * px))
+        return fail(c, SRH_ERR_BAD_ARG, "srh_graph_edge_widths: out overlaps an input");
+    EdgeWidthParams p;
+    p.g.nodes = nodes_dev; p.g.edges = edges_dev; p.g.N = N; p.g.E = E; p.g.H = H; p.g.W = W; p.g.t = 1;
+    p.d2 = d2; p.R = R; p.out = out;
+    hipSetDevice(c->device);
+    hipStream_t s = (hipStream_t)stream;
+    TRYK(c, "graph_edge_widths", 0, 56.0 * E, s, launch_graph_edge_widths(p, s));
+    return 0;
+}

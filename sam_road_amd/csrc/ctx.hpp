@@ -5,6 +5,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <mutex>
 #include <string>
 #include <vector>
 
@@ -60,6 +61,10 @@ struct SRH_INTERNAL srh_ctx {
         sd_tok{bufs};
     // toponet workspace
     DevBuf t_feat16{bufs}, t_pf16{bufs}, t_pair16{bufs};
+    // ROAD_WIDTH: the column pass's distances between the two launches of srh_road_dist.  The entry runs on writer threads: the lock is
+    // held from the workspace's growth to the second launch, and calls on one stream are ordered by it.
+    DevBuf road_g{bufs};
+    std::mutex road_mu;
     // profiling
     bool profiling = false;
     std::vector<std::string> cls_names;

@@ -13,6 +13,7 @@
 #include "scene_float_piece.hpp"
 #include "graph_raster_piece.hpp"
 #include "edge_support_piece.hpp"
+#include "road_width_piece.hpp"
 
 namespace srh {
 
@@ -239,6 +240,12 @@ int launch_graph_compare(const GraphCompareParams& p, hipStream_t s);
 // The road-mask evidence under every edge (edge_support.hip; the parameters in edge_support_piece.hpp): one launch, a wave
 // per edge, four int32 per edge.  E >= 1; the tables are on the device and have been checked on the host (gr_tables_ok).  -2 for bad parameters.
 int launch_graph_edge_stats(const EdgeStatsParams& p, hipStream_t s);
+// The capped squared distance map of a thresholded mask (road_width.hip; the parameters in road_width_piece.hpp): pass 0
+// the column pass (mask -> g), pass 1 the row pass (g -> d2), one launch each.  -2 for bad parameters.
+int launch_road_dist(const RoadDistParams& p, int pass, hipStream_t s);
+// The six width statistics of every edge over its centre line: one launch, 16 lanes per edge, eight int32 per edge.  E >= 1; the tables
+// are on the device and have been checked on the host (gr_tables_ok).  -2 for bad parameters.
+int launch_graph_edge_widths(const EdgeWidthParams& p, hipStream_t s);
 
 // Bilinear sampler (F.grid_sample, align_corners=False, zeros) on channels-last embeddings.
 struct SampleParams {

@@ -173,9 +173,21 @@ def edge_support_ref(nodes, edges, mask, width, on_level, valid=None):
     n, e = check_graph(nodes, edges)
     t, level = check_width(width), check_on_level(on_level)
     out = np.zeros((e.shape[0], 4), np.int32)
-    n = n.astype(np.int64)
+    for k, box, cov in covered_sets(n, e, H, W, t):
+        m = mask[box][cov]
+        out[k, 0], out[k, 1], out[k, 2] = m.size, int(m.sum(dtype=np.int64)), int((m > level).sum())
+        if valid is not None:
+            out[k, 3] = int((valid[box][cov] == 0).sum())
+    return out
+
+
+def covered_sets(nodes, edges, H, W, t):
+    """THE COVERED SET of every edge that has pixels in the image, for the statistics that are taken over it (here and in road_width.py):
+    yields (edge index, (row slice, column slice) of the edge's box grown by ceil(t / 2) and clipped to the image, bool mask of C_e
+    inside that box).  nodes / edges: as check_graph returns them; t: a checked width.  An edge whose box is empty is not yielded."""
+    n = nodes.astype(np.int64)
     g, tt = (t + 1) // 2, t * t
-    for k, (ia, ib) in enumerate(e.tolist()):
+    for k, (ia, ib) in enumerate(edges.tolist()):
         (ar, ac), (br, bc) = n[ia].tolist(), n[ib].tolist()
         y0, y1 = max(min(ar, br) - g, 0), min(max(ar, br) + g, H - 1)
         x0, x1 = max(min(ac, bc) - g, 0), min(max(ac, bc) + g, W - 1)
@@ -191,11 +203,7 @@ def edge_support_ref(nodes, edges, mask, width, on_level, valid=None):
             at_b = 4 * ((pr - dr) ** 2 + (pc - dc) ** 2) <= tt
             cross = pr * dc - pc * dr
             cov = np.where(u <= 0, cov, np.where(u >= L, at_b, 4 * cross * cross <= tt * L))
-        m = mask[y0:y1 + 1, x0:x1 + 1][cov]
-        out[k, 0], out[k, 1], out[k, 2] = m.size, int(m.sum(dtype=np.int64)), int((m > level).sum())
-        if valid is not None:
-            out[k, 3] = int((valid[y0:y1 + 1, x0:x1 + 1][cov] == 0).sum())
-    return out
+        yield k, (slice(y0, y1 + 1), slice(x0, x1 + 1)), cov
 
 
 def _stats(stats):

@@ -29,6 +29,7 @@ from . import distributed as D
 from .aoi import aoi_edges, aoi_key_of, aoi_pack, aoi_ref, read_geojson, scene_aoi_key, scene_aoi_override
 from .graph_points import extract_graph_points
 from .edge_support import apply as apply_edge_support, edge_support_key, edge_support_override, write_geojson
+from .road_width import apply as apply_road_width, road_width_key, road_width_override
 from .graph_raster import graph_raster_key, graph_raster_override, read_gt_graph, render as render_graph, total_metrics
 from .hostcpu import fill_threads, usable_cpus, worker_threads
 from .mask_clean import MaskRule, idle as _rule_idle, mask_clean_key, mask_clean_override, mask_clean_table
@@ -2178,6 +2179,10 @@ def main(argv=None):
     edges it does not support are dropped before the pickle, the renders and diff/metrics.json are written; `--graph-geojson` writes
     graph_geojson/{id}.geojson, one LineString per edge with its evidence as properties, through `--geotransform G0 .. G5` into map
     coordinates.  Without them nothing of this runs.
+    `--road-width` (with `--road-width-radius R`, `--road-width-on T`, `--road-min-width W`, `--road-max-width W`, `--road-min-in F`,
+    `--drop-isolated-nodes`) lay over the config's ROAD_WIDTH (sam_road_amd/road_width.py): an exact distance map of the thresholded road
+    mask is built on the device and every edge gets its road width from it along its centre line; edges outside the stated widths are
+    dropped, behind EDGE_SUPPORT's filter and before the files are written, and the GeoJSON's features carry the width attributes.
     Extras: `--images a.png b.npy ...` runs explicit scene files instead of the dataset split; under torchrun
     (one process per GPU) the scenes are dealt round-robin to the ranks (`--shard scenes`, default) or every scene's tiles are split
     over the ranks (`--shard tiles`; `tiles-pipelined` for the software-pipelined loop), all ranks writing into the one output directory.
@@ -2308,6 +2313,20 @@ def main(argv=None):
                          "overriding max_invalid of the config's EDGE_SUPPORT")
     ap.add_argument("--drop-isolated-nodes", action="store_true", default=None,
                     help="(extension) after the edge filter, drop the nodes without an edge (drop_isolated of the config's EDGE_SUPPORT)")
+    ap.add_argument("--road-width", action="store_true", default=None,
+                    help="(extension) measure the road width under every edge from an exact distance map of the thresholded road mask "
+                         "(ROAD_WIDTH with its defaults; --graph-geojson writes the widths as properties)")
+    ap.add_argument("--road-width-radius", default=None, type=int, metavar="R",
+                    help="(extension) distances are exact up to R px (1..254, default 32) and capped there, overriding max_radius of the config's ROAD_WIDTH")
+    ap.add_argument("--road-width-on", default=None, type=float, metavar="T",
+                    help="(extension) a pixel is road above floor(T * 255) (default ROAD_THRESHOLD), overriding on of the config's ROAD_WIDTH")
+    ap.add_argument("--road-min-width", default=None, type=float, metavar="W",
+                    help="(extension) drop the edges whose mean road width is below W px, overriding min_width of the config's ROAD_WIDTH")
+    ap.add_argument("--road-max-width", default=None, type=float, metavar="W",
+                    help="(extension) drop the edges whose mean road width is above W px, overriding max_width of the config's ROAD_WIDTH")
+    ap.add_argument("--road-min-in", default=None, type=float, metavar="F",
+                    help="(extension) drop the edges with less than the fraction F (0..1) of their centre line on the road, overriding min_in of "
+                         "the config's ROAD_WIDTH")
     ap.add_argument("--graph-geojson", action="store_true", default=None,
                     help="(extension) write graph_geojson/{id}.geojson: one LineString per edge, [x, y] = [col + 1/2, row + 1/2], with the "
                          "edge's attributes of EDGE_SUPPORT as properties where the key is given")
@@ -2316,12 +2335,20 @@ def main(argv=None):
                          "whose value it takes when only that one is given)")
     args = ap.parse_args(argv)
     config = load_config(args.config)
-    if any(v is not None for v in (args.edge_support_width, args.edge_on, args.edge_min_mean, args.edge_min_on, args.edge_max_invalid, args.drop_isolated_nodes)):
+    road_flags = (args.road_width, args.road_width_on, args.road_width_radius, args.road_min_width, args.road_max_width, args.road_min_in)
+    road_on = any(v is not None for v in road_flags) or bool(config.get("ROAD_WIDTH"))
+    edge_flags = (args.edge_support_width, args.edge_on, args.edge_min_mean, args.edge_min_on, args.edge_max_invalid)
+    # --drop-isolated-nodes is shared: it goes to every key that is in use, and to EDGE_SUPPORT as before where ROAD_WIDTH is not
+    edge_drop = args.drop_isolated_nodes if any(v is not None for v in edge_flags) or config.get("EDGE_SUPPORT") or not road_on else None
+    if any(v is not None for v in edge_flags + (edge_drop,)):
         config.EDGE_SUPPORT = edge_support_override(config, args.edge_support_width, args.edge_on, args.edge_min_mean, args.edge_min_on,
-                                                    args.edge_max_invalid, args.drop_isolated_nodes, attributes_only=bool(args.graph_geojson))
+                                                    args.edge_max_invalid, edge_drop, attributes_only=bool(args.graph_geojson))
     support = edge_support_key(config, attributes_only=bool(args.graph_geojson))      # an EDGE_SUPPORT that cannot be used fails here, before the model is built
+    if any(v is not None for v in road_flags):
+        config.ROAD_WIDTH = road_width_override(config, *road_flags, drop_isolated=args.drop_isolated_nodes)
+    width = road_width_key(config)               # a ROAD_WIDTH that cannot be used fails here, before the model is built
     export_gt = args.geotransform if args.geotransform is not None else args.aoi_geotransform
-    post = support is not None or bool(args.graph_geojson)                           # a step between a scene's result and its files
+    post = support is not None or width is not None or bool(args.graph_geojson)      # a step between a scene's result and its files
     if args.viz or args.graph_mask is not None or args.diff is not None:
         config.GRAPH_RASTER = graph_raster_override(config, args.viz, args.graph_mask, True if args.diff == [] else args.diff)
     raster = graph_raster_key(config)            # a GRAPH_RASTER that cannot be used fails here, before the model is built
@@ -2488,7 +2515,7 @@ def main(argv=None):
                                                                                           ("diff", "diff", raster.diff)) if on is not None}
     for d in render_dirs.values():
         os.makedirs(d, exist_ok=True)
-    render_stream = torch.cuda.Stream(device) if (raster is not None or support is not None) and device.type == "cuda" else None
+    render_stream = torch.cuda.Stream(device) if (raster is not None or support is not None or width is not None) and device.type == "cuda" else None
     geojson_dir = os.path.join(output_dir, "graph_geojson") if args.graph_geojson else None
     if geojson_dir is not None:
         os.makedirs(geojson_dir, exist_ok=True)
@@ -2509,7 +2536,13 @@ def main(argv=None):
     def finish_scene(img_id, img, valid, res, gt_path):
         import contextlib
         with torch.cuda.stream(render_stream) if render_stream is not None else contextlib.nullcontext():
-            (pred_nodes, pred_edges, itsc_mask, _), attrs = apply_edge_support(support, res, valid=valid, net=net)
+            kept, attrs = apply_edge_support(support, res, valid=valid, net=net)
+            # ROAD_WIDTH runs behind EDGE_SUPPORT, on the graph it kept; the attributes of the edges both keep are merged
+            (pred_nodes, pred_edges, itsc_mask, _), widths, keep = apply_road_width(width, kept, net=net, return_keep=True)
+        if widths is not None and attrs is not None:
+            attrs = [dict(attrs[k], **w) for k, w in zip(np.flatnonzero(keep).tolist(), widths)]
+        elif widths is not None:
+            attrs = widths
         write_graph(img_id, pred_nodes, pred_edges)
         if geojson_dir is not None:
             write_geojson(os.path.join(geojson_dir, f"{img_id}.geojson"), pred_nodes, pred_edges, attrs, export_gt)

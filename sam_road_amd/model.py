@@ -314,6 +314,61 @@ class GraphRasterOps:
                                                    SAMRoad._stream(dev)), "srh_graph_edge_stats")
         return out                                # the device tables were made on this stream and are read on it
 
+    @torch.no_grad()
+    def road_dist(self, mask, on_level=127, radius=32):
+        """The capped squared distance map of a thresholded mask (srh_road_dist; ROAD_WIDTH, DESIGN.md §6q, the rule in
+        sam_road_amd/road_width.py): mask uint8 [H, W], a numpy array or a tensor on the device -> a NEW uint16 [H, W] tensor on the
+        device, 0 where mask <= on_level, else min(radius^2, the squared distance to the nearest such pixel of the image).  Two launches,
+        H W bytes of the library context's workspace between them, nothing read back."""
+        import numpy as np
+        from . import edge_support as _es
+        from . import road_width as _rw
+        ctx, dev = self._graph_ctx()
+        level, R = _es.check_on_level(on_level), _rw.check_radius(radius)
+        if not torch.is_tensor(mask):
+            mask = np.asarray(mask)
+            if mask.dtype != np.uint8 or mask.ndim != 2:
+                raise ValueError(f"mask must be uint8 [H, W], got {mask.dtype} {mask.shape}")
+            mask = torch.from_numpy(np.ascontiguousarray(mask)).to(dev)
+        if mask.dim() != 2 or mask.dtype != torch.uint8:
+            raise ValueError(f"mask must be uint8 [H, W], got {mask.dtype} {tuple(mask.shape)}")
+        H, W = mask.shape
+        if H < 1 or W < 1 or H * W > 2 ** 31 - 1:
+            raise ValueError(f"the image must have at least 1 x 1 and at most 2^31 - 1 pixels, got {H} x {W}")
+        mask = self._graph_u8("mask", mask, (H, W), dev)
+        out = torch.empty((H, W), dtype=torch.uint16, device=dev)
+        with torch.cuda.device(dev):
+            ctx.check(ctx.lib.srh_road_dist(ctx.handle, mask.data_ptr(), H, W, level, R, out.data_ptr(), SAMRoad._stream(dev)), "srh_road_dist")
+        return out
+
+    @torch.no_grad()
+    def graph_edge_widths(self, nodes, edges, d2, radius=32):
+        """The width statistics of every edge (srh_graph_edge_widths; ROAD_WIDTH): nodes int [N, 2] (row, col) and edges
+        int [E, 2] on the HOST, checked by graph_raster.check_graph; d2 the uint16 [H, W] tensor of road_dist at the same radius, on the
+        device -> a NEW int32 [E, 8] tensor on the device, rows {n, n_in, s_q, n_cap, d2_min, d2_max, 0, 0} over the edge's centre line.
+        One launch (none for E = 0), no workspace of the library context, nothing read back."""
+        from . import graph_raster as _gr
+        from . import road_width as _rw
+        ctx, dev = self._graph_ctx()
+        R = _rw.check_radius(radius)
+        n, e = _gr.check_graph(nodes, edges)
+        if not torch.is_tensor(d2) or d2.device != dev or d2.dtype != torch.uint16 or d2.dim() != 2 or not d2.is_contiguous():
+            raise ValueError(f"d2 must be a contiguous uint16 [H, W] tensor on {dev}, got "
+                             f"{(d2.dtype, tuple(d2.shape), d2.device) if torch.is_tensor(d2) else type(d2)}")
+        H, W = d2.shape
+        if H < 1 or W < 1 or H * W > 2 ** 31 - 1:
+            raise ValueError(f"the image must have at least 1 x 1 and at most 2^31 - 1 pixels, got {H} x {W}")
+        N, E = int(n.shape[0]), int(e.shape[0])
+        out = torch.empty((E, 8), dtype=torch.int32, device=dev)
+        if E == 0:
+            return out
+        n_h, e_h = torch.from_numpy(n), torch.from_numpy(e)
+        n_d, e_d = n_h.to(dev), e_h.to(dev)
+        with torch.cuda.device(dev):
+            ctx.check(ctx.lib.srh_graph_edge_widths(ctx.handle, n_h.data_ptr(), n_d.data_ptr(), N, e_h.data_ptr(), e_d.data_ptr(), E, H, W,
+                                                    d2.data_ptr(), R, out.data_ptr(), SAMRoad._stream(dev)), "srh_graph_edge_widths")
+        return out                                # the device tables were made on this stream and are read on it
+
 
 class DeviceGraphOps(GraphRasterOps):
     """GraphRasterOps without a model: the entries need a device, not weights."""

@@ -43,6 +43,9 @@ The final map_decoder bias is lowered so that the random network yields sparse m
                                                                     # identical mask passed as valid in turn, and the host time of nodata_ref
     python tools/scene_bench.py --edge-support [T] [--scene 4096 --tiles 32]     # EDGE_SUPPORT: the per-edge statistics against edge_support_ref, the whole
                                                                     # call, the kernel alone, the host reference, the pipelined loop without / with the filter
+    python tools/scene_bench.py --road-width [R] [--scene 4096 --tiles 32]       # ROAD_WIDTH: the distance map and the per-edge statistics against their
+                                                                    # references, the whole call, the three kernels alone, the same work on the host,
+                                                                    # the pipelined loop without / with the key
     python tools/scene_bench.py --viz [--scene 4096 --tiles 32]     # GRAPH_RASTER: "graph_raster" compares the device class map with graph_raster_ref
                                                                     # (the run ends if they differ), reports the device time of raster, composite and
                                                                     # compare beside pass 1 and the host reference, and the pipelined loop with PNG
@@ -726,6 +729,123 @@ def edge_support_report(args, net, cfg, img, iters=20):
     return rep
 
 
+def road_width_report(args, net, cfg, img, iters=20):
+    """--road-width [R] (ROAD_WIDTH): the device distance map against road_dist_ref and the device statistics against road_width_ref on
+    this scene size (the run ends if they differ); ms of the whole apply call from host arrays (mask and table upload, three kernels, the
+    32 E-byte download, keep rule and attributes; wall clock around a synchronised call) and of the device part alone, device ms of each
+    of the three kernels (the profiler rows), host ms of the same work (scipy's distance_transform_edt where it is installed, road_dist_ref,
+    the per-edge loop of road_width_ref); and ms per scene of the pipelined loop as the CLI runs it — mask PNGs on writer threads —
+    without the key and with it (on a writer thread, on a stream of its own), alternated.  The graph is the scene's own if the stand-in
+    weights yield at least 1000 edges, else a synthetic road grid of 32-px cells."""
+    import sam_road_amd.inferencer as inf
+    from concurrent.futures import ThreadPoolExecutor
+    from PIL import Image
+    import io
+    from sam_road_amd import edge_support as es
+    from sam_road_amd import road_width as rw
+    dev = next(net.parameters()).device
+    H, W = img.shape[:2]
+    R = args.road_width
+    nodes, edges, _, road = inf.infer_one_img(net, img, cfg)
+    own = edges.shape[0] >= 1000
+    if not own:
+        nodes, edges = road_grid(H, W, 32, 1)
+    level = es.on_level_of(cfg.ROAD_THRESHOLD)
+    rep = {"graph": "the scene's own" if own else "synthetic road grid, 32-px cells", "nodes": int(nodes.shape[0]), "edges": int(edges.shape[0]), "max_radius": R,
+           "on_level": level}
+    try:
+        from scipy.ndimage import distance_transform_edt
+        t0 = time.perf_counter()
+        distance_transform_edt(road > level)
+        rep["host_ms_scipy_distance_transform_edt"] = round(1e3 * (time.perf_counter() - t0), 1)
+    except ImportError:
+        rep["host_ms_scipy_distance_transform_edt"] = None
+    t0 = time.perf_counter()
+    d2 = rw.road_dist_ref(road, level, R)
+    rep["host_ms_road_dist_ref"] = round(1e3 * (time.perf_counter() - t0), 1)
+    t0 = time.perf_counter()
+    want = rw.road_width_ref(nodes, edges, road, level, R, d2=d2)
+    rep["host_ms_road_width_ref_edge_loop"] = round(1e3 * (time.perf_counter() - t0), 1)
+    road_d = torch.from_numpy(road).to(dev)
+    d2_d = net.road_dist(road_d, level, R)
+    if not np.array_equal(d2_d.cpu().numpy(), d2):
+        raise SystemExit(f"the device distance map differs from road_dist_ref on {int((d2_d.cpu().numpy() != d2).sum())} pixels")
+    got = rw.edge_widths(nodes, edges, road, level, R, net=net)
+    if not np.array_equal(got, want):
+        raise SystemExit(f"the device statistics differ from road_width_ref on {int((got != want).any(axis=1).sum())} edges")
+    rep["equals_road_dist_ref"] = rep["equals_road_width_ref"] = True
+    rep["road_fraction"], rep["capped_fraction_of_road"] = round(float((d2 > 0).mean()), 4), round(float((d2 == R * R).sum() / max(1, (d2 > 0).sum())), 4)
+    rep["covered_px_per_edge_mean"], rep["in_road_px_per_edge_mean"] = round(float(want[:, 0].mean()), 2), round(float(want[:, 1].mean()), 2)
+
+    def wall_ms(fn):
+        fn()
+        ms = []
+        for _ in range(iters):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            fn()
+            ms.append(1e3 * (time.perf_counter() - t0))
+        ms.sort()
+        return {"median": round(ms[len(ms) // 2], 4), "min_max": [round(ms[0], 4), round(ms[-1], 4)]}
+
+    key = rw.road_width_key_of({"max_radius": R}, cfg.ROAD_THRESHOLD)
+    result = (nodes, edges, road, road)
+    rep["whole_apply_ms_from_host_arrays"] = wall_ms(lambda: rw.apply(key, result, net=net))
+    rep["edge_widths_ms_from_host_arrays"] = wall_ms(lambda: rw.edge_widths(nodes, edges, road, level, R, net=net))
+    rep["device_part_ms_mask_on_the_device"] = wall_ms(lambda: net.graph_edge_widths(nodes, edges, net.road_dist(road_d, level, R), R).cpu())
+    ctx, _ = net._weights(dev)
+    per_call = []
+    for _ in range(3):                                     # three groups of `iters` calls: the run-to-run span of the kernel times
+        ctx.profile_read()
+        ctx.profile_enable(True)
+        for _ in range(iters):
+            net.graph_edge_widths(nodes, edges, net.road_dist(road_d, level, R), R)
+        torch.cuda.synchronize()
+        rows = {r["name"]: round(r["ms"] / r["launches"], 4) for r in ctx.profile_read() if r["launches"]}
+        per_call.append({k: rows[k] for k in ("road_dist_cols", "road_dist_rows", "graph_edge_widths")})
+        ctx.profile_enable(False)
+    rep["kernel_ms_per_call_three_groups"] = per_call
+    if args.no_pipelined:
+        return rep
+    stream = torch.cuda.Stream(dev)
+
+    def png(a):
+        Image.fromarray(a).save(io.BytesIO(), format="PNG", compress_level=1)
+
+    stage = []
+
+    def finish(res):
+        t0 = time.perf_counter()
+        with torch.cuda.stream(stream):
+            rw.apply(key, res, net=net)
+        stage.append(1e3 * (time.perf_counter() - t0))
+
+    def piped(on, n=12, writers=3):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        with ThreadPoolExecutor(writers) as pool:
+            futs = []
+            for res in inf.infer_imgs(net, (img for _ in range(n)), cfg):
+                futs += [pool.submit(png, res[2]), pool.submit(png, res[3])]
+                if on:
+                    futs.append(pool.submit(finish, res))
+            for f in futs:
+                f.result()
+        torch.cuda.synchronize()
+        return round(1e3 * (time.perf_counter() - t0) / n, 2)
+
+    for on in (False, True):
+        piped(on, 3)
+    stage.clear()
+    runs = {"without_2_writers": [], "without": [], "with": []}      # the CLI adds a writer thread with the key: both pools, so the thread is not mistaken for the key
+    for _ in range(3):
+        for name, on, writers in (("without_2_writers", False, 2), ("without", False, 3), ("with", True, 3)):
+            runs[name].append(piped(on, writers=writers))
+    rep["pipelined_ms_per_scene_runs_of_12_alternated"] = runs
+    rep["writer_thread_ms_per_scene_median_width_step"] = round(sorted(stage)[len(stage) // 2], 2)
+    return rep
+
+
 def float_report(args, net, cfg, img, rng, iters=20):
     """--float C [--float-range LO HI] [--float-percentile P Q]: the scene as a C-band float32 scene (bands 0..2 hold the synthetic RGB / 255,
     the rest noise).  The device result against float_scene_ref for both keys (the run ends if they differ); device ms of each SCENE_FLOAT
@@ -867,6 +987,9 @@ def main():
     ap.add_argument("--diff", action="store_true", help="GRAPH_RASTER: the same leg as --viz")
     ap.add_argument("--edge-support", type=int, nargs="?", const=1, default=None, metavar="T",
                     help="EDGE_SUPPORT: time the per-edge statistics at width T (default 1) on this scene and the pipelined loop without / with the filter, alternated")
+    ap.add_argument("--road-width", type=int, nargs="?", const=32, default=None, metavar="R",
+                    help="ROAD_WIDTH: time the distance map at max_radius R (default 32) and the per-edge statistics on this scene and the pipelined loop "
+                         "without / with the key, alternated")
     ap.add_argument("--float", type=int, default=None, metavar="C",
                     help="SCENE_FLOAT: the scene arrives as a float32 scene of C bands (bands 0..2 hold the synthetic RGB / 255, the rest noise); "
                          "the three launches, the pipelined loop with a fixed range and with a percentile stretch and the host reference are timed")
@@ -979,6 +1102,11 @@ def main():
         if world > 1 or args.scenes is not None or args.valid_frac is not None or args.scale is not None or args.bands is not None:
             ap.error("--edge-support times one unmasked u8 scene on one GPU (not with --scenes, --valid-frac, --scale or --bands)")
         print(json.dumps({"scene": f"synthetic {H}x{W}", "infer_batch_size": args.batch, "edge_support": edge_support_report(args, net, cfg, img)}))
+        return
+    if args.road_width is not None:
+        if world > 1 or args.scenes is not None or args.valid_frac is not None or args.scale is not None or args.bands is not None:
+            ap.error("--road-width times one unmasked u8 scene on one GPU (not with --scenes, --valid-frac, --scale or --bands)")
+        print(json.dumps({"scene": f"synthetic {H}x{W}", "infer_batch_size": args.batch, "road_width": road_width_report(args, net, cfg, img)}))
         return
     if args.float is not None:
         if world > 1 or args.scenes is not None or args.valid_frac is not None or args.scale is not None or args.bands is not None:
