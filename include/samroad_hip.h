@@ -528,6 +528,28 @@ int srh_road_dist(srh_ctx* ctx, const uint8_t* mask, int H, int W, int on_level,
 int srh_graph_edge_widths(srh_ctx* ctx, const int32_t* nodes_host, const int32_t* nodes_dev, int N, const int32_t* edges_host,
                           const int32_t* edges_dev, int E, int H, int W, const uint16_t* d2, int R, int32_t* out, void* stream);
 
+/* GeoTIFF scenes (config key GEOTIFF; an extension).  Two additive entries, srh_tiff_assemble here and the host entry
+ * srh_tiff_lzw_decode below; the ABI number stays 11 because nothing existing changes, and a run without the key calls neither.
+ *
+ * srh_tiff_assemble: the DECOMPRESSED strips or tiles of a TIFF, as the file holds them, -> the raster out [H, W, C] on the device, samples
+ * of dtype SRH_U8, SRH_U16 or SRH_F32 (moved as bit patterns) in native byte order.  flat: flat_bytes bytes on the device, 16-byte
+ * aligned.  The table, int64 [n_seg, 7], is given twice, as for srh_mask_clean: table_host is validated and sizes the launch, table_dev is
+ * what the kernel reads.  Row k: {OFF, BYTES, ROW0, COL0, ROWS, COLS, BAND}: the segment lies at flat + OFF (a multiple of 16) and covers
+ * rows ROW0 .. ROW0 + ROWS - 1 and columns COL0 .. COL0 + COLS - 1 — those outside the raster are padding and are never stored; BAND -1:
+ * ROWS x COLS pixels of C interleaved samples, BAND b: ROWS x COLS samples of band b.  BYTES = ROWS x COLS x (C or 1) x sample size.
+ * predictor 1: none; 2 (SRH_U8, SRH_U16): every sample is the wrapping difference to the sample of the same band one pixel to the left in
+ * the segment's row; 3 (SRH_F32): TIFF Technical Note 3, the row's four byte planes, most significant first, differenced bytewise with
+ * stride C (1 for a band segment) over the whole row.  big_endian 1: the samples of predictor 1 and 2 are byte-swapped first.
+ * One launch whatever the file holds: a workgroup per row of a segment, an exact parallel prefix sum in wrapping integers (shuffles in a
+ * wave, LDS across waves, fixed-size chunks with a carried total: LDS does not depend on W), 16-byte stores where a chunky row's
+ * alignment allows, no atomics, nothing read back.  The pixels no segment covers are not written.  It equals tiff_read_ref of
+ * sam_road_amd/geotiff.py bit for bit.  SRH_ERR_BAD_ARG, and nothing is launched, for a null argument, H or W < 1 or H W > 2^31 - 1, C
+ * outside 1 .. 16, another dtype, a predictor that does not go with the dtype, n_seg < 1, a misaligned flat, out or device table, an out
+ * that overlaps an input, or a host table in which a segment leaves flat or starts outside the raster, OFF is no multiple of 16, BAND
+ * lies outside -1 .. C - 1 or BYTES is not the product above.  Profiler row: tiff_assemble. */
+int srh_tiff_assemble(srh_ctx* ctx, const uint8_t* flat, int64_t flat_bytes, const int64_t* table_host, const int64_t* table_dev, int n_seg,
+                      void* out, int H, int W, int C, int dtype, int predictor, int big_endian, void* stream);
+
 /* op level(used by the parity tests to localise a failure; same kernels as above) ----------------- */
 
 /* out = act(A[M,K] W[N,K]^T + bias) (+resid); A,W fp16; N%128==0, K%64==0. act: 0/1 GELU/2 ReLU. */
@@ -739,6 +761,15 @@ int srh_pass2_vote_sums(const float* const* scores, const int32_t* batch_tile0, 
  * distinct).  out_edges int64 [n,2]; *n_edges their number. */
 int srh_votes_to_edges(const int64_t* keys, const double* sums, const double* counts, const int64_t* first, int64_t n,
                        int64_t n_points, double threshold, int64_t* out_edges, int64_t* n_edges);
+
+/* The LZW segments of a TIFF (config key GEOTIFF), decoded on host threads: codes most significant bit first, 9 to 12
+ * bits, the width growing one code early, 256 = clear, 257 = end, as every current writer emits them.  Segment k is src[in_off[k] ..
+ * in_off[k] + in_bytes[k]) and must decode to exactly out_bytes[k] bytes, written at dst + out_off[k]; n_threads workers take segments
+ * from a shared counter.  Whatever a stream holds, nothing is read outside its input and nothing written outside its output.  Returns
+ * 0, or k + 1 for the lowest k whose stream is damaged or holds fewer or more bytes (the other segments are decoded all the same), or
+ * SRH_ERR_BAD_ARG for a null pointer, a negative size or a segment that leaves src or dst.  No device work. */
+int srh_tiff_lzw_decode(const uint8_t* src, int64_t src_bytes, const int64_t* in_off, const int64_t* in_bytes, int64_t n, uint8_t* dst,
+                        int64_t dst_bytes, const int64_t* out_off, const int64_t* out_bytes, int32_t n_threads);
 
 #ifdef __cplusplus
 }

@@ -593,3 +593,34 @@ extern "C" int srh_graph_edge_widths(srh_ctx* c, const int32_t* nodes_host, cons
     TRYK(c, "graph_edge_widths", 0, 56.0 * E, s, launch_graph_edge_widths(p, s));
     return 0;
 }
+
+// ---- a GeoTIFF's decompressed segments -> the scene raster (kernel in scene_tiff.hip, behaviour in DESIGN.md §6r) ---------------------------------
+extern "C" int srh_tiff_assemble(srh_ctx* c, const uint8_t* flat, int64_t flat_bytes, const int64_t* table_host, const int64_t* table_dev, int n_seg,
+                                 void* out, int H, int W, int C, int dtype, int predictor, int big_endian, void* stream) {
+    if (!c || !flat || !table_host || !table_dev || !out) return fail(c, SRH_ERR_BAD_ARG, "srh_tiff_assemble: null argument");
+    if (H < 1 || W < 1 || (double)H * W > (double)TIF_MAX_PIXELS) return fail(c, SRH_ERR_BAD_ARG, "srh_tiff_assemble: H and W are at least 1 and H W at most 2^31 - 1");
+    if (C < 1 || C > TIF_MAX_BANDS) return fail(c, SRH_ERR_BAD_ARG, "srh_tiff_assemble: 1 to 16 bands");
+    if (dtype != SRH_U8 && dtype != SRH_U16 && dtype != SRH_F32) return fail(c, SRH_ERR_BAD_ARG, "srh_tiff_assemble: the samples are SRH_U8, SRH_U16 or SRH_F32");
+    const int B = dtype == SRH_U8 ? 1 : dtype == SRH_U16 ? 2 : 4;
+    if (predictor < 1 || predictor > 3 || (predictor == 2 && B == 4) || (predictor == 3 && B != 4))
+        return fail(c, SRH_ERR_BAD_ARG, "srh_tiff_assemble: predictor 1, 2 with integer samples or 3 with float samples");
+    if (big_endian != 0 && big_endian != 1) return fail(c, SRH_ERR_BAD_ARG, "srh_tiff_assemble: big_endian is 0 or 1");
+    if (n_seg < 1 || flat_bytes < 1) return fail(c, SRH_ERR_BAD_ARG, "srh_tiff_assemble: at least one segment");
+    if (reinterpret_cast<uintptr_t>(flat) & (TIF_ALIGN - 1)) return fail(c, SRH_ERR_BAD_ARG, "srh_tiff_assemble: flat is 16-byte aligned");
+    if (reinterpret_cast<uintptr_t>(out) & (uintptr_t)(B - 1)) return fail(c, SRH_ERR_BAD_ARG, "srh_tiff_assemble: out is aligned to its samples");
+    if (reinterpret_cast<uintptr_t>(table_dev) & 7) return fail(c, SRH_ERR_BAD_ARG, "srh_tiff_assemble: the device table is 8-byte aligned");
+    long max_rows = 0;
+    if (!tif_table_ok(table_host, n_seg, flat_bytes, H, W, C, B, &max_rows))
+        return fail(c, SRH_ERR_BAD_ARG, "srh_tiff_assemble: an inconsistent table (a segment leaves the flat array or the raster, is misaligned, or its bytes are "
+                                        "not rows x columns x samples)");
+    const double ob = (double)H * W * C * B;
+    if (ranges_overlap(out, ob, flat, (double)flat_bytes) || ranges_overlap(out, ob, table_dev, 56.0 * n_seg))
+        return fail(c, SRH_ERR_BAD_ARG, "srh_tiff_assemble: out overlaps an input");
+    TiffParams p;
+    p.flat = flat; p.table = table_dev; p.n_seg = n_seg; p.max_rows = (int)max_rows; p.out = static_cast<uint8_t*>(out);
+    p.H = H; p.W = W; p.C = C; p.B = B; p.predictor = predictor; p.big_endian = big_endian;
+    hipSetDevice(c->device);
+    hipStream_t s = (hipStream_t)stream;
+    TRYK(c, "tiff_assemble", 0, (double)flat_bytes + ob, s, launch_tiff_assemble(p, s));
+    return 0;
+}

@@ -889,3 +889,34 @@ extern "C" int srh_votes_to_edges(const int64_t* keys, const double* sums, const
     *n_edges = e;
     return 0;
 } catch (...) { return SRH_ERR_HIP; }      // std::bad_alloc / std::system_error (thread limit) must not cross the C ABI
+
+// ---------------------------------------------------------------------------------------------------------------
+// The LZW segments of a TIFF (config key GEOTIFF; the decoder in geotiff_piece.hpp): segment k is
+// src[in_off[k] .. + in_bytes[k]) and decodes to exactly out_bytes[k] bytes at dst + out_off[k].  Worker threads take
+// segments from a shared counter.  0, or k + 1 for the first segment (lowest k) whose stream is damaged, short or long.
+// ---------------------------------------------------------------------------------------------------------------
+#include "geotiff_piece.hpp"
+
+extern "C" int srh_tiff_lzw_decode(const uint8_t* src, int64_t src_bytes, const int64_t* in_off, const int64_t* in_bytes, int64_t n,
+                                   uint8_t* dst, int64_t dst_bytes, const int64_t* out_off, const int64_t* out_bytes, int32_t n_threads) try {
+    if (n < 0 || src_bytes < 0 || dst_bytes < 0 || (n > 0 && (!src || !dst || !in_off || !in_bytes || !out_off || !out_bytes))) return SRH_ERR_BAD_ARG;
+    for (int64_t k = 0; k < n; ++k)
+        if (in_off[k] < 0 || in_bytes[k] < 0 || in_off[k] > src_bytes || in_bytes[k] > src_bytes - in_off[k] || out_off[k] < 0 || out_bytes[k] < 0 ||
+            out_off[k] > dst_bytes || out_bytes[k] > dst_bytes - out_off[k])
+            return SRH_ERR_BAD_ARG;
+    std::atomic<int64_t> next(0), bad(n);
+    auto work = [&] {
+        for (int64_t k = next.fetch_add(1); k < n; k = next.fetch_add(1))
+            if (srh::tif_lzw_decode(src + in_off[k], (long)in_bytes[k], dst + out_off[k], (long)out_bytes[k]) != 0) {
+                int64_t seen = bad.load();
+                while (k < seen && !bad.compare_exchange_weak(seen, k)) {}
+            }
+    };
+    const int64_t nt = std::max<int64_t>(1, std::min<int64_t>(n_threads, n));
+    {
+        JoiningThreads pool;
+        for (int64_t t = 1; t < nt; ++t) pool.emplace_back(work);
+        work();
+    }
+    return bad.load() < n ? (int)std::min<int64_t>(bad.load() + 1, INT_MAX) : 0;
+} catch (...) { return SRH_ERR_HIP; }      // std::system_error (thread limit) must not cross the C ABI

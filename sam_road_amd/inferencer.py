@@ -27,6 +27,7 @@ import torch
 from . import _lib
 from . import distributed as D
 from .aoi import aoi_edges, aoi_key_of, aoi_pack, aoi_ref, read_geojson, scene_aoi_key, scene_aoi_override
+from .geotiff import TiffScene, geotiff_key, geotiff_override, is_tiff_path, open_scene, write_geotiff
 from .graph_points import extract_graph_points
 from .edge_support import apply as apply_edge_support, edge_support_key, edge_support_override, write_geojson
 from .road_width import apply as apply_road_width, road_width_key, road_width_override
@@ -600,7 +601,7 @@ def _scene_plan(img, config):
     INFER_PATCHES_PER_EDGE may be an int or [n_y, n_x].  Everything that can be refused is refused here, before the device is
     touched."""
     neighbor_queries(config)
-    img = np.asarray(img)
+    img = img if isinstance(img, TiffScene) else np.asarray(img)      # a GeoTIFF scene (GEOTIFF, DESIGN.md §6r) is checked by its header and decoded on the device
     # the reference uses img.shape[0] for both axes (inferencer.py:63,67) and casts whatever it gets to f32: it would mis-stride a
     # non-square scene and silently convert a non-u8 one.  Here H and W are separate all the way down; non-u8 is refused
     bands = scene_bands_key(config)
@@ -997,6 +998,9 @@ class _GroupScene:
 def _plan_group_scene(img, valid, config):
     """_pass1_front's planning step for one scene of a group: the same checks in the same order, so a scene that would raise alone
     raises the same error here."""
+    if isinstance(img, TiffScene):
+        raise ValueError(f"{img.path}: a GeoTIFF scene (GEOTIFF) does not combine with SCENE_GROUP (a group's scenes are packed from host arrays): "
+                         "drop one of them")
     img, infos, all_xy = _scene_plan(img, config)
     pad = scene_pad_plan(img.shape, config)
     shape = tuple(int(v) for v in img.shape[:2])
@@ -1212,7 +1216,7 @@ class _Lane:
 class _BlockingIO:
     """How infer_one_img and the tile-sharded loops move a scene's arrays: one blocking copy each way, pageable memory.  The other
     implementation of the same four operations is _LaneIO.  `lap` (a _Laps) names the steps of pass 1 for the profile."""
-    STEPS = {"upload": "scene upload", "aoi": "area of interest mask", "nodata": "nodata mask", "bands": "band select + stretch", "float": "float scene -> u8 + mask", "scale": "scene resample", "pad": "scene pad", "pack": "group pack", "select": "tile selection (count kernel + counts D2H)", "fill": "nodata fill",
+    STEPS = {"upload": "scene upload", "tiff": "GeoTIFF assemble", "aoi": "area of interest mask", "nodata": "nodata mask", "bands": "band select + stretch", "float": "float scene -> u8 + mask", "scale": "scene resample", "pad": "scene pad", "pack": "group pack", "select": "tile selection (count kernel + counts D2H)", "fill": "nodata fill",
              "pass 1": "pass 1 (GPU)"}
     alloc = None                                       # the pass-2 collate fills plain numpy arrays
 
@@ -1239,7 +1243,7 @@ class _LaneIO:
     """The operations of _BlockingIO on infer_imgs' lane, for ONE scene in flight (`pool`: its page-locked staging): uploads are staged
     and stream-ordered, the counts come back over the copy stream, the pass-2 collate writes straight into the staging buffers.  With the
     profile on, five device events time the scene's pass 1, pass 2 and score download."""
-    STEPS = {"upload": "stage + queue scene upload", "aoi": "queue area of interest mask", "nodata": "queue nodata mask", "bands": "band select + stretch (upload lane)", "float": "float scene -> u8 + mask (upload lane)", "scale": "queue scene resample", "pad": "queue scene pad", "pack": "queue group pack", "select": "tile selection (upload lane)", "pass 1": "queue pass 1"}
+    STEPS = {"upload": "stage + queue scene upload", "tiff": "queue GeoTIFF assemble", "aoi": "queue area of interest mask", "nodata": "queue nodata mask", "bands": "band select + stretch (upload lane)", "float": "float scene -> u8 + mask (upload lane)", "scale": "queue scene resample", "pad": "queue scene pad", "pack": "queue group pack", "select": "tile selection (upload lane)", "pass 1": "queue pass 1"}
     EVENTS = {"launch pass 1": 0, "normalised": 1, "pass 2 uploaded": 2, "pass 2 launched": 3, "pass 2 on its way back": 4}
 
     def __init__(self, lane, pool, lap):
@@ -1363,6 +1367,22 @@ class _SceneJob:
     model_masks: list = None
 
 
+def _upload_scene(net, io, img):
+    """THE scene upload of every loop.  An array goes as it always went.  A TiffScene (GEOTIFF) goes as the decompressed
+    segments of its file, predictor, byte order, planes and tiles as the file has them, and one launch assembles the raster [H, W, C] on
+    the device (step "tiff"): the decoded, interleaved scene never exists on the host, and everything behind this sees the device raster
+    it always saw.  A file that IS the raster (little-endian, uncompressed, predictor 1, chunky strips) is uploaded and used as it is."""
+    if not isinstance(img, TiffScene):
+        return io.upload("scene", img)
+    flat, table = img.loaded(fill_threads())
+    if img.is_raster:
+        return io.upload("scene", flat.view(img.dtype).reshape(img.shape))
+    flat_d, table_d = io.upload("scene", flat), io.upload("tiff_table", table)
+    scene = net.tiff_assemble(img, flat_d, table, table_d)
+    io.step("tiff")
+    return scene
+
+
 def _pass1_front(ctx, io, img, valid=None, group=None, aoi=None):
     """Pass 1 of one scene, queued (GPU): plan, upload, [band step,] [resample,] [border padding,] [tile selection, nodata fill,] crop ->
     encoder -> decoder -> fused canvases, [canvas reduce,] normalise[, masks cropped back][, small components dropped][, masks resampled
@@ -1426,7 +1446,7 @@ def _pass1_front(ctx, io, img, valid=None, group=None, aoi=None):
         elif masked:
             min_frac, fill = _mask_keys(config)
         pass1_kw, norm_kw, n_orient = ctx.features
-        scene = io.upload("scene", img)                    # the u8 scene, ONCE; tiles are cropped on the device
+        scene = _upload_scene(net, io, img)                # the u8 scene, ONCE; tiles are cropped on the device
         xy_dev = io.upload("xy", all_xy)
         if ctx.clean is not None:                          # MASK_CLEAN: the two masks of the real scene (model frame), one above the other
             clean_table = _mask_clean_images(ctx.clean, [(0, *shape)], shape[0] * shape[1])
@@ -2086,6 +2106,29 @@ def get_img_paths(root_dir, image_indices):
     return [os.path.join(root_dir, f"region_{ind}_sat.png") for ind in image_indices]
 
 
+def _nodata_from_files(heads):
+    """GEOTIFF nodata: file — the ONE nodata value (tag 42113) the run's GeoTIFF scenes state, as (value, whether the files are float):
+    an int for integer files.  ValueError for a run without such scenes, a file without the tag, two files that differ (both are named),
+    integer and float files side by side, or a value an integer file cannot hold."""
+    if not heads:
+        raise ValueError("GEOTIFF: nodata 'file' (--nodata-from-file) needs --images with .tif / .tiff scenes")
+    items = list(heads.items())
+    p0, h0 = items[0]
+    same = lambda a, b: a == b or (a != a and b != b)
+    for p, h in items:
+        if h.nodata is None:
+            raise ValueError(f"{p}: the file states no nodata value (tag 42113), which GEOTIFF nodata 'file' (--nodata-from-file) asks for")
+        if not same(h.nodata, h0.nodata):
+            raise ValueError(f"GEOTIFF: nodata 'file': {p0} states {h0.nodata!r} and {p} states {h.nodata!r}; all scenes of a run must state one value")
+        if (h.dtype.kind == "f") != (h0.dtype.kind == "f"):
+            raise ValueError(f"GEOTIFF: nodata 'file': {p0} is {h0.dtype} and {p} is {h.dtype}; run integer and float scenes apart")
+    if h0.dtype.kind == "f":
+        return float(h0.nodata), True
+    if h0.nodata != int(h0.nodata) or not 0 <= h0.nodata < 2 ** (8 * h0.dtype.itemsize):
+        raise ValueError(f"{p0}: the nodata value {h0.nodata!r} (tag 42113) is no level of a {h0.dtype} scene")
+    return int(h0.nodata), False
+
+
 def read_rgb_img(path):
     """dataset.py:16-19 (cv2.imread + BGR->RGB): [H,W,3] uint8 RGB.  PIL decodes the same 8-bit PNGs."""
     from PIL import Image
@@ -2333,8 +2376,21 @@ def main(argv=None):
     ap.add_argument("--geotransform", default=None, nargs=6, type=float, metavar="G",
                     help="(extension) G0 .. G5 of the GeoJSON export: X = G0 + x G1 + y G2, Y = G3 + x G4 + y G5 (the forward of --aoi-geotransform, "
                          "whose value it takes when only that one is given)")
+    ap.add_argument("--geotiff", action="store_true", default=None,
+                    help="(extension) read .tif / .tiff scenes as GeoTIFFs (GEOTIFF with its defaults): strips or tiles, 1..16 bands of uint8 / uint16 / "
+                         "float32, LZW or deflate, predictors, both byte orders, BigTIFF; decompressed on host threads, assembled on the device.  The "
+                         "scene's own geotransform becomes the default of --geotransform and --aoi-geotransform")
+    ap.add_argument("--nodata-from-file", action="store_true", default=None,
+                    help="(extension) take the files' nodata value (tag 42113) as the value of SCENE_NODATA, or as nodata of SCENE_FLOAT for float "
+                         "files (nodata: file of the config's GEOTIFF); every scene of the run must state the same value")
+    ap.add_argument("--mask-geotiff", action="store_true", default=None,
+                    help="(extension) also write mask_tif/{id}_road.tif and mask_tif/{id}_itsc.tif with the scene's geo tags (masks of the config's GEOTIFF)")
     args = ap.parse_args(argv)
     config = load_config(args.config)
+    if args.geotiff or args.nodata_from_file or args.mask_geotiff:
+        config.GEOTIFF = geotiff_override(config, args.geotiff, args.nodata_from_file, args.mask_geotiff)
+    tiff = geotiff_key(config)                   # a GEOTIFF that cannot be used fails here, and so does a file that cannot be read:
+    tiff_heads = {p: open_scene(p) for p in (args.images or []) if is_tiff_path(p)} if tiff is not None else {}      # headers only
     road_flags = (args.road_width, args.road_width_on, args.road_width_radius, args.road_min_width, args.road_max_width, args.road_min_in)
     road_on = any(v is not None for v in road_flags) or bool(config.get("ROAD_WIDTH"))
     edge_flags = (args.edge_support_width, args.edge_on, args.edge_min_mean, args.edge_min_on, args.edge_max_invalid)
@@ -2349,6 +2405,7 @@ def main(argv=None):
     width = road_width_key(config)               # a ROAD_WIDTH that cannot be used fails here, before the model is built
     export_gt = args.geotransform if args.geotransform is not None else args.aoi_geotransform
     post = support is not None or width is not None or bool(args.graph_geojson)      # a step between a scene's result and its files
+    tiff_masks = tiff is not None and tiff.masks
     if args.viz or args.graph_mask is not None or args.diff is not None:
         config.GRAPH_RASTER = graph_raster_override(config, args.viz, args.graph_mask, True if args.diff == [] else args.diff)
     raster = graph_raster_key(config)            # a GRAPH_RASTER that cannot be used fails here, before the model is built
@@ -2367,6 +2424,24 @@ def main(argv=None):
             job_aois = [None if path == "-" else scene_aoi_override(config, read_geojson(path)) for path in args.aoi]
             for a in job_aois:
                 aoi_key_of(a)
+    if tiff is not None and tiff.georef and tiff_heads and config.get("SCENE_AOI"):
+        # GEOTIFF: a scene's own geotransform is the default of the area of interest's, scene by scene; one that is given wins
+        base = config.SCENE_AOI if isinstance(config.SCENE_AOI, dict) else {"include": list(config.SCENE_AOI)}
+        if "geotransform" not in base:
+            mine = lambda k: job_aois[k] if job_aois is not None and job_aois[k] is not None else base
+            own = [dict(mine(k), geotransform=list(tiff_heads[p].geotransform)) if p in tiff_heads and tiff_heads[p].geotransform is not None else mine(k)
+                   for k, p in enumerate(args.images)]
+            stated = [a["geotransform"] for a in own if "geotransform" in a]
+            if stated:                       # every scene brings its own key; the config's (saved with the run) says the first scene's transform
+                for a in own:
+                    aoi_key_of(a)
+                job_aois, config.SCENE_AOI = own, dict(base, geotransform=stated[0])
+    if tiff is not None and tiff.nodata == "file":
+        value, is_float = _nodata_from_files(tiff_heads)
+        if is_float and value == value:      # NaN is nodata under SCENE_FLOAT whatever the key says
+            config.SCENE_FLOAT = scene_float_override(config, nodata=[value])
+        elif not is_float:
+            config.SCENE_NODATA = scene_nodata_override(config, [value])
     if any(v is not None for v in (args.nodata, args.nodata_tolerance, args.nodata_match, args.nodata_min_area, args.nodata_grow)):
         config.SCENE_NODATA = scene_nodata_override(config, args.nodata, args.nodata_tolerance, args.nodata_match, args.nodata_min_area, args.nodata_grow)
     if args.bands is not None or args.stretch_range is not None or args.stretch_percentile is not None or args.gamma is not None:
@@ -2448,7 +2523,8 @@ def main(argv=None):
         job_masks = job_masks[rank::world]
         job_gts = job_gts[rank::world]
         job_aois = job_aois[rank::world] if job_aois is not None else None
-    use_alpha = args.valid_masks is None and any(has_alpha(p) for _, p in jobs)      # headers only; mask files take precedence
+    as_tiff = lambda p: tiff is not None and is_tiff_path(p)                          # GEOTIFF: such a scene's bands are bands, none is an alpha
+    use_alpha = args.valid_masks is None and any(has_alpha(p) for _, p in jobs if not as_tiff(p))      # headers only; mask files take precedence
     masked = args.valid_masks is not None or use_alpha
     import collections
     scene_valids = collections.deque()           # the masks of the scenes the loader has handed out, in the same order
@@ -2471,10 +2547,13 @@ def main(argv=None):
 
     def scenes(depth=3):                         # decode ahead on worker threads: a 2048^2 RGB PNG takes ~100 ms to decode, more than
         def load(path, mask_path):               # the GPU needs for the scene
-            img = np.load(path) if str(path).endswith(".npy") else read_rgb_img(path)
+            if as_tiff(path):                      # header, then the segments decompressed on host threads: the pixels are assembled on the device
+                img = open_scene(path).load(fill_threads())
+            else:
+                img = np.load(path) if str(path).endswith(".npy") else read_rgb_img(path)
             if mask_path is not None:
                 return img, read_valid_mask(mask_path)
-            return img, (read_alpha_valid(path) if use_alpha else None)
+            return img, (read_alpha_valid(path) if use_alpha and not as_tiff(path) else None)
         with ThreadPoolExecutor(depth) as ex:
             futs = {}
             for j in range(len(jobs)):
@@ -2483,7 +2562,7 @@ def main(argv=None):
                         futs[k] = ex.submit(load, jobs[k][1], job_masks[k])
                 img, valid = futs.pop(j).result()
                 scene_valids.append(valid)
-                if raster is not None or post:
+                if raster is not None or post or tiff_masks:
                     render_inputs.append((img, valid))
                 yield img
 
@@ -2495,6 +2574,12 @@ def main(argv=None):
 
     os.makedirs(mask_save_dir, exist_ok=True)
     os.makedirs(graph_save_dir, exist_ok=True)
+    if tiff_masks:
+        os.makedirs(os.path.join(output_dir, "mask_tif"), exist_ok=True)
+
+    def write_mask_tifs(img_id, scene, road_mask, itsc_mask):                    # GEOTIFF masks: the PNGs' pixels with the scene's geo tags
+        write_geotiff(os.path.join(output_dir, "mask_tif", f"{img_id}_road.tif"), road_mask, like=scene)
+        write_geotiff(os.path.join(output_dir, "mask_tif", f"{img_id}_itsc.tif"), itsc_mask, like=scene)
 
     def write_png(mask, name):
         # zlib level 1 = cv2.imwrite's default for PNG (the reference, inferencer.py:303-304); PIL's default level 6 takes ~50 ms per
@@ -2545,7 +2630,8 @@ def main(argv=None):
             attrs = widths
         write_graph(img_id, pred_nodes, pred_edges)
         if geojson_dir is not None:
-            write_geojson(os.path.join(geojson_dir, f"{img_id}.geojson"), pred_nodes, pred_edges, attrs, export_gt)
+            own_gt = img.geotransform if tiff is not None and tiff.georef and isinstance(img, TiffScene) else None      # GEOTIFF: the default
+            write_geojson(os.path.join(geojson_dir, f"{img_id}.geojson"), pred_nodes, pred_edges, attrs, export_gt if export_gt is not None else own_gt)
         return render_scene(img_id, img, valid, pred_nodes, pred_edges, itsc_mask.shape, gt_path) if raster is not None else (img_id, None)
 
     # the reference times infer_one_img per image (inferencer.py:292-296); the scenes are software-pipelined here (infer_imgs), so
@@ -2563,10 +2649,12 @@ def main(argv=None):
             start_seconds = time.time()
             res = next(results)
             total_inference_seconds += time.time() - start_seconds
-            scene_img, scene_valid = render_inputs.popleft() if raster is not None or post else (None, None)
+            scene_img, scene_valid = render_inputs.popleft() if raster is not None or post or tiff_masks else (None, None)
             if res is None:                      # non-zero rank of a tile-sharded run
                 continue
             pred_nodes, pred_edges, itsc_mask, road_mask = res
+            if tiff_masks and isinstance(scene_img, TiffScene):
+                pending.append(writer.submit(write_mask_tifs, img_id, scene_img, road_mask, itsc_mask))
             if post:                             # the graph's files follow the filter; the masks are what they were
                 rendered.append(writer.submit(finish_scene, img_id, scene_img, scene_valid, res, gt_path))
                 pending += [writer.submit(write_png, road_mask, f"{img_id}_road.png"), writer.submit(write_png, itsc_mask, f"{img_id}_itsc.png")]

@@ -921,6 +921,35 @@ class SAMRoad(nn.Module, GraphRasterOps):
                                             out.data_ptr(), self._stream(dev)), "srh_scene_pad")
         return out
 
+    # ---- scene level, GeoTIFF scenes (GEOTIFF) ---------------------------------------------------------------------------
+    @torch.no_grad()
+    def tiff_assemble(self, scene, flat, table, table_dev=None):
+        """The decompressed segments of a GeoTIFF -> its raster on the GPU (srh_tiff_assemble; the rule in sam_road_amd/geotiff.py): scene
+        a geotiff.TiffScene, flat the uint8 tensor of scene.segments() ON THE GPU (16-byte aligned), table its int64 [n, 7] table on the
+        HOST (a numpy array; checked again by the entry; table_dev: the same on the GPU where the caller has uploaded it) -> a NEW tensor [H, W, C] of the file's sample type, equal to
+        tiff_read_ref bit for bit.  One launch, no workspace of the library context, nothing read back."""
+        import numpy as np
+        dev = flat.device
+        ctx, _ = self._weights(dev)
+        dtypes = {"uint8": (torch.uint8, _lib.SRH_U8), "uint16": (torch.uint16, _lib.SRH_U16), "float32": (torch.float32, _lib.SRH_F32)}
+        if flat.dtype != torch.uint8 or flat.dim() != 1 or not flat.is_contiguous() or flat.numel() < 1:
+            raise ValueError(f"flat must be a contiguous uint8 [n] tensor, got {flat.dtype} {tuple(flat.shape)}")
+        if str(scene.dtype) not in dtypes:
+            raise ValueError(f"a GeoTIFF scene is uint8, uint16 or float32, got {scene.dtype}")
+        table = np.ascontiguousarray(table)
+        if table.dtype != np.int64 or table.ndim != 2 or table.shape[1] != 7 or table.shape[0] < 1:
+            raise ValueError(f"table must be int64 [n, 7], got {table.dtype} {table.shape}")
+        t_h = torch.from_numpy(table)
+        t_d = t_h.to(dev) if table_dev is None else table_dev
+        H, W, Cb = (int(v) for v in scene.shape)
+        t_dtype, code = dtypes[str(scene.dtype)]
+        out = torch.empty((H, W, Cb), dtype=t_dtype, device=dev)
+        with torch.cuda.device(dev):
+            ctx.check(ctx.lib.srh_tiff_assemble(ctx.handle, flat.data_ptr(), flat.numel(), t_h.data_ptr(), t_d.data_ptr(), int(table.shape[0]),
+                                                out.data_ptr(), H, W, Cb, code, int(scene.predictor), 0 if scene.little else 1, self._stream(dev)),
+                      "srh_tiff_assemble")
+        return out                                # the device table was made on this stream and is read on it
+
     # ---- scene level, 16-bit and multi-band scenes (SCENE_BANDS, DESIGN.md §6i) ---------------------------------------------------------
     @staticmethod
     def _bands_src(src, select):

@@ -56,6 +56,11 @@ The final map_decoder bias is lowered so that the random network yields sparse m
                                                                     # 16384-edge limit, and reports the device time of scene_aoi_fill alone for
                                                                     # each, pass 1's, the pipelined loop unmasked / keyed / with the identical
                                                                     # mask passed as valid in turn, and the host time of aoi_ref
+    python tools/scene_bench.py --geotiff {none,deflate,lzw} ... [--tiled] [--planar] [--geotiff-cache DIR]    # GEOTIFF: the scene as a u8 RGB
+                                                                    # and a 4-band uint16 GeoTIFF written with the test kit's writer; "geotiff" reports
+                                                                    # host decompress, upload, srh_tiff_assemble alone beside srh_scene_bands_apply,
+                                                                    # PIL and numpy on the same data, and the pipelined loop fed the TIFF with the
+                                                                    # key / fed the .npy of the same scene, alternated
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 tools/scene_bench.py    # N GPUs:
         tiles sharded over the ranks (RCCL: packed-weight broadcast, banded canvas reduce, point broadcast, vote gather);
         rank 0 prints ms/scene (max over ranks) and the per-rank stage times
@@ -946,6 +951,136 @@ def float_report(args, net, cfg, img, rng, iters=20):
     return rep
 
 
+def geotiff_report(args, net, cfg, img, rng, iters=20):
+    """--geotiff {none,deflate,lzw} ... [--tiled] [--planar] [--geotiff-cache DIR]: the scene as a u8 RGB and as a 4-band uint16 GeoTIFF
+    (bands 0..2 the synthetic RGB x 257, band 3 another blocky band; predictor 2 where compressed), written with the test kit's writer into
+    a temporary directory (or kept in DIR from one run to the next: the kit's LZW coder is plain Python).  Per file: host ms of open_scene +
+    segments() at the loader's thread count, upload ms of the flat array, device ms of srh_tiff_assemble alone with the bytes it moves, and
+    srh_scene_bands_apply on the same raster as the yardstick of a bandwidth-bound pass; the same file through PIL where PIL reads it and
+    the numpy steps of tiff_read_ref (cumsum, planar -> interleaved); the device raster against tiff_read_ref (the run ends if they
+    differ); ms per scene of the pipelined loop fed the TIFF with the key and fed the .npy of the same scene, both through the CLI's
+    three loader threads, three runs of 12 scenes each, alternated."""
+    import tempfile
+    from concurrent.futures import ThreadPoolExecutor
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+    import geotiff_kit as gk
+    import sam_road_amd.inferencer as inf
+    from sam_road_amd import Config
+    from sam_road_amd import geotiff as gt
+    from sam_road_amd.hostcpu import fill_threads
+    dev = next(net.parameters()).device
+    H, W = img.shape[:2]
+    u16 = np.empty((H, W, 4), np.uint16)
+    u16[..., :3] = img.astype(np.uint16) * 257
+    u16[..., 3] = np.kron(rng.integers(0, 65536, size=(H // 8, W // 8)), np.ones((8, 8))).astype(np.uint16)
+    rasters = {"u8_rgb": (img, {}), "u16_4band": (u16, dict(SCENE_BANDS={"select": [0, 1, 2], "stretch": [0, 65535]}))}
+    work = args.geotiff_cache or tempfile.mkdtemp(prefix="scene_bench_tif_")
+    os.makedirs(work, exist_ok=True)
+    threads = fill_threads()
+    report = {"loader_threads": 3, "decompress_threads": threads, "layout": ("tiles 512x512" if args.tiled else "strips") + (", planar" if args.planar else ""), "files": {}}
+
+    def device_ms(fn):
+        fn()
+        evs = []
+        for _ in range(iters):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fn()
+            e1.record()
+            evs.append((e0, e1))
+        torch.cuda.synchronize()
+        ms = sorted(a.elapsed_time(b) for a, b in evs)
+        return ms[len(ms) // 2], ms[0], ms[-1]
+
+    def row(ms, nbytes):
+        return {"device_us_median": round(1e3 * ms[0], 1), "device_us_min_max": [round(1e3 * ms[1], 1), round(1e3 * ms[2], 1)], "bytes": int(nbytes),
+                "GB_per_s_at_median": round(nbytes / ms[0] / 1e6, 1)}
+
+    def wall_ms(fn, n=3):
+        best = None
+        for _ in range(n):
+            t0 = time.perf_counter()
+            out = fn()
+            t = 1e3 * (time.perf_counter() - t0)
+            best = t if best is None or t < best else best
+        return round(best, 2), out
+
+    def fed(load, paths, c):                               # the CLI's loader: three threads decode ahead of the scene's turn
+        def gen():
+            with ThreadPoolExecutor(3) as ex:
+                futs = {}
+                for j in range(len(paths)):
+                    for k in range(j, min(j + 3, len(paths))):
+                        if k not in futs:
+                            futs[k] = ex.submit(load, paths[k])
+                    yield futs.pop(j).result()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in inf.infer_imgs(net, gen(), c):
+            pass
+        torch.cuda.synchronize()
+        return round(1e3 * (time.perf_counter() - t0) / len(paths), 2)
+
+    for rname, (raster, keys) in rasters.items():
+        npy = os.path.join(work, f"{rname}.npy")
+        np.save(npy, raster)
+        t_cumsum, _ = wall_ms(lambda: np.cumsum(raster, axis=1, dtype=raster.dtype))
+        planes = np.ascontiguousarray(raster.transpose(2, 0, 1))
+        t_inter, _ = wall_ms(lambda: np.ascontiguousarray(planes.transpose(1, 2, 0)))
+        report[f"{rname}_numpy_ms"] = {"cumsum": t_cumsum, "planar_to_interleaved": t_inter, "np_load": wall_ms(lambda: np.load(npy))[0]}
+        raster_d = torch.from_numpy(raster).to(dev)
+        lut = torch.zeros((3, 256 if raster.dtype == np.uint8 else 65536), dtype=torch.uint8, device=dev)
+        report[f"{rname}_yardstick_scene_bands_apply"] = row(device_ms(lambda: net.scene_bands_apply(raster_d, [0, 1, 2], lut)), raster.nbytes + 3 * H * W)
+        del raster_d
+        base = Config(dict(cfg, **keys))
+        keyed = Config(dict(base, GEOTIFF=True))
+        for comp in args.geotiff:
+            name = f"{rname}_{comp}_{'tiled' if args.tiled else 'strips'}{'_planar' if args.planar else ''}"
+            path = os.path.join(work, name + ".tif")
+            if not os.path.exists(path):
+                gk.write_tiff(path, raster, compression=comp, predictor=1 if comp == "none" else 2, planar=2 if args.planar else 1,
+                              tile=(512, 512) if args.tiled else None, rows_per_strip=None if args.tiled else 64, geo=gk.GEO)
+            sc = gt.open_scene(path)
+            rep = {"file_bytes": os.path.getsize(path), "segments": len(sc.offsets), "is_raster": bool(sc.is_raster)}
+            rep["host_ms_open_and_segments"], (flat, table) = wall_ms(lambda: gt.open_scene(path).segments(threads))
+            rep["host_ms_segments_one_thread"] = wall_ms(lambda: gt.open_scene(path).segments(1), 1)[0]
+            if raster.dtype == np.uint8 and not args.planar:
+                from PIL import Image
+                try:
+                    rep["host_ms_PIL_read"] = wall_ms(lambda: np.array(Image.open(path)))[0]
+                except Exception as e:
+                    rep["host_ms_PIL_read"] = f"PIL does not read it: {type(e).__name__}"
+
+            def upload():
+                t = torch.from_numpy(flat).to(dev)
+                torch.cuda.synchronize()
+                return t
+            rep["upload_ms_pageable"], flat_d = wall_ms(upload)
+            rep["flat_bytes"] = int(flat.size)
+            if not sc.is_raster:
+                table_d = torch.from_numpy(table).to(dev)
+                got = net.tiff_assemble(sc, flat_d, table, table_d)
+                if not gk.same_bits(got.cpu().numpy(), raster):
+                    raise SystemExit(f"{name}: the device raster differs from the source")
+                rep["tiff_assemble"] = row(device_ms(lambda: net.tiff_assemble(sc, flat_d, table, table_d)), flat.size + raster.nbytes)
+            del flat_d
+            report["files"][name] = rep
+            if args.no_pipelined:
+                continue
+            load_tif = lambda p: gt.open_scene(p).load(threads)
+            fed(load_tif, [path] * 3, keyed), fed(np.load, [npy] * 3, base)
+            runs = {"tiff_with_the_key": [], "npy_of_the_same_scene": []}
+            for _ in range(3):
+                runs["tiff_with_the_key"].append(fed(load_tif, [path] * 12, keyed))
+                runs["npy_of_the_same_scene"].append(fed(np.load, [npy] * 12, base))
+            rep["pipelined_ms_per_scene_runs_of_12_alternated"] = runs
+            a = inf.infer_one_img(net, gt.open_scene(path), keyed)
+            b = inf.infer_one_img(net, raster, base)
+            rep["keyed_equals_the_array_run"] = all(np.array_equal(x, y) for x, y in zip(a, b))
+            rep["graph_points"], rep["edges"] = int(a[0].shape[0]), int(a[1].shape[0])
+    return report
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--bias", type=float, default=-2.2)
@@ -995,6 +1130,12 @@ def main():
                          "the three launches, the pipelined loop with a fixed range and with a percentile stretch and the host reference are timed")
     ap.add_argument("--float-range", nargs=2, type=float, default=None, metavar=("LO", "HI"), help="with --float: the fixed range (default 0 1)")
     ap.add_argument("--float-percentile", nargs=2, type=float, default=None, metavar=("P", "Q"), help="with --float: the percentiles (default 2 98)")
+    ap.add_argument("--geotiff", nargs="+", default=None, choices=("none", "deflate", "lzw"), metavar="COMP",
+                    help="GEOTIFF: write the scene to temporary TIFFs (u8 RGB and 4-band uint16) with the test kit's writer, time the decode on host and "
+                         "device and run the pipelined loop on them against the .npy of the same scenes")
+    ap.add_argument("--tiled", action="store_true", help="with --geotiff: 512 x 512 tiles instead of strips of 64 rows")
+    ap.add_argument("--planar", action="store_true", help="with --geotiff: PlanarConfiguration 2")
+    ap.add_argument("--geotiff-cache", default=None, metavar="DIR", help="with --geotiff: keep the files in DIR and reuse those that are there")
     ap.add_argument("--no-pipelined", action="store_true", help="skip the infer_imgs runs (12- and 48-scene streams)")
     ap.add_argument("--patch", type=int, default=512, metavar="P", help="PATCH_SIZE (default 512)")
     ap.add_argument("--margin", type=int, default=64, metavar="M", help="SAMPLE_MARGIN (default 64)")
@@ -1112,6 +1253,11 @@ def main():
         if world > 1 or args.scenes is not None or args.valid_frac is not None or args.scale is not None or args.bands is not None:
             ap.error("--float C times one unmasked float32 scene on one GPU (not with --scenes, --valid-frac, --scale or --bands)")
         print(json.dumps({"scene": f"synthetic {H}x{W} float32 x {args.float}", "infer_batch_size": args.batch, "scene_float": float_report(args, net, cfg, img, rng)}))
+        return
+    if args.geotiff is not None:
+        if world > 1 or args.scenes is not None or args.valid_frac is not None or args.scale is not None or args.bands is not None:
+            ap.error("--geotiff times unmasked scenes on one GPU (not with --scenes, --valid-frac, --scale or --bands)")
+        print(json.dumps({"scene": f"synthetic {H}x{W} as GeoTIFFs", "infer_batch_size": args.batch, "geotiff": geotiff_report(args, net, cfg, img, rng)}))
         return
     bands_report = None
     if args.bands is not None:
