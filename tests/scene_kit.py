@@ -413,16 +413,16 @@ def compare_worlds(one, many, shapes, kinds, must_be_identical):
 
 
 # ---- the CLI harness --------------------------------------------------------------------------------------------------------------
-def run_cli(inf, net, tmp_path, monkeypatch, name, cfg, images, *argv):
-    """inf.main in tmp_path with the model replaced by net: writes cfg as {name}.yaml, runs --output_dir name on the image files, reads
+def run_cli(cli, net, tmp_path, monkeypatch, name, cfg, images, *argv):
+    """cli.main (sam_road_amd.cli, the module whose _build_net it replaces) in tmp_path with the model replaced by net: writes cfg as {name}.yaml, runs --output_dir name on the image files, reads
     the results back: {image stem: (itsc mask, road mask, graph, the saved config)}."""
     import yaml
     from PIL import Image
     monkeypatch.chdir(tmp_path)
-    monkeypatch.setattr(inf, "_build_net", lambda config, checkpoint, device: net)
+    monkeypatch.setattr(cli, "_build_net", lambda config, checkpoint, device: net)
     with open(f"{name}.yaml", "w") as f:
         yaml.safe_dump(dict(cfg, DATASET="cityscale"), f)
-    inf.main(["--config", f"{name}.yaml", "--checkpoint", "none", "--device", "cpu", "--output_dir", name, *argv, "--images", *images])
+    cli.main(["--config", f"{name}.yaml", "--checkpoint", "none", "--device", "cpu", "--output_dir", name, *argv, "--images", *images])
     saved = yaml.safe_load(open(f"save/{name}/config.yaml"))
     out = {}
     for stem in [os.path.splitext(os.path.basename(p))[0] for p in images]:

@@ -179,7 +179,7 @@ def _cli_rank(world, rank, port, work, out):
     try:
         os.environ.update(RANK=str(rank), LOCAL_RANK=str(rank), WORLD_SIZE=str(world), MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
         os.chdir(work)
-        from sam_road_amd import inferencer as inf
+        from sam_road_amd import cli, inferencer as inf
         seen = []
 
         def fake_infer_imgs(net, imgs, config, device=None, tile_sharded=None, pipelined=None):
@@ -189,7 +189,7 @@ def _cli_rank(world, rank, port, work, out):
                 nodes = np.array([[1, 2], [3, 4], [int(im[0, 0, 0]), 7]], dtype=np.int64)
                 yield nodes, np.array([[0, 1], [1, 2]], dtype=np.int64), im[:, :, 0].copy(), im[:, :, 1].copy()
         inf.infer_imgs = fake_infer_imgs
-        inf._build_net = lambda config, checkpoint, device: None
+        cli._build_net = lambda config, checkpoint, device: None
         inf.main(["--config", "cfg.yaml", "--checkpoint", "ckpt.ckpt", "--output_dir", "run2", "--device", "cpu"])
         out.put((rank, seen))
     except Exception:  # pragma: no cover

@@ -16,6 +16,7 @@ import torch
 
 from sam_road_amd import Config
 from sam_road_amd import edge_support as es
+from sam_road_amd import cli
 from sam_road_amd import inferencer as inf
 from sam_road_amd.aoi import aoi_key_of
 from sam_road_amd.edge_support import (MAX_COVERED, EdgeSupport, edge_attrs, edge_keep, edge_support_key, edge_support_key_of, edge_support_override,
@@ -207,7 +208,7 @@ def test_every_refusal_is_a_value_error_before_the_model_is_touched(tmp_path, mo
 
     def untouchable(*a, **k):
         raise AssertionError("the model was built")
-    monkeypatch.setattr(inf, "_build_net", untouchable)
+    monkeypatch.setattr(cli, "_build_net", untouchable)
     cases = [(b, ()) for b in BAD_KEYS[:6]] + [(None, ("--edge-support-width", "0")), (None, ("--edge-support-width", "256", "--edge-min-on", "0.5")),
                                                (None, ("--edge-on", "1.5", "--edge-min-on", "0.5")), (None, ("--edge-min-mean", "-1")), (None, ("--edge-min-on", "2")),
                                                (None, ("--edge-max-invalid", "-1")), (None, ("--edge-support-width", "3")), (None, ("--drop-isolated-nodes",)),
@@ -288,16 +289,16 @@ def test_cli_without_the_key_is_the_run_it_was_and_with_it_writes_the_filtered_g
     np.save("va.npy", valid)
 
     # without the key: no call, and the files of a run in which the new code is out of the way, byte for byte
-    plain = run_cli(inf, net, tmp_path, monkeypatch, "plain", CFG, ["a.png"], "--viz")
+    plain = run_cli(cli, net, tmp_path, monkeypatch, "plain", CFG, ["a.png"], "--viz")
     assert not ek.support_calls(net) and es.apply(None, plain, net=None) == (plain, None)
     assert _files("save/plain") == ["config.yaml", "graph/a.p", "inference_time.txt", "mask/a_itsc.png", "mask/a_road.png", "viz/a.png"]
     with monkeypatch.context() as mp:
         def never(*a, **k):
             raise AssertionError("the new code ran")
-        mp.setattr(inf, "edge_support_key", lambda *a, **k: None)
-        mp.setattr(inf, "apply_edge_support", never)
-        mp.setattr(inf, "write_geojson", never)
-        run_cli(inf, net, tmp_path, mp, "bypassed", CFG, ["a.png"], "--viz")
+        mp.setattr(cli, "edge_support_key", lambda *a, **k: None)
+        mp.setattr(cli, "apply_edge_support", never)
+        mp.setattr(cli, "write_geojson", never)
+        run_cli(cli, net, tmp_path, mp, "bypassed", CFG, ["a.png"], "--viz")
     assert _files("save/bypassed") == _files("save/plain")
     for f in _files("save/plain"):
         if f != "inference_time.txt":
@@ -318,7 +319,7 @@ def test_cli_without_the_key_is_the_run_it_was_and_with_it_writes_the_filtered_g
     assert ek.support_calls(net) == [("graph_edge_stats", (H, W), 1, 127, True)]
     net.calls.clear()
     gt = [10.0, 2.0, 0.0, 500.0, 0.0, -2.0]
-    got = run_cli(inf, net, tmp_path, monkeypatch, "kept", CFG, ["a.png"], "--edge-min-on", repr(f_med), "--drop-isolated-nodes", "--viz", "--graph-geojson",
+    got = run_cli(cli, net, tmp_path, monkeypatch, "kept", CFG, ["a.png"], "--edge-min-on", repr(f_med), "--drop-isolated-nodes", "--viz", "--graph-geojson",
                   "--geotransform", *[str(g) for g in gt], "--valid-masks", "va.npy")["a"]
     assert got[3]["EDGE_SUPPORT"] == {"min_on": f_med, "drop_isolated": True} and len(ek.support_calls(net)) == 1
     assert _files("save/kept") == sorted(_files("save/plain") + ["graph_geojson/a.geojson"])
@@ -330,11 +331,11 @@ def test_cli_without_the_key_is_the_run_it_was_and_with_it_writes_the_filtered_g
     assert len(doc["features"]) == want_edges.shape[0] and all(f["properties"]["on_frac"] >= f_med for f in doc["features"])
     # --graph-geojson alone: the unfiltered graph, geometry only, in pixel coordinates; no call
     net.calls.clear()
-    run_cli(inf, net, tmp_path, monkeypatch, "export", CFG, ["a.png"], "--graph-geojson", "--valid-masks", "va.npy")
+    run_cli(cli, net, tmp_path, monkeypatch, "export", CFG, ["a.png"], "--graph-geojson", "--valid-masks", "va.npy")
     assert not ek.support_calls(net)
     assert json.load(open("save/export/graph_geojson/a.geojson")) == json.loads(json.dumps(graph_geojson(nodes, edges)))
     # a key without a condition and --graph-geojson: attributes, nothing filtered
-    run_cli(inf, net, tmp_path, monkeypatch, "attrs", CFG, ["a.png"], "--graph-geojson", "--edge-support-width", "3", "--geotransform", *[str(g) for g in gt],
+    run_cli(cli, net, tmp_path, monkeypatch, "attrs", CFG, ["a.png"], "--graph-geojson", "--edge-support-width", "3", "--geotransform", *[str(g) for g in gt],
             "--valid-masks", "va.npy")
     want = graph_geojson(nodes, edges, edge_attrs(nodes, edges, edge_support_ref(nodes, edges, road, 3, 127, valid)), gt)
     assert json.load(open("save/attrs/graph_geojson/a.geojson")) == json.loads(json.dumps(want))

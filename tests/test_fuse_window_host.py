@@ -13,6 +13,7 @@ import pytest
 import torch
 
 from sam_road_amd import Config, _lib
+from sam_road_amd import cli
 from sam_road_amd import inferencer as inf
 from sam_road_amd.inferencer import infer_imgs, infer_one_img
 
@@ -244,7 +245,7 @@ def test_cli_takes_the_key_and_the_flag(tmp_path, monkeypatch, standin):
     plain, hann = cfg, dict(cfg, FUSE_WINDOW="hann")
 
     def run(name, config, *argv):
-        return run_cli(inf, net, tmp_path, monkeypatch, name, config, ["rgb.png"], *argv)["rgb"]
+        return run_cli(cli, net, tmp_path, monkeypatch, name, config, ["rgb.png"], *argv)["rgb"]
 
     want = {k: infer_one_img(net, img, Config(dict(cfg, **({} if k == "uniform" else dict(FUSE_WINDOW=k)))), device="cpu")
             for k in ("uniform", "hann", "triangle")}
@@ -266,6 +267,6 @@ def test_cli_takes_the_key_and_the_flag(tmp_path, monkeypatch, standin):
                   "--fuse-window", "gauss"])
     with open("bad.yaml", "w") as f:
         yaml.safe_dump(dict(cfg, DATASET="cityscale", FUSE_WINDOW="gauss"), f)
-    monkeypatch.setattr(inf, "_build_net", lambda *a: (_ for _ in ()).throw(AssertionError("the model was built")))
+    monkeypatch.setattr(cli, "_build_net", lambda *a: (_ for _ in ()).throw(AssertionError("the model was built")))
     with pytest.raises(ValueError, match="one of"):
         inf.main(["--config", "bad.yaml", "--checkpoint", "none", "--device", "cpu", "--output_dir", "f", "--images", "rgb.png"])

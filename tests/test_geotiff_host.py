@@ -17,6 +17,7 @@ from PIL import Image
 
 from sam_road_amd import Config
 from sam_road_amd import geotiff as gt
+from sam_road_amd import cli
 from sam_road_amd import inferencer as inf
 from sam_road_amd.edge_support import graph_geojson
 from sam_road_amd.inferencer import infer_imgs, infer_one_img
@@ -281,21 +282,21 @@ def test_nodata_from_files(tmp_path):
     a = gk.sample((20, 30, 4), "uint16", 1)
     f = gk.sample((20, 30, 2), "float32", 1)
     mk = lambda name, arr, nd: (lambda p: (p, gt.open_scene(p)))(gk.write_tiff(str(tmp_path / name), arr, nodata=nd))
-    assert inf._nodata_from_files(dict([mk("a.tif", a, 0), mk("b.tif", a, "0.0")])) == (0, False)
-    assert inf._nodata_from_files(dict([mk("a.tif", f, -9999), mk("b.tif", f, "-9999.0")])) == (-9999.0, True)
-    v, is_float = inf._nodata_from_files(dict([mk("a.tif", f, "nan"), mk("b.tif", f, "nan")]))
+    assert cli._nodata_from_files(dict([mk("a.tif", a, 0), mk("b.tif", a, "0.0")])) == (0, False)
+    assert cli._nodata_from_files(dict([mk("a.tif", f, -9999), mk("b.tif", f, "-9999.0")])) == (-9999.0, True)
+    v, is_float = cli._nodata_from_files(dict([mk("a.tif", f, "nan"), mk("b.tif", f, "nan")]))
     assert is_float and v != v
     with pytest.raises(ValueError, match=r"a\.tif states 0\.0 and .*b\.tif states 65535\.0"):
-        inf._nodata_from_files(dict([mk("a.tif", a, 0), mk("b.tif", a, 65535)]))
+        cli._nodata_from_files(dict([mk("a.tif", a, 0), mk("b.tif", a, 65535)]))
     with pytest.raises(ValueError, match=r"b\.tif.*no nodata"):
-        inf._nodata_from_files(dict([mk("a.tif", a, 0), mk("b.tif", a, None)]))
+        cli._nodata_from_files(dict([mk("a.tif", a, 0), mk("b.tif", a, None)]))
     with pytest.raises(ValueError, match="integer and float"):
-        inf._nodata_from_files(dict([mk("a.tif", a, 0), mk("b.tif", f, 0)]))
+        cli._nodata_from_files(dict([mk("a.tif", a, 0), mk("b.tif", f, 0)]))
     for nd in (-1, 65536, 0.5):
         with pytest.raises(ValueError, match="no level"):
-            inf._nodata_from_files(dict([mk("a.tif", a, nd)]))
+            cli._nodata_from_files(dict([mk("a.tif", a, nd)]))
     with pytest.raises(ValueError, match="--images"):
-        inf._nodata_from_files({})
+        cli._nodata_from_files({})
 
 
 # ---- 6. the whole loop on the CPU stand-in ----------------------------------------------------------------------------------------------------------
@@ -381,14 +382,14 @@ def test_cli(tmp_path, monkeypatch, u8_scene):
     monkeypatch.chdir(tmp_path)
     Image.fromarray(u8_scene).save("p.tif")                   # an 8-bit RGB TIFF, as PIL writes it
     # without the key the .tif goes through PIL as before, and the new code is out of the way: the same files, byte for byte
-    plain = run_cli(inf, net, tmp_path, monkeypatch, "plain", E2E_CFG, ["p.tif"], "--graph-geojson")
+    plain = run_cli(cli, net, tmp_path, monkeypatch, "plain", E2E_CFG, ["p.tif"], "--graph-geojson")
     assert not gk.tiff_calls(net) and "GEOTIFF" not in plain["p"][3]
     with monkeypatch.context() as mp:
         def never(*a, **k):
             raise AssertionError("the new code ran")
         for fn in ("open_scene", "write_geotiff", "_nodata_from_files"):
-            mp.setattr(inf, fn, never)
-        run_cli(inf, net, tmp_path, mp, "bypassed", E2E_CFG, ["p.tif"], "--graph-geojson")
+            mp.setattr(cli, fn, never)
+        run_cli(cli, net, tmp_path, mp, "bypassed", E2E_CFG, ["p.tif"], "--graph-geojson")
     assert _files("save/plain") == _files("save/bypassed") == ["config.yaml", "graph/p.p", "graph_geojson/p.geojson", "inference_time.txt", "mask/p_itsc.png", "mask/p_road.png"]
     for f in _files("save/plain"):
         if f != "inference_time.txt":
@@ -400,7 +401,7 @@ def test_cli(tmp_path, monkeypatch, u8_scene):
     gk.write_tiff("a.tif", raw, compression="lzw", predictor=2, tile=(64, 64), geo=gk.GEO, nodata=0)
     argv = ["--geotiff", "--bands", ",".join(str(b) for b in SELECT), "--stretch-percentile", "2", "98", "--nodata-from-file", "--graph-geojson", "--mask-geotiff"]
     net.calls.clear()
-    got = run_cli(inf, net, tmp_path, monkeypatch, "geo", E2E_CFG, ["a.tif"], *argv)["a"]
+    got = run_cli(cli, net, tmp_path, monkeypatch, "geo", E2E_CFG, ["a.tif"], *argv)["a"]
     assert got[3]["GEOTIFF"] == {"nodata": "file", "masks": True} and got[3]["SCENE_NODATA"] == {"value": 0} and len(gk.tiff_calls(net)) == 1
     assert _files("save/geo") == ["config.yaml", "graph/a.p", "graph_geojson/a.geojson", "inference_time.txt", "mask/a_itsc.png", "mask/a_road.png",
                                   "mask_tif/a_itsc.tif", "mask_tif/a_road.tif"]
@@ -423,14 +424,14 @@ def test_cli(tmp_path, monkeypatch, u8_scene):
         back = gt.open_scene(f"save/geo/mask_tif/a_{kind}.tif")
         assert back.geo_tags == src.geo_tags and back.geotransform == gk.GEO_TRANSFORM
     # an explicit --geotransform wins; georef: false switches the default off
-    run_cli(inf, net, tmp_path, monkeypatch, "explicit", E2E_CFG, ["a.tif"], *argv[:-1], "--geotransform", "1", "2", "0", "3", "0", "4")
+    run_cli(cli, net, tmp_path, monkeypatch, "explicit", E2E_CFG, ["a.tif"], *argv[:-1], "--geotransform", "1", "2", "0", "3", "0", "4")
     assert json.load(open("save/explicit/graph_geojson/a.geojson")) == json.loads(json.dumps(graph_geojson(nodes, edges, None, (1.0, 2.0, 0.0, 3.0, 0.0, 4.0))))
     assert "mask_tif/a_road.tif" not in _files("save/explicit")
-    run_cli(inf, net, tmp_path, monkeypatch, "pixels", dict(E2E_CFG, GEOTIFF={"georef": False}), ["a.tif"], *argv[1:-1])
+    run_cli(cli, net, tmp_path, monkeypatch, "pixels", dict(E2E_CFG, GEOTIFF={"georef": False}), ["a.tif"], *argv[1:-1])
     assert json.load(open("save/pixels/graph_geojson/a.geojson")) == json.loads(json.dumps(graph_geojson(nodes, edges)))
     # scenes that state different nodata values: refused before the model is built
     gk.write_tiff("b.tif", raw, geo=gk.GEO, nodata=65535)
-    monkeypatch.setattr(inf, "_build_net", lambda *a, **k: (_ for _ in ()).throw(AssertionError("the model was built")))
+    monkeypatch.setattr(cli, "_build_net", lambda *a, **k: (_ for _ in ()).throw(AssertionError("the model was built")))
     with open("geo.yaml") as f:
         assert f.read()
     with pytest.raises(ValueError, match=r"a\.tif states 0\.0 and b\.tif states 65535\.0"):
@@ -452,13 +453,13 @@ def test_cli_area_of_interest_takes_the_scene_transform(tmp_path, monkeypatch, u
     xy = lambda c, r: [g[0] + c * g[1] + r * g[2], g[3] + c * g[4] + r * g[5]]
     with open("aoi.geojson", "w") as f:
         json.dump({"type": "Polygon", "coordinates": [[xy(20, 30), xy(330, 30), xy(330, 300), xy(20, 300), xy(20, 30)]]}, f)
-    own = run_cli(inf, net, tmp_path, monkeypatch, "own", E2E_CFG, ["a.tif"], "--geotiff", "--aoi", "aoi.geojson")["a"]
-    stated = run_cli(inf, net, tmp_path, monkeypatch, "stated", E2E_CFG, ["a.tif"], "--geotiff", "--aoi", "aoi.geojson", "--aoi-geotransform", *[repr(v) for v in g])["a"]
+    own = run_cli(cli, net, tmp_path, monkeypatch, "own", E2E_CFG, ["a.tif"], "--geotiff", "--aoi", "aoi.geojson")["a"]
+    stated = run_cli(cli, net, tmp_path, monkeypatch, "stated", E2E_CFG, ["a.tif"], "--geotiff", "--aoi", "aoi.geojson", "--aoi-geotransform", *[repr(v) for v in g])["a"]
     assert np.array_equal(own[0], stated[0]) and np.array_equal(own[1], stated[1]) and own[2] == stated[2]
     assert own[1][30:300, 20:330].any() and not own[1][:30].any() and not own[1][:, 330:].any()
     assert own[3]["SCENE_AOI"]["geotransform"] == list(g)
     with pytest.raises(ValueError, match="SCENE_AOI"):        # georef off: the polygons are pixels again, and these are far outside
-        run_cli(inf, net, tmp_path, monkeypatch, "off", dict(E2E_CFG, GEOTIFF={"georef": False}), ["a.tif"], "--aoi", "aoi.geojson")
+        run_cli(cli, net, tmp_path, monkeypatch, "off", dict(E2E_CFG, GEOTIFF={"georef": False}), ["a.tif"], "--aoi", "aoi.geojson")
 
 
 # ---- 7. the kernel's own code, on the CPU ---------------------------------------------------------------------------------------------------------

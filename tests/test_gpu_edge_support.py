@@ -220,7 +220,7 @@ def test_apply_and_the_cli_end_to_end(pair, tmp_path, monkeypatch):
     --graph-geojson writes the filtered pickle, the viz and the GeoJSON of exactly that graph, and leaves the masks as they were."""
     from PIL import Image
     from sam_road_amd import Config
-    from sam_road_amd import inferencer as inf
+    from sam_road_amd import cli, inferencer as inf
     _, net = pair
     monkeypatch.chdir(tmp_path)
     H, W = 401, 523
@@ -249,8 +249,8 @@ def test_apply_and_the_cli_end_to_end(pair, tmp_path, monkeypatch):
         key = edge_support_key(Config(cfg, EDGE_SUPPORT={"min_on": f_med, "drop_isolated": True}))
         (want_nodes, want_edges, _, _), want_attrs = es.apply_ref(key, res, valid)
         assert 0 < want_edges.shape[0] < edges.shape[0]                              # at least one edge dropped, at least one kept
-        before = run_cli(inf, net, tmp_path, monkeypatch, "before", cfg, ["rgb.png"], "--device", "cuda", "--valid-masks", "valid.npy")["rgb"]
-        got = run_cli(inf, net, tmp_path, monkeypatch, "kept", cfg, ["rgb.png"], "--device", "cuda", "--valid-masks", "valid.npy", "--edge-min-on", repr(f_med),
+        before = run_cli(cli, net, tmp_path, monkeypatch, "before", cfg, ["rgb.png"], "--device", "cuda", "--valid-masks", "valid.npy")["rgb"]
+        got = run_cli(cli, net, tmp_path, monkeypatch, "kept", cfg, ["rgb.png"], "--device", "cuda", "--valid-masks", "valid.npy", "--edge-min-on", repr(f_med),
                       "--drop-isolated-nodes", "--viz", "--graph-geojson")["rgb"]
     plain_files = ["config.yaml", "graph/rgb.p", "inference_time.txt", "mask/rgb_itsc.png", "mask/rgb_road.png"]
     assert _files("save/before") == plain_files and _files("save/kept") == sorted(plain_files + ["viz/rgb.png", "graph_geojson/rgb.geojson"])

@@ -300,7 +300,7 @@ def test_cli_end_to_end(pair, tmp_path, monkeypatch):
     the same run without the flags writes exactly the files it wrote before, with the same bytes."""
     from PIL import Image
     from sam_road_amd import Config
-    from sam_road_amd import inferencer as inf
+    from sam_road_amd import cli, inferencer as inf
     from sam_road_amd.formats import convert_to_sat2graph_format
     _, net = pair
     monkeypatch.chdir(tmp_path)
@@ -317,8 +317,8 @@ def test_cli_end_to_end(pair, tmp_path, monkeypatch):
             base = dict(CFG, INFER_PATCHES_PER_EDGE=4, **extra)
             _, _, kp0, road0 = inf.infer_one_img(net, img, Config(base))
             cfg = dict(base, **thresholds(kp0, road0))
-            before = run_cli(inf, net, tmp_path, monkeypatch, f"{name}_before", cfg, ["rgb.png"], "--device", "cuda")["rgb"]
-            got = run_cli(inf, net, tmp_path, monkeypatch, name, cfg, ["rgb.png"], *flags)["rgb"]
+            before = run_cli(cli, net, tmp_path, monkeypatch, f"{name}_before", cfg, ["rgb.png"], "--device", "cuda")["rgb"]
+            got = run_cli(cli, net, tmp_path, monkeypatch, name, cfg, ["rgb.png"], *flags)["rgb"]
         plain_files = ["config.yaml", "graph/rgb.p", "inference_time.txt", "mask/rgb_itsc.png", "mask/rgb_road.png"]
         assert _files(f"save/{name}_before") == plain_files
         assert _files(f"save/{name}") == sorted(plain_files + ["viz/rgb.png", "graph_mask/rgb.png", "diff/rgb.png", "diff/metrics.json"])

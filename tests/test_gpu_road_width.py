@@ -333,7 +333,7 @@ def test_the_cli_end_to_end(pair, tmp_path, monkeypatch):
     out of the way, byte for byte."""
     from PIL import Image
     from sam_road_amd import Config
-    from sam_road_amd import inferencer as inf
+    from sam_road_amd import cli, inferencer as inf
     _, net = pair
     monkeypatch.chdir(tmp_path)
     H, W = 401, 523
@@ -344,14 +344,14 @@ def test_the_cli_end_to_end(pair, tmp_path, monkeypatch):
         base = dict(CFG, INFER_PATCHES_PER_EDGE=4)
         _, _, kp0, road0 = inf.infer_one_img(net, img, Config(base))
         cfg = dict(base, **thresholds(kp0, road0))
-        plain = run_cli(inf, net, tmp_path, monkeypatch, "plain", cfg, ["rgb.png"], "--device", "cuda")["rgb"]
+        plain = run_cli(cli, net, tmp_path, monkeypatch, "plain", cfg, ["rgb.png"], "--device", "cuda")["rgb"]
         with monkeypatch.context() as mp:
             def never(*a, **k):
                 raise AssertionError("the new code ran")
-            mp.setattr(inf, "road_width_key", lambda *a, **k: None)
-            mp.setattr(inf, "apply_road_width", never)
-            run_cli(inf, net, tmp_path, mp, "bypassed", cfg, ["rgb.png"], "--device", "cuda")
-        got = run_cli(inf, net, tmp_path, monkeypatch, "width", cfg, ["rgb.png"], "--device", "cuda", "--road-width", "--graph-geojson")["rgb"]
+            mp.setattr(cli, "road_width_key", lambda *a, **k: None)
+            mp.setattr(cli, "apply_road_width", never)
+            run_cli(cli, net, tmp_path, mp, "bypassed", cfg, ["rgb.png"], "--device", "cuda")
+        got = run_cli(cli, net, tmp_path, monkeypatch, "width", cfg, ["rgb.png"], "--device", "cuda", "--road-width", "--graph-geojson")["rgb"]
     plain_files = ["config.yaml", "graph/rgb.p", "inference_time.txt", "mask/rgb_itsc.png", "mask/rgb_road.png"]
     assert _files("save/plain") == _files("save/bypassed") == plain_files and _files("save/width") == sorted(plain_files + ["graph_geojson/rgb.geojson"])
     for f in plain_files:

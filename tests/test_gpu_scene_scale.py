@@ -266,7 +266,7 @@ def test_infer_imgs_pipelined_equals_infer_one_img(pair):
 def test_cli_writes_scene_sized_masks_and_scene_coordinates(pair, tmp_path, monkeypatch):
     from PIL import Image
     from sam_road_amd import Config
-    from sam_road_amd import inferencer as inf
+    from sam_road_amd import cli
     from sam_road_amd.formats import convert_to_sat2graph_format
     _, net = pair
     img = rect_scene(600, 640, 48)
@@ -277,7 +277,7 @@ def test_cli_writes_scene_sized_masks_and_scene_coordinates(pair, tmp_path, monk
         _, _, kp0, road0 = infer_one_img_at(net, img, dict(CFG, SCENE_SCALE=[1, 2]))
         cfg = dict(CFG, **_thresholds(kp0, road0))
         want = infer_one_img_at(net, img, dict(cfg, SCENE_SCALE=[1, 2]))
-        got = run_cli(inf, net, tmp_path, monkeypatch, "scale", cfg, ["rgb.png"], "--device", "cuda", "--scene-scale", "1", "2")["rgb"]
+        got = run_cli(cli, net, tmp_path, monkeypatch, "scale", cfg, ["rgb.png"], "--device", "cuda", "--scene-scale", "1", "2")["rgb"]
     assert got[0].shape == got[1].shape == (600, 640) and got[3]["SCENE_SCALE"] == [1, 2]
     np.testing.assert_array_equal(got[0], want[2])
     np.testing.assert_array_equal(got[1], want[3])

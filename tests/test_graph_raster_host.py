@@ -14,6 +14,7 @@ import pytest
 import torch
 
 from sam_road_amd import Config
+from sam_road_amd import cli
 from sam_road_amd import inferencer as inf
 from sam_road_amd.formats import convert_to_sat2graph_format
 from sam_road_amd.graph_raster import (EDGE_COLOR, MAX_COORD, MAX_SPAN, NODE_COLOR, VIZ_DEFAULT, GraphRaster, VizStyle, check_graph, compare_ref,
@@ -205,7 +206,7 @@ def test_every_refusal_is_a_value_error_before_the_model_is_touched(tmp_path, mo
 
     def untouchable(*a, **k):
         raise AssertionError("the model was built")
-    monkeypatch.setattr(inf, "_build_net", untouchable)
+    monkeypatch.setattr(cli, "_build_net", untouchable)
     for n, (bad, argv) in enumerate([(b, ()) for b in BAD_KEYS[:8]] + [(None, ("--graph-mask", "0")), (None, ("--graph-mask", "128")), (None, ("--diff", "3", "2")),
                                                                         (None, ("--diff", "1")), (None, ("--diff", "0", "5")), ({"viz": {"width": 0}}, ("--viz",)),
                                                                         (None, ("--diff",))]):     # the last: --images without --gt-graphs
@@ -267,10 +268,10 @@ def test_cli_writes_the_renders_of_the_returned_graph(tmp_path, monkeypatch):
     sp = read_gt_graph("gt.p", spacenet=True)[0]
     assert sorted(map(tuple, sp.tolist())) == sorted((400 - r, c) for r, c in GT[0].tolist())              # inferencer.py:289-292
 
-    plain = run_cli(inf, net, tmp_path, monkeypatch, "plain", CFG, ["a.png", "b.png"])
+    plain = run_cli(cli, net, tmp_path, monkeypatch, "plain", CFG, ["a.png", "b.png"])
     assert not gk.raster_calls(net)
     assert _files("save/plain") == ["config.yaml", "graph/a.p", "graph/b.p", "inference_time.txt", "mask/a_itsc.png", "mask/a_road.png", "mask/b_itsc.png", "mask/b_road.png"]
-    got = run_cli(inf, net, tmp_path, monkeypatch, "all", CFG, ["a.png", "b.png"], "--viz", "--graph-mask", "3", "--diff", "--gt-graphs", "gt.p", "-",
+    got = run_cli(cli, net, tmp_path, monkeypatch, "all", CFG, ["a.png", "b.png"], "--viz", "--graph-mask", "3", "--diff", "--gt-graphs", "gt.p", "-",
                   "--valid-masks", "va.npy", "-")
     assert got["a"][3]["GRAPH_RASTER"] == {"viz": True, "mask": {"radius": 3}, "diff": True}
     assert _files("save/all") == sorted(_files("save/plain") + ["viz/a.png", "viz/b.png", "graph_mask/a.png", "graph_mask/b.png", "diff/a.png", "diff/metrics.json"])
@@ -291,7 +292,7 @@ def test_cli_writes_the_renders_of_the_returned_graph(tmp_path, monkeypatch):
     # the key in the config alone does the same; a flag replaces its part
     net.calls.clear()
     keyed = dict(CFG, GRAPH_RASTER={"viz": {"width": 2, "mark": "square", "radius": 1, "edge_color": [9, 8, 7]}, "mask": 9})
-    got = run_cli(inf, net, tmp_path, monkeypatch, "keyed", keyed, ["a.png"], "--graph-mask", "2")
+    got = run_cli(cli, net, tmp_path, monkeypatch, "keyed", keyed, ["a.png"], "--graph-mask", "2")
     assert got["a"][3]["GRAPH_RASTER"]["mask"] == {"radius": 2} and _files("save/keyed")[-1] == "viz/a.png" and "graph_mask/a.png" in _files("save/keyed")
     nodes, edges = read_gt_graph("save/keyed/graph/a.p")
     np.testing.assert_array_equal(np.array(Image.open("save/keyed/viz/a.png")), composite_ref(graph_raster_ref(nodes, edges, (H, W), 2, "square", 1), a, (9, 8, 7)))

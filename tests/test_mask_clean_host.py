@@ -14,6 +14,7 @@ import pytest
 import torch
 
 from sam_road_amd import Config
+from sam_road_amd import cli
 from sam_road_amd import inferencer as inf
 from sam_road_amd import mask_clean as mc
 from sam_road_amd.inferencer import infer_imgs, infer_one_img, mask_clean_plan, scene_tiles
@@ -480,7 +481,7 @@ def test_cli_takes_the_key_and_the_flags(tmp_path, monkeypatch, scene_run):
     Image.fromarray(img).save("rgb.png")
 
     def run(name, config, *argv):
-        return run_cli(inf, net, tmp_path, monkeypatch, name, config, ["rgb.png"], *argv)["rgb"]
+        return run_cli(cli, net, tmp_path, monkeypatch, name, config, ["rgb.png"], *argv)["rgb"]
 
     def check(got):
         np.testing.assert_array_equal(got[0], want[2])                         # the PNGs are the cleaned masks
@@ -495,7 +496,7 @@ def test_cli_takes_the_key_and_the_flags(tmp_path, monkeypatch, scene_run):
     assert got[3]["MASK_CLEAN"] == {"road": key["road"], "keypoint": key["keypoint"]}
     wrong = {"road": {"min_area": 1, "min_peak": key["road"]["min_peak"]}, "keypoint": key["keypoint"], "connectivity": 4}
     check(run("c", dict(CFG, MASK_CLEAN=wrong), "--mask-min-area", area[0], "--mask-connectivity", "8"))      # a flag replaces its field only
-    monkeypatch.setattr(inf, "_build_net", lambda *a: (_ for _ in ()).throw(AssertionError("the model was built")))
+    monkeypatch.setattr(cli, "_build_net", lambda *a: (_ for _ in ()).throw(AssertionError("the model was built")))
     base = ["--config", "b.yaml", "--checkpoint", "none", "--device", "cpu", "--output_dir", "e", "--images", "rgb.png"]
     with pytest.raises(ValueError, match="connectivity must be 4 or 8"):
         inf.main(base + ["--mask-connectivity", "6"])

@@ -206,7 +206,7 @@ def test_cli_plumbing_matches_reference_run(tmp_path, monkeypatch):
     produced), same pickle structure incl. the SpaceNet (400 - r, c) flip.  The model call is replaced by one that returns the
     reference's own per-image results, so this runs without a GPU and checks the plumbing only (the GPU twin is
     test_cli_end_to_end_gpu)."""
-    from sam_road_amd import inferencer as inf
+    from sam_road_amd import cli, inferencer as inf
     mg = _mg()
     g = np.load(f"{GOLD}/refrun_cli.npz")
     for dataset in ("spacenet", "cityscale"):
@@ -234,7 +234,7 @@ def test_cli_plumbing_matches_reference_run(tmp_path, monkeypatch):
             return nodes, edges, g[key + "_itsc"], g[key + "_road"]
 
         monkeypatch.setattr(inf, "infer_imgs", lambda net, imgs, config, _f=fake_infer, **kw: (_f(net, im, config) for im in imgs))
-        monkeypatch.setattr(inf, "_build_net", lambda config, checkpoint, device: None)
+        monkeypatch.setattr(cli, "_build_net", lambda config, checkpoint, device: None)
         monkeypatch.chdir(work)
         inf.main(["--config", "cfg.yaml", "--checkpoint", "ckpt.ckpt", "--output_dir", "run1", "--device", "cpu"])
         outdir = work / "save" / "run1"

@@ -16,6 +16,7 @@ import pytest
 import torch
 
 from sam_road_amd import Config
+from sam_road_amd import cli
 from sam_road_amd import inferencer as inf
 from sam_road_amd import road_width as rw
 from sam_road_amd.edge_support import edge_attrs, edge_support_ref, graph_geojson
@@ -219,7 +220,7 @@ def test_every_refusal_is_a_value_error_before_the_model_is_touched(tmp_path, mo
 
     def untouchable(*a, **k):
         raise AssertionError("the model was built")
-    monkeypatch.setattr(inf, "_build_net", untouchable)
+    monkeypatch.setattr(cli, "_build_net", untouchable)
     cases = [(b, ()) for b in BAD_KEYS[:7]] + [(None, ("--road-width-radius", "0")), (None, ("--road-width", "--road-width-radius", "255")),
                                                (None, ("--road-width-on", "1.5")), (None, ("--road-min-width", "-1")), (None, ("--road-max-width", "-2")),
                                                (None, ("--road-min-in", "2")), (None, ("--road-min-width", "5", "--road-max-width", "4")),
@@ -296,15 +297,15 @@ def test_cli_without_the_key_is_the_run_it_was_and_with_it_writes_the_widths(tmp
     Image.fromarray(img).save("a.png")
 
     # without the key: no call, and the files of a run in which the new code is out of the way, byte for byte
-    plain = run_cli(inf, net, tmp_path, monkeypatch, "plain", CFG, ["a.png"], "--viz")
+    plain = run_cli(cli, net, tmp_path, monkeypatch, "plain", CFG, ["a.png"], "--viz")
     assert not wk.width_calls(net) and not wk.ek.support_calls(net)
     assert _files("save/plain") == ["config.yaml", "graph/a.p", "inference_time.txt", "mask/a_itsc.png", "mask/a_road.png", "viz/a.png"]
     with monkeypatch.context() as mp:
         def never(*a, **k):
             raise AssertionError("the new code ran")
-        mp.setattr(inf, "road_width_key", lambda *a, **k: None)
-        mp.setattr(inf, "apply_road_width", never)
-        run_cli(inf, net, tmp_path, mp, "bypassed", CFG, ["a.png"], "--viz")
+        mp.setattr(cli, "road_width_key", lambda *a, **k: None)
+        mp.setattr(cli, "apply_road_width", never)
+        run_cli(cli, net, tmp_path, mp, "bypassed", CFG, ["a.png"], "--viz")
     assert _files("save/bypassed") == _files("save/plain")
     for f in _files("save/plain"):
         if f != "inference_time.txt":
@@ -316,7 +317,7 @@ def test_cli_without_the_key_is_the_run_it_was_and_with_it_writes_the_widths(tmp
     nodes, edges, _, road = res
     assert edges.shape[0] > 3
     net.calls.clear()
-    got = run_cli(inf, net, tmp_path, monkeypatch, "attrs", CFG, ["a.png"], "--road-width", "--graph-geojson", "--viz")["a"]
+    got = run_cli(cli, net, tmp_path, monkeypatch, "attrs", CFG, ["a.png"], "--road-width", "--graph-geojson", "--viz")["a"]
     assert got[3]["ROAD_WIDTH"] == {"max_radius": 32} and [c[0] for c in wk.width_calls(net)] == ["road_dist", "graph_edge_widths"] and not wk.ek.support_calls(net)
     assert _files("save/attrs") == sorted(_files("save/plain") + ["graph_geojson/a.geojson"])
     st = road_width_ref(nodes, edges, road, 127, 32)
@@ -336,7 +337,7 @@ def test_cli_without_the_key_is_the_run_it_was_and_with_it_writes_the_widths(tmp
         key = road_width_key(Config(CFG, ROAD_WIDTH={"min_in": f_med, "max_radius": 7, "drop_isolated": True}))
         (want_nodes, want_edges, _, _), want_attrs = rw.apply_ref(key, res)
     assert want_edges.shape[0] < edges.shape[0]
-    got = run_cli(inf, net, tmp_path, monkeypatch, "kept", CFG, ["a.png"], "--road-min-in", repr(f_med), "--road-width-radius", "7", "--drop-isolated-nodes", "--graph-geojson")["a"]
+    got = run_cli(cli, net, tmp_path, monkeypatch, "kept", CFG, ["a.png"], "--road-min-in", repr(f_med), "--road-width-radius", "7", "--drop-isolated-nodes", "--graph-geojson")["a"]
     assert got[3]["ROAD_WIDTH"] == {"min_in": f_med, "max_radius": 7, "drop_isolated": True} and "EDGE_SUPPORT" not in got[3]
     assert got[2] == convert_to_sat2graph_format(want_nodes, want_edges)                         # the pickle
     assert json.load(open("save/kept/graph_geojson/a.geojson")) == json.loads(json.dumps(graph_geojson(want_nodes, want_edges, want_attrs)))
@@ -351,7 +352,7 @@ def test_cli_without_the_key_is_the_run_it_was_and_with_it_writes_the_widths(tmp
     (want_nodes, want_edges, _, _), want_w = rw.apply_ref(wkey, mid)
     assert 0 < mid[1].shape[0] < edges.shape[0] and np.array_equal(want_edges, mid[1])
     net.calls.clear()
-    got = run_cli(inf, net, tmp_path, monkeypatch, "both", CFG, ["a.png"], "--edge-min-on", repr(o_med), "--road-min-in", "0", "--graph-geojson")["a"]
+    got = run_cli(cli, net, tmp_path, monkeypatch, "both", CFG, ["a.png"], "--edge-min-on", repr(o_med), "--road-min-in", "0", "--graph-geojson")["a"]
     assert [c[0] for c in net.calls if c[0].startswith(("graph_edge", "road_"))] == ["graph_edge_stats", "road_dist", "graph_edge_widths"]
     assert got[2] == convert_to_sat2graph_format(want_nodes, want_edges)
     doc = json.load(open("save/both/graph_geojson/a.geojson"))

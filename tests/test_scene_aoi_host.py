@@ -13,6 +13,7 @@ import pytest
 import torch
 
 from sam_road_amd import Config
+from sam_road_amd import cli
 from sam_road_amd import inferencer as inf
 from sam_road_amd.aoi import (SceneAoi, aoi_edges, aoi_fill_ref, aoi_key_of, aoi_pack, aoi_ref, read_geojson, scene_aoi_key,
                               scene_aoi_override)
@@ -533,7 +534,7 @@ def test_cli_takes_the_flags(tmp_path, monkeypatch, scene):
         assert got[2] == convert_to_sat2graph_format(want[0], want[1])
 
     # one file for every scene, the exclude and the buffer beside it
-    got = run_cli(inf, net, tmp_path, monkeypatch, "one", CFG, ["a.png", "b.png"], "--aoi", "holed.geojson", "--aoi-exclude", "cut.geojson", "--aoi-buffer", "2")
+    got = run_cli(cli, net, tmp_path, monkeypatch, "one", CFG, ["a.png", "b.png"], "--aoi", "holed.geojson", "--aoi-exclude", "cut.geojson", "--aoi-buffer", "2")
     assert _key(got["a"][3]["SCENE_AOI"]) == _key(HOLED)
     check(got["a"], _run(net, scene, CFG, valid=aoi_ref((H, W), _key(HOLED))))
     check(got["b"], _run(net, other, CFG, valid=aoi_ref((384, 640), _key(HOLED))))
@@ -541,12 +542,12 @@ def test_cli_takes_the_flags(tmp_path, monkeypatch, scene):
     gt = ["100", "0.5", "0", "50", "0", "0.25"]                                  # X = 100 + col / 2, Y = 50 + row / 4
     with open("tri_map.geojson", "w") as f:
         json.dump({"type": "Polygon", "coordinates": [[[100 + c / 2, 50 + r / 4] for r, c in TRIANGLE[0][0]]]}, f)
-    got = run_cli(inf, net, tmp_path, monkeypatch, "per", dict(CFG, SCENE_AOI={"buffer": 1}), ["a.png", "b.png"], "--aoi", "tri_map.geojson", "-", "--aoi-geotransform", *gt)
+    got = run_cli(cli, net, tmp_path, monkeypatch, "per", dict(CFG, SCENE_AOI={"buffer": 1}), ["a.png", "b.png"], "--aoi", "tri_map.geojson", "-", "--aoi-geotransform", *gt)
     check(got["a"], _run(net, scene, CFG, valid=aoi_ref((H, W), _key({"include": TRIANGLE, "buffer": 1}))))
     check(got["b"], _run(net, other, CFG))                                       # no include, no exclude: the whole scene, whatever the buffer
     with pytest.raises(ValueError, match="LineString"):
-        run_cli(inf, net, tmp_path, monkeypatch, "bad", CFG, ["a.png"], "--aoi", "line.geojson")
+        run_cli(cli, net, tmp_path, monkeypatch, "bad", CFG, ["a.png"], "--aoi", "line.geojson")
     with pytest.raises(ValueError, match="SCENE_AOI"):
-        run_cli(inf, net, tmp_path, monkeypatch, "bad2", CFG, ["a.png"], "--aoi", "tri.geojson", "--aoi-buffer", "17")
+        run_cli(cli, net, tmp_path, monkeypatch, "bad2", CFG, ["a.png"], "--aoi", "tri.geojson", "--aoi-buffer", "17")
     with pytest.raises(ValueError, match="SCENE_GROUP"):
-        run_cli(inf, net, tmp_path, monkeypatch, "bad3", CFG, ["a.png", "b.png"], "--aoi", "tri.geojson", "--scene-group", "2")
+        run_cli(cli, net, tmp_path, monkeypatch, "bad3", CFG, ["a.png", "b.png"], "--aoi", "tri.geojson", "--scene-group", "2")

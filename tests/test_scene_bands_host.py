@@ -13,6 +13,7 @@ import pytest
 import torch
 
 from sam_road_amd import Config
+from sam_road_amd import cli
 from sam_road_amd import inferencer as inf
 from sam_road_amd.inferencer import infer_imgs, infer_one_img, scene_tiles
 from sam_road_amd.radiometry import apply_luts, band_lut, band_luts, scene_bands_key, scene_bands_override, stretch_from_hist
@@ -484,7 +485,7 @@ def test_cli_takes_the_key_and_the_flags(tmp_path, monkeypatch, standin, scene, 
     np.save("raw.npy", raw)
 
     def run(name, config, *argv):
-        return run_cli(inf, standin, tmp_path, monkeypatch, name, config, ["raw.npy"], *argv)["raw"]
+        return run_cli(cli, standin, tmp_path, monkeypatch, name, config, ["raw.npy"], *argv)["raw"]
 
     def check(got, want):
         np.testing.assert_array_equal(got[0], want[2])
@@ -504,7 +505,7 @@ def test_cli_takes_the_key_and_the_flags(tmp_path, monkeypatch, standin, scene, 
     assert got[3]["SCENE_BANDS"] == {"select": SELECT, "stretch": [0, 65535], "gamma": 1.0}
     check(got, stock_run)
     assert scene_bands_override(Config(dict(SCENE_BANDS=key)), gamma=2.0) == dict(key, gamma=2.0)
-    monkeypatch.setattr(inf, "_build_net", lambda *a: (_ for _ in ()).throw(AssertionError("the model was built")))
+    monkeypatch.setattr(cli, "_build_net", lambda *a: (_ for _ in ()).throw(AssertionError("the model was built")))
     base = ["--config", "b.yaml", "--checkpoint", "none", "--device", "cpu", "--output_dir", "e", "--images", "raw.npy"]
     with pytest.raises(ValueError, match="select"):
         inf.main(base + ["--bands", "0,1"])

@@ -15,6 +15,7 @@ import torch
 
 from sam_road_amd import Config
 from sam_road_amd import float_scene as fs
+from sam_road_amd import cli
 from sam_road_amd import inferencer as inf
 from sam_road_amd.aoi import aoi_ref, scene_aoi_key
 from sam_road_amd.inferencer import infer_imgs, infer_one_img, scene_tiles
@@ -664,7 +665,7 @@ def test_cli_takes_the_key_and_the_flags(tmp_path, monkeypatch, standin, scene):
     np.save("raw.npy", raw)
 
     def run(name, config, *argv):
-        return run_cli(inf, standin, tmp_path, monkeypatch, name, config, ["raw.npy"], *argv)["raw"]
+        return run_cli(cli, standin, tmp_path, monkeypatch, name, config, ["raw.npy"], *argv)["raw"]
 
     def check(got, want):
         np.testing.assert_array_equal(got[0], want[2])
@@ -688,7 +689,7 @@ def test_cli_takes_the_key_and_the_flags(tmp_path, monkeypatch, standin, scene):
     assert got[3]["SCENE_FLOAT"] == dict(fixed, gamma=1.0, transfer="linear")     # one flag keeps the other fields
     check(got, _run(standin, raw, dict(E2E_CFG, SCENE_FLOAT=fixed)))
     assert fs.scene_float_override(Config(dict(SCENE_FLOAT=key)), gamma=2.0) == dict(key, gamma=2.0)
-    monkeypatch.setattr(inf, "_build_net", lambda *a: (_ for _ in ()).throw(AssertionError("the model was built")))
+    monkeypatch.setattr(cli, "_build_net", lambda *a: (_ for _ in ()).throw(AssertionError("the model was built")))
     base = ["--config", "b.yaml", "--checkpoint", "none", "--device", "cpu", "--output_dir", "e", "--images", "raw.npy"]
     with pytest.raises(ValueError, match="select"):
         inf.main(base + ["--float-bands", "0,1", "--float-range", "0", "1"])

@@ -13,6 +13,7 @@ import pytest
 import torch
 
 from sam_road_amd import Config, _lib
+from sam_road_amd import cli
 from sam_road_amd import inferencer as inf
 from sam_road_amd.inferencer import group_fits, group_geometry, infer_imgs, infer_one_img, scene_group_key
 
@@ -403,17 +404,17 @@ def test_cli_scene_group_gives_the_files_of_a_run_without_it(tmp_path, monkeypat
     for i, im in enumerate(imgs):
         names.append(f"chip{i}.png")
         Image.fromarray(im).save(names[-1])
-    plain = run_cli(inf, net, tmp_path, monkeypatch, "a", HOST_CFG, names)
+    plain = run_cli(cli, net, tmp_path, monkeypatch, "a", HOST_CFG, names)
     assert not group_calls(net)
-    grouped = run_cli(inf, net, tmp_path, monkeypatch, "b", HOST_CFG, names, "--scene-group", "2")
+    grouped = run_cli(cli, net, tmp_path, monkeypatch, "b", HOST_CFG, names, "--scene-group", "2")
     assert [c[:2] for c in group_calls(net)] == [("group_pack", 2), ("group_crop", 2)]
-    by_key = run_cli(inf, net, tmp_path, monkeypatch, "c", dict(HOST_CFG, SCENE_GROUP=3), names)
+    by_key = run_cli(cli, net, tmp_path, monkeypatch, "c", dict(HOST_CFG, SCENE_GROUP=3), names)
     for stem in plain:
         for other in (grouped, by_key):
             np.testing.assert_array_equal(plain[stem][0], other[stem][0])
             np.testing.assert_array_equal(plain[stem][1], other[stem][1])
             assert plain[stem][2] == other[stem][2]
     assert grouped["chip0"][3]["SCENE_GROUP"] == 2 and "SCENE_GROUP" not in plain["chip0"][3]
-    monkeypatch.setattr(inf, "_build_net", lambda *a: (_ for _ in ()).throw(AssertionError("the model was built")))
+    monkeypatch.setattr(cli, "_build_net", lambda *a: (_ for _ in ()).throw(AssertionError("the model was built")))
     with pytest.raises(ValueError, match="SCENE_GROUP"):
         inf.main(["--config", "a.yaml", "--checkpoint", "none", "--device", "cpu", "--output_dir", "e", "--images", *names, "--scene-group", "0"])

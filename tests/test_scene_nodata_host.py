@@ -12,6 +12,7 @@ import pytest
 import torch
 
 from sam_road_amd import Config
+from sam_road_amd import cli
 from sam_road_amd import inferencer as inf
 from sam_road_amd.inferencer import _empty_result, infer_imgs, infer_one_img, scene_tiles
 from sam_road_amd.nodata import SceneNodata, grow_ref, nodata_ref, nodata_table, scene_nodata_check, scene_nodata_key, scene_nodata_override
@@ -440,7 +441,7 @@ def test_cli_takes_the_flags_beside_valid_masks(tmp_path, monkeypatch, collar):
     np.save("caller.npy", caller)
 
     def run(name, config, *argv):
-        return run_cli(inf, net, tmp_path, monkeypatch, name, config, ["rgb.png"], *argv)["rgb"]
+        return run_cli(cli, net, tmp_path, monkeypatch, name, config, ["rgb.png"], *argv)["rgb"]
 
     def check(got, want):
         np.testing.assert_array_equal(got[0], want[2])

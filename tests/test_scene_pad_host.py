@@ -13,6 +13,7 @@ import pytest
 import torch
 
 from sam_road_amd import Config, _lib
+from sam_road_amd import cli
 from sam_road_amd import inferencer as inf
 from sam_road_amd.graph_points import extract_graph_points
 from sam_road_amd.inferencer import edge_votes, infer_imgs, infer_one_img, scene_pad_key, scene_pad_plan, scene_tiles, votes_to_edges
@@ -381,7 +382,7 @@ def test_cli_takes_the_key_and_the_flags(tmp_path, monkeypatch, standin, square_
     plain, pad, edge = _E2E_CFG, dict(_E2E_CFG, SCENE_PAD={"border": 24}), dict(_E2E_CFG, SCENE_PAD={"border": 8, "mode": "edge"})
 
     def run(name, config, *argv):
-        return run_cli(inf, standin, tmp_path, monkeypatch, name, config, ["rgb.png"], *argv)["rgb"]
+        return run_cli(cli, standin, tmp_path, monkeypatch, name, config, ["rgb.png"], *argv)["rgb"]
 
     def check(got, want):
         np.testing.assert_array_equal(got[0], want[2])
@@ -397,7 +398,7 @@ def test_cli_takes_the_key_and_the_flags(tmp_path, monkeypatch, standin, square_
     got = run("d", edge, "--scene-pad-mode", "constant")                  # one flag keeps the other field of the YAML
     assert got[3]["SCENE_PAD"] == {"border": [8, 8], "mode": "constant"}
     check(got, infer_one_img(standin, img, Config(dict(_E2E_CFG, SCENE_PAD={"border": 8, "mode": "constant"})), device="cpu"))
-    monkeypatch.setattr(inf, "_build_net", lambda *a: (_ for _ in ()).throw(AssertionError("the model was built")))
+    monkeypatch.setattr(cli, "_build_net", lambda *a: (_ for _ in ()).throw(AssertionError("the model was built")))
     with pytest.raises(ValueError, match="border"):
         inf.main(["--config", "b.yaml", "--checkpoint", "none", "--device", "cpu", "--output_dir", "e", "--images", "rgb.png", "--scene-pad", "-4"])
     with pytest.raises(SystemExit):

@@ -13,6 +13,7 @@ import pytest
 import torch
 
 from sam_road_amd import Config
+from sam_road_amd import cli
 from sam_road_amd import inferencer as inf
 from sam_road_amd import resample as rs
 from sam_road_amd.inferencer import infer_imgs, infer_one_img, scene_tiles
@@ -478,7 +479,7 @@ def test_cli_takes_the_key_and_the_flags(tmp_path, monkeypatch, standin, half_ru
     Image.fromarray(img).save("rgb.png")
 
     def run(name, config, *argv):
-        return run_cli(inf, standin, tmp_path, monkeypatch, name, config, ["rgb.png"], *argv)["rgb"]
+        return run_cli(cli, standin, tmp_path, monkeypatch, name, config, ["rgb.png"], *argv)["rgb"]
 
     def check(got):
         np.testing.assert_array_equal(got[0], want[2])
@@ -493,7 +494,7 @@ def test_cli_takes_the_key_and_the_flags(tmp_path, monkeypatch, standin, half_ru
     check(got)
     assert got[3]["SCENE_SCALE"] == {"scene_gsd": 0.5, "model_gsd": 1.0}
     check(run("d", dict(CFG, SCENE_SCALE={"scene_gsd": 3.0, "model_gsd": 2.0}), "--scene-gsd", "1.0"))      # the other field stays
-    monkeypatch.setattr(inf, "_build_net", lambda *a: (_ for _ in ()).throw(AssertionError("the model was built")))
+    monkeypatch.setattr(cli, "_build_net", lambda *a: (_ for _ in ()).throw(AssertionError("the model was built")))
     base = ["--config", "b.yaml", "--checkpoint", "none", "--device", "cpu", "--output_dir", "e", "--images", "rgb.png"]
     with pytest.raises(ValueError, match="reduces to 1/9"):
         inf.main(base + ["--scene-scale", "1", "9"])

@@ -12,6 +12,7 @@ import pytest
 import torch
 
 from sam_road_amd import Config, _lib
+from sam_road_amd import cli
 from sam_road_amd import inferencer as inf
 from sam_road_amd.inferencer import infer_imgs, infer_one_img, orient_tile, tta_plan, unorient_tile
 
@@ -254,7 +255,7 @@ def test_cli_takes_the_key_and_the_flag(tmp_path, monkeypatch, standin):
     plain, two = cfg, dict(cfg, TTA=["id", "flip_v"])
 
     def run(name, config, *argv):
-        return run_cli(inf, net, tmp_path, monkeypatch, name, config, ["rgb.png"], *argv)["rgb"]
+        return run_cli(cli, net, tmp_path, monkeypatch, name, config, ["rgb.png"], *argv)["rgb"]
 
     want = {k: infer_one_img(net, img, Config(dict(cfg, **({} if k == "plain" else dict(TTA=k.split(","))))), device="cpu")
             for k in ("plain", "id,flip_v", "id,rot270")}
@@ -271,7 +272,7 @@ def test_cli_takes_the_key_and_the_flag(tmp_path, monkeypatch, standin):
     check(got, "id,rot270")
     assert got[3]["TTA"] == ["id", "rot270"]
     check(run("d", two, "--tta", "id"), "plain")                         # and overrides the YAML
-    monkeypatch.setattr(inf, "_build_net", lambda *a: (_ for _ in ()).throw(AssertionError("the model was built")))
+    monkeypatch.setattr(cli, "_build_net", lambda *a: (_ for _ in ()).throw(AssertionError("the model was built")))
     for bad, what in (("flip_h,id", "first"), ("id,spin", "one of"), ("id,id", "twice")):
         with pytest.raises(ValueError, match=what):
             inf.main(["--config", "a.yaml", "--checkpoint", "none", "--device", "cpu", "--output_dir", "e", "--images", "rgb.png", "--tta", bad])

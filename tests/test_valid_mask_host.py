@@ -174,6 +174,7 @@ def test_pipelined_tile_sharded_world2_masked():
 def test_cli_valid_masks_and_rgba(tmp_path, monkeypatch, standin):
     from PIL import Image
     import sam_road_amd.inferencer as inf
+    from sam_road_amd import cli
     net, cfg = standin
     H, W = 384, 640
     img = _rect_scene(H, W, 60)
@@ -195,7 +196,7 @@ def test_cli_valid_masks_and_rgba(tmp_path, monkeypatch, standin):
     np.testing.assert_array_equal(inf.read_alpha_valid("pal.png"), left)
 
     def run(name, images, *argv):
-        return run_cli(inf, net, tmp_path, monkeypatch, name, cfg, images, *argv)
+        return run_cli(cli, net, tmp_path, monkeypatch, name, cfg, images, *argv)
 
     want = {k: infer_one_img(net, img, Config(cfg), device="cpu", valid=v) for k, v in (("plain", None), ("band", band), ("left", left))}
     from sam_road_amd.formats import convert_to_sat2graph_format
