@@ -367,4 +367,3 @@ def test_sam_attention(ctx, S, win, hd):
     tag = "op_attention[S=%d,win=%d,hd=%d]" % (S, win, hd)
     tolerances.check(tag + " max-abs", err.max().item(), tolerances.ATTN_OP_MAX)
     tolerances.check(tag + " mean-abs", err.mean().item(), tolerances.ATTN_OP_MEAN)
-    assert err.max().item() < 2e-2 and err.mean().item() < 1.5e-3, (err.max().item(), err.mean().item())
