@@ -528,6 +528,33 @@ int srh_road_dist(srh_ctx* ctx, const uint8_t* mask, int H, int W, int on_level,
 int srh_graph_edge_widths(srh_ctx* ctx, const int32_t* nodes_host, const int32_t* nodes_dev, int N, const int32_t* edges_host,
                           const int32_t* edges_dev, int E, int H, int W, const uint16_t* d2, int R, int32_t* out, void* stream);
 
+/* Spur and small-component pruning of a graph and its chains (config key GRAPH_CLEAN; an extension).  One additive entry;
+ * the ABI number stays 11 because nothing existing changes, and a run without the key does not call it.  Nothing is read back.
+ *
+ * Tables as srh_graph_edge_stats takes them (the host copy is validated, the 4-byte aligned device copy is read and never written), N and
+ * E at most SRH_GRAPH_CLEAN_MAX_ITEMS = 2^26.  The graph is a multigraph: self-loops and parallel edges count as they stand.  The rule is
+ * that of sam_road_amd/graph_clean.py, in integers: len_q(e) = floor(16 sqrt(dr^2 + dc^2)); a chain is a class of live edges under "share
+ * a node of degree exactly 2", its id the smallest edge index; a component's id is its smallest node index.  In each of `rounds` rounds
+ * (1 .. SRH_GRAPH_CLEAN_MAX_ROUNDS), all at once on the graph the round before left, a live edge is dropped if its chain has one end of
+ * degree 1, one of degree >= 3 and a 64-bit length sum < spur_q (a spur), or if its component's 64-bit length sum is < comp_q; a
+ * threshold of 0 is not stated and its test never holds.  spur_q, comp_q: ceil(16 s), ceil(16 c) for thresholds in pixels.
+ *   state_out u8 [E] on the device: 0 kept, else 4 * round + 1 (spur) + 2 (small component)
+ *   out int32 [E, 4] on the device, 16-byte aligned: {chain, component, min(chain length, 2^31 - 1), min(component length, 2^31 - 1)} of
+ *       one more pass over the kept graph, ids in the indices given; {-1, -1, 0, 0} for a dropped edge
+ * Every element of both is defined after the call and nothing else of the caller's is written.  Integer sums: the same numbers in any
+ * order.  5 (rounds + 1) launches whatever the graph holds — init, edges, chains, sums, decide per pass — over a workspace of the context
+ * of 24 N + 25 E bytes that grows on demand; the entry holds a lock of the context from the workspace's growth to the last launch and a
+ * call waits on the device for the call before it, so it may be called from several threads on several streams.  E = 0 is SRH_OK and
+ * launches nothing (state_out and out may then be NULL).  SRH_ERR_BAD_ARG, and nothing is launched, for every condition
+ * srh_graph_edge_stats refuses of its tables, N or E above 2^26, rounds outside 1 .. 8, a negative threshold, a null state_out or out
+ * with E > 0, an out that is not 16-byte aligned, or an output overlapping an input, the other output or the workspace.  Profiler rows:
+ * graph_clean_init, graph_clean_edges, graph_clean_chains, graph_clean_sums, graph_clean_decide. */
+#define SRH_GRAPH_CLEAN_MAX_ROUNDS 8
+#define SRH_GRAPH_CLEAN_MAX_ITEMS (1 << 26)
+int srh_graph_clean(srh_ctx* ctx, const int32_t* nodes_host, const int32_t* nodes_dev, int N, const int32_t* edges_host,
+                    const int32_t* edges_dev, int E, int64_t spur_q, int64_t comp_q, int rounds, uint8_t* state_out, int32_t* out,
+                    void* stream);
+
 /* GeoTIFF scenes (config key GEOTIFF; an extension).  Two additive entries, srh_tiff_assemble here and the host entry
  * srh_tiff_lzw_decode below; the ABI number stays 11 because nothing existing changes, and a run without the key calls neither.
  *

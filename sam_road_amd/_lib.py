@@ -94,6 +94,7 @@ SYMBOLS = {
     "srh_graph_edge_stats": (_I, [_P, _P, _P, _I, _P, _P, _I, _I, _I, _I, _P, _P, _I, _P, _P]),
     "srh_road_dist": (_I, [_P, _P, _I, _I, _I, _I, _P, _P]),
     "srh_graph_edge_widths": (_I, [_P, _P, _P, _I, _P, _P, _I, _I, _I, _P, _I, _P, _P]),
+    "srh_graph_clean": (_I, [_P, _P, _P, _I, _P, _P, _I, C.c_int64, C.c_int64, _I, _P, _P, _P]),
     "srh_tiff_assemble": (_I, [_P, _P, C.c_int64, _P, _P, _I, _P, _I, _I, _I, _I, _I, _I, _P]),
     "srh_tiff_lzw_decode": (_I, [_P, C.c_int64, _P, _P, C.c_int64, _P, C.c_int64, _P, _P, C.c_int32]),
     "srh_op_patch_im2col": (_I, [_P, _P, _I, _I, _P, _I, _I, _I, _P, _P]),

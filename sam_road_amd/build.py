@@ -9,7 +9,7 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libsamroad_hip.so")
-SOURCES = ["api_ctx.hip", "api_weights.hip", "api_model.hip", "api_scene.hip", "api_ops.hip", "gemm.hip", "gemm_z192.hip", "norm.hip", "patch.hip", "attention.hip", "attention_hdx.hip", "decoder.hip", "scene_valid.hip", "scene_window.hip", "scene_tta.hip", "scene_pad.hip", "scene_group.hip", "scene_bands.hip", "scene_scale.hip", "mask_clean.hip", "scene_nodata.hip", "scene_aoi.hip", "scene_float.hip", "graph_raster.hip", "edge_support.hip", "road_width.hip", "scene_tiff.hip", "sam_decoder.hip", "topo.hip", "topo_fused.hip", "host_geom.hip"]
+SOURCES = ["api_ctx.hip", "api_weights.hip", "api_model.hip", "api_scene.hip", "api_ops.hip", "gemm.hip", "gemm_z192.hip", "norm.hip", "patch.hip", "attention.hip", "attention_hdx.hip", "decoder.hip", "scene_valid.hip", "scene_window.hip", "scene_tta.hip", "scene_pad.hip", "scene_group.hip", "scene_bands.hip", "scene_scale.hip", "mask_clean.hip", "scene_nodata.hip", "scene_aoi.hip", "scene_float.hip", "graph_raster.hip", "edge_support.hip", "road_width.hip", "graph_clean.hip", "scene_tiff.hip", "sam_decoder.hip", "topo.hip", "topo_fused.hip", "host_geom.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function", "-Wno-unused-value", "-Wno-unused-result"]
 
 # The softmax row maxima are taken over MFMA results; without this flag every fmaxf operand gets a v_max x, x to quiet a

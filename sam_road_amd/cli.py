@@ -18,6 +18,10 @@ coordinates.  Without them nothing of this runs.
 `--drop-isolated-nodes`) lay over the config's ROAD_WIDTH (sam_road_amd/road_width.py): an exact distance map of the thresholded road
 mask is built on the device and every edge gets its road width from it along its centre line; edges outside the stated widths are
 dropped, behind EDGE_SUPPORT's filter and before the files are written, and the GeoJSON's features carry the width attributes.
+`--graph-min-spur S`, `--graph-min-component C`, `--graph-clean-rounds R`, `--graph-polylines` (with `--drop-isolated-nodes`) lay over
+the config's GRAPH_CLEAN (sam_road_amd/graph_clean.py): dead-end spurs shorter than S px and connected components shorter than C px are
+dropped on the device, behind the two filters above and before the files are written; every kept edge gets its chain (road segment) and
+component with their lengths, and `--graph-polylines` writes graph_polylines/{id}.geojson, one LineString per chain.
 Extras: `--images a.png b.npy ...` runs explicit scene files instead of the dataset split; under torchrun
 (one process per GPU) the scenes are dealt round-robin to the ranks (`--shard scenes`, default) or every scene's tiles are split
 over the ranks (`--shard tiles`; `tiles-pipelined` for the software-pipelined loop), all ranks writing into the one output directory.
@@ -57,6 +61,7 @@ from .mask_clean import mask_clean_override
 from .nodata import scene_nodata_key, scene_nodata_override
 from .radiometry import scene_bands_key, scene_bands_override
 from .resample import scene_scale_key, scene_scale_override
+from .graph_clean import apply as apply_graph_clean, graph_clean_key, graph_clean_override, table_of as clean_table_of, write_polylines
 from .road_width import apply as apply_road_width, road_width_key, road_width_override
 
 
@@ -246,6 +251,17 @@ def build_parser():
     ap.add_argument("--road-min-in", default=None, type=float, metavar="F",
                     help="(extension) drop the edges with less than the fraction F (0..1) of their centre line on the road, overriding min_in of "
                          "the config's ROAD_WIDTH")
+    ap.add_argument("--graph-min-spur", default=None, type=float, metavar="S",
+                    help="(extension) drop the dead-end chains (one end of degree 1, one at a junction) shorter than S px, overriding min_spur of "
+                         "the config's GRAPH_CLEAN")
+    ap.add_argument("--graph-min-component", default=None, type=float, metavar="C",
+                    help="(extension) drop the connected components whose edges add up to less than C px, overriding min_component of the config's GRAPH_CLEAN")
+    ap.add_argument("--graph-clean-rounds", default=None, type=int, metavar="R",
+                    help="(extension) apply the two tests R times (1..8, default 1), each time on what the round before left, overriding rounds of "
+                         "the config's GRAPH_CLEAN")
+    ap.add_argument("--graph-polylines", action="store_true", default=None,
+                    help="(extension) write graph_polylines/{id}.geojson: one LineString per chain of the graph (a road segment between junctions "
+                         "or dead ends), with --geotransform as --graph-geojson; alone it turns on a GRAPH_CLEAN that filters nothing")
     ap.add_argument("--graph-geojson", action="store_true", default=None,
                     help="(extension) write graph_geojson/{id}.geojson: one LineString per edge, [x, y] = [col + 1/2, row + 1/2], with the "
                          "edge's attributes of EDGE_SUPPORT as properties where the key is given")
@@ -271,17 +287,19 @@ class RunPlan:
     tiff_heads: dict                # path -> header of the --images that are read as GeoTIFFs
     support: object                 # the EDGE_SUPPORT key, or None
     width: object                   # the ROAD_WIDTH key, or None
+    clean: object                   # the GRAPH_CLEAN key, or None
     raster: object                  # the GRAPH_RASTER key, or None
     export_gt: object               # the geotransform of the GeoJSON export that was given, or None
     job_aois: object                # one SCENE_AOI value per --images entry where the scenes have their own, or None
     geojson: bool                   # graph_geojson/ is written
+    polylines: bool                 # graph_polylines/ is written
     tiff_masks: bool                # mask_tif/ is written
     spacenet_gt: bool               # the ground-truth graphs are the SpaceNet dataset's own (flipped rows)
 
     @property
     def post(self):
         """A step between a scene's result and its files."""
-        return self.support is not None or self.width is not None or self.geojson
+        return self.support is not None or self.width is not None or self.clean is not None or self.geojson
 
     @property
     def keeps_inputs(self):
@@ -308,8 +326,11 @@ def resolve_run(ap, args, config, world=1):
     road_flags = (args.road_width, args.road_width_on, args.road_width_radius, args.road_min_width, args.road_max_width, args.road_min_in)
     road_on = any(v is not None for v in road_flags) or bool(config.get("ROAD_WIDTH"))
     edge_flags = (args.edge_support_width, args.edge_on, args.edge_min_mean, args.edge_min_on, args.edge_max_invalid)
-    # --drop-isolated-nodes is shared: it goes to every key that is in use, and to EDGE_SUPPORT as before where ROAD_WIDTH is not
-    edge_drop = args.drop_isolated_nodes if any(v is not None for v in edge_flags) or config.get("EDGE_SUPPORT") or not road_on else None
+    clean_flags = (args.graph_polylines, args.graph_min_spur, args.graph_min_component, args.graph_clean_rounds)
+    clean_on = any(v is not None for v in clean_flags) or bool(config.get("GRAPH_CLEAN"))
+    # --drop-isolated-nodes is shared: it goes to every key that is in use, and to EDGE_SUPPORT as before where neither ROAD_WIDTH nor
+    # GRAPH_CLEAN is
+    edge_drop = args.drop_isolated_nodes if any(v is not None for v in edge_flags) or config.get("EDGE_SUPPORT") or not (road_on or clean_on) else None
     if any(v is not None for v in edge_flags + (edge_drop,)):
         config.EDGE_SUPPORT = edge_support_override(config, args.edge_support_width, args.edge_on, args.edge_min_mean, args.edge_min_on,
                                                     args.edge_max_invalid, edge_drop, attributes_only=bool(args.graph_geojson))
@@ -317,6 +338,9 @@ def resolve_run(ap, args, config, world=1):
     if any(v is not None for v in road_flags):
         config.ROAD_WIDTH = road_width_override(config, *road_flags, drop_isolated=args.drop_isolated_nodes)
     width = road_width_key(config)               # and a ROAD_WIDTH
+    if any(v is not None for v in clean_flags):
+        config.GRAPH_CLEAN = graph_clean_override(config, *clean_flags, drop_isolated=args.drop_isolated_nodes)
+    clean = graph_clean_key(config)              # and a GRAPH_CLEAN
     export_gt = args.geotransform if args.geotransform is not None else args.aoi_geotransform
     if args.viz or args.graph_mask is not None or args.diff is not None:
         config.GRAPH_RASTER = graph_raster_override(config, args.viz, args.graph_mask, True if args.diff == [] else args.diff)
@@ -393,8 +417,8 @@ def resolve_run(ap, args, config, world=1):
     if scene.scene_group_key(config) > 1 and args.shard != "scenes" and world > 1:                                              # and a SCENE_GROUP
         raise ValueError("SCENE_GROUP applies to --shard scenes (every rank runs whole scenes); a tile-sharded mode runs its scenes one by one")
     _one_per_image(ap, args.valid_masks, args.images, "--valid-masks takes exactly one entry per --images entry ('-' for a scene without a mask)")
-    return RunPlan(tiff=tiff, tiff_heads=tiff_heads, support=support, width=width, raster=raster, export_gt=export_gt, job_aois=job_aois,
-                   geojson=bool(args.graph_geojson), tiff_masks=bool(tiff is not None and tiff.masks),
+    return RunPlan(tiff=tiff, tiff_heads=tiff_heads, support=support, width=width, clean=clean, raster=raster, export_gt=export_gt, job_aois=job_aois,
+                   geojson=bool(args.graph_geojson), polylines=bool(args.graph_polylines), tiff_masks=bool(tiff is not None and tiff.masks),
                    spacenet_gt=args.images is None and config.DATASET == "spacenet")
 
 
@@ -475,6 +499,15 @@ class SceneLoader:
             yield self._valids.popleft()
 
 
+def _merge_attrs(attrs, keep, more):
+    """The attributes of the steps so far, subset by the keep mask of the step that just ran, with that step's own laid over them."""
+    if more is None:
+        return attrs
+    if attrs is None:
+        return more
+    return [dict(attrs[k], **m) for k, m in zip(np.flatnonzero(keep).tolist(), more)]
+
+
 class SceneWriter:
     """The files of a scene: mask/{id}_road.png, mask/{id}_itsc.png, graph/{id}.p, and what the plan adds to them.  PNG encoding and
     pickling (tens of ms per 2048^2 scene) run on writer threads so that the scene loop goes straight back to the GPU.
@@ -490,10 +523,12 @@ class SceneWriter:
         self.render_dirs = {} if raster is None else {k: os.path.join(output_dir, d) for k, d, on in (
             ("viz", "viz", raster.viz), ("mask", "graph_mask", raster.mask), ("diff", "diff", raster.diff)) if on is not None}
         self.geojson_dir = os.path.join(output_dir, "graph_geojson") if plan.geojson else None
-        extra = ([os.path.join(output_dir, "mask_tif")] if plan.tiff_masks else []) + ([self.geojson_dir] if plan.geojson else [])
+        self.polylines_dir = os.path.join(output_dir, "graph_polylines") if plan.polylines else None
+        extra = ([os.path.join(output_dir, "mask_tif")] if plan.tiff_masks else []) + ([self.geojson_dir] if plan.geojson else []) + \
+            ([self.polylines_dir] if plan.polylines else [])
         for d in [self.mask_dir, self.graph_dir, *self.render_dirs.values(), *extra]:
             os.makedirs(d, exist_ok=True)
-        on_device = (raster is not None or plan.support is not None or plan.width is not None) and device.type == "cuda"
+        on_device = (raster is not None or plan.support is not None or plan.width is not None or plan.clean is not None) and device.type == "cuda"
         self.render_stream = torch.cuda.Stream(device) if on_device else None
         self.threads = 2 + len(self.render_dirs) + int(plan.post)
 
@@ -533,16 +568,18 @@ class SceneWriter:
         with self._on_render_stream():
             kept, attrs = apply_edge_support(plan.support, res, valid=valid, net=self.net)
             # ROAD_WIDTH runs behind EDGE_SUPPORT, on the graph it kept; the attributes of the edges both keep are merged
-            (pred_nodes, pred_edges, itsc_mask, _), widths, keep = apply_road_width(plan.width, kept, net=self.net, return_keep=True)
-        if widths is not None and attrs is not None:
-            attrs = [dict(attrs[k], **w) for k, w in zip(np.flatnonzero(keep).tolist(), widths)]
-        elif widths is not None:
-            attrs = widths
+            measured, widths, keep = apply_road_width(plan.width, kept, net=self.net, return_keep=True)
+            attrs = _merge_attrs(attrs, keep, widths)
+            # GRAPH_CLEAN runs behind both, on the graph they kept, and the attributes are carried along in the same way
+            (pred_nodes, pred_edges, itsc_mask, _), chains, keep = apply_graph_clean(plan.clean, measured, net=self.net, return_keep=True)
+            attrs = _merge_attrs(attrs, keep, chains)
         self.write_graph(img_id, pred_nodes, pred_edges)
+        own_gt = img.geotransform if plan.tiff is not None and plan.tiff.georef and isinstance(img, TiffScene) else None          # GEOTIFF: the default
+        export_gt = plan.export_gt if plan.export_gt is not None else own_gt
         if self.geojson_dir is not None:
-            own_gt = img.geotransform if plan.tiff is not None and plan.tiff.georef and isinstance(img, TiffScene) else None      # GEOTIFF: the default
-            write_geojson(os.path.join(self.geojson_dir, f"{img_id}.geojson"), pred_nodes, pred_edges, attrs,
-                          plan.export_gt if plan.export_gt is not None else own_gt)
+            write_geojson(os.path.join(self.geojson_dir, f"{img_id}.geojson"), pred_nodes, pred_edges, attrs, export_gt)
+        if self.polylines_dir is not None:
+            write_polylines(os.path.join(self.polylines_dir, f"{img_id}.geojson"), pred_nodes, pred_edges, clean_table_of(chains), export_gt)
         return self.render_scene(img_id, img, valid, pred_nodes, pred_edges, itsc_mask.shape, gt_path) if plan.raster is not None else (img_id, None)
 
     def submit(self, pool, record, img, valid, res):

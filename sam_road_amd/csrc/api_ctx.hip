@@ -59,6 +59,7 @@ extern "C" void srh_ctx_destroy(srh_ctx* c) {
     if (c->lane_stream) hipStreamDestroy(c->lane_stream);   // every call joined it to its caller's stream; what is queued still completes
     if (c->lane_fork) hipEventDestroy(c->lane_fork);
     if (c->lane_join) hipEventDestroy(c->lane_join);
+    if (c->clean_done) hipEventDestroy(c->clean_done);
     for (DevBuf* b : c->bufs) b->release();
     c->ztab.release();
     if (c->nf_host) hipHostFree(c->nf_host);

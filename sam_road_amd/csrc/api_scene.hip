@@ -594,6 +594,64 @@ extern "C" int srh_graph_edge_widths(srh_ctx* c, const int32_t* nodes_host, cons
     return 0;
 }
 
+// ---- spur and small-component pruning of the graph (kernels in graph_clean.hip, behaviour in DESIGN.md §6s) -----------------------------------
+static_assert(SRH_GRAPH_CLEAN_MAX_ROUNDS == GC_MAX_ROUNDS && SRH_GRAPH_CLEAN_MAX_ITEMS == GC_MAX_ITEMS, "limits of the header and the kernel");
+
+extern "C" int srh_graph_clean(srh_ctx* c, const int32_t* nodes_host, const int32_t* nodes_dev, int N, const int32_t* edges_host,
+                               const int32_t* edges_dev, int E, int64_t spur_q, int64_t comp_q, int rounds, uint8_t* state_out, int32_t* out,
+                               void* stream) {
+    if (!c || N < 0 || E < 0 || (N > 0 && (!nodes_host || !nodes_dev)) || (E > 0 && (!edges_host || !edges_dev || !state_out || !out)))
+        return fail(c, SRH_ERR_BAD_ARG, "srh_graph_clean: null argument or a negative count");
+    if (N > GC_MAX_ITEMS || E > GC_MAX_ITEMS) return fail(c, SRH_ERR_BAD_ARG, "srh_graph_clean: at most 2^26 nodes and 2^26 edges");
+    if (rounds < 1 || rounds > GC_MAX_ROUNDS) return fail(c, SRH_ERR_BAD_ARG, "srh_graph_clean: rounds is 1 to 8");
+    if (spur_q < 0 || comp_q < 0) return fail(c, SRH_ERR_BAD_ARG, "srh_graph_clean: a threshold is >= 0 (0: not stated)");
+    if ((reinterpret_cast<uintptr_t>(nodes_dev) | reinterpret_cast<uintptr_t>(edges_dev)) & 3) return fail(c, SRH_ERR_BAD_ARG, "srh_graph_clean: the device tables are 4-byte aligned");
+    if (reinterpret_cast<uintptr_t>(out) & 15) return fail(c, SRH_ERR_BAD_ARG, "srh_graph_clean: out is 16-byte aligned");
+    if (!gr_tables_ok(nodes_host, N, edges_host, E))
+        return fail(c, SRH_ERR_BAD_ARG, "srh_graph_clean: an inconsistent table (coordinates within +-2^28, edge indices in [0, N), an edge spans at most "
+                                        "16383 px per axis)");
+    if (E == 0) return 0;                        // nothing to write, nothing launched
+    const double sb = (double)E, ob = 16.0 * E;
+    if (ranges_overlap(out, ob, nodes_dev, 8.0 * N) || ranges_overlap(out, ob, edges_dev, 8.0 * E) || ranges_overlap(state_out, sb, nodes_dev, 8.0 * N) ||
+        ranges_overlap(state_out, sb, edges_dev, 8.0 * E))
+        return fail(c, SRH_ERR_BAD_ARG, "srh_graph_clean: an output overlaps an input");
+    if (ranges_overlap(out, ob, state_out, sb)) return fail(c, SRH_ERR_BAD_ARG, "srh_graph_clean: state_out and out overlap");
+    hipSetDevice(c->device);
+    hipStream_t s = (hipStream_t)stream;
+    std::lock_guard<std::mutex> lock(c->clean_mu);
+    const size_t ws = gc_workspace_bytes(N, E);
+    if (c->clean_ws.ensure(ws, 0.25)) return fail(c, SRH_ERR_HIP, "graph clean workspace allocation failed");
+    if (ranges_overlap(out, ob, c->clean_ws.p, (double)c->clean_ws.cap) || ranges_overlap(state_out, sb, c->clean_ws.p, (double)c->clean_ws.cap))
+        return fail(c, SRH_ERR_BAD_ARG, "srh_graph_clean: an output overlaps the workspace");
+    if (!c->clean_done && hipEventCreateWithFlags(&c->clean_done, hipEventDisableTiming) != hipSuccess) {
+        c->clean_done = nullptr;
+        return fail(c, SRH_ERR_HIP, "graph clean event creation failed");
+    }
+    // the call before this one, on whatever stream, has left the workspace before this one's first launch touches it (a no-op on a fresh event)
+    if (hipStreamWaitEvent(s, c->clean_done, 0) != hipSuccess) return fail(c, SRH_ERR_HIP, "srh_graph_clean: waiting for the workspace failed");
+    GraphCleanParams p;
+    p.nodes = nodes_dev; p.edges = edges_dev; p.N = N; p.E = E; p.spur_q = spur_q; p.comp_q = comp_q; p.state = state_out; p.out = out;
+    gc_workspace_carve(c->clean_ws.p, N, E, p);
+    const double n = (double)N, e = (double)E;
+    int rc = 0;
+    for (int r = 1; r <= rounds + 1 && !rc; ++r) {
+        p.round = r <= rounds ? r : 0;
+        p.first = r == 1;
+        rc = [&]() -> int {
+            TRYK(c, "graph_clean_init", 0, 24 * n + 16 * e, s, launch_graph_clean(p, 0, s));
+            TRYK(c, "graph_clean_edges", 0, 9 * e + 32 * e, s, launch_graph_clean(p, 1, s));
+            TRYK(c, "graph_clean_chains", 0, 12 * n, s, launch_graph_clean(p, 2, s));
+            TRYK(c, "graph_clean_sums", 0, 9 * e + 56 * e, s, launch_graph_clean(p, 3, s));
+            TRYK(c, "graph_clean_decide", 0, 9 * e + 36 * e, s, launch_graph_clean(p, 4, s));
+            return 0;
+        }();
+    }
+    const hipError_t rec = hipEventRecord(c->clean_done, s);        // also after a failed launch: what was queued still uses the workspace
+    if (rc) return rc;
+    if (rec != hipSuccess) return hip_fail(c, rec, "srh_graph_clean: recording the workspace event");
+    return 0;
+}
+
 // ---- a GeoTIFF's decompressed segments -> the scene raster (kernel in scene_tiff.hip, behaviour in DESIGN.md §6r) ---------------------------------
 extern "C" int srh_tiff_assemble(srh_ctx* c, const uint8_t* flat, int64_t flat_bytes, const int64_t* table_host, const int64_t* table_dev, int n_seg,
                                  void* out, int H, int W, int C, int dtype, int predictor, int big_endian, void* stream) {

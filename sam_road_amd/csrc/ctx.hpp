@@ -65,6 +65,12 @@ struct SRH_INTERNAL srh_ctx {
     // held from the workspace's growth to the second launch, and calls on one stream are ordered by it.
     DevBuf road_g{bufs};
     std::mutex road_mu;
+    // GRAPH_CLEAN: the forests and sums of srh_graph_clean, about 24 B per node and 25 B per edge.  The entry runs on writer threads: the lock
+    // is held from the workspace's growth to the last launch, and a call on another stream waits on the device (clean_done, recorded behind
+    // the last launch of every call) until the call before it has left the workspace.
+    DevBuf clean_ws{bufs};
+    std::mutex clean_mu;
+    hipEvent_t clean_done = nullptr;
     // profiling
     bool profiling = false;
     std::vector<std::string> cls_names;

@@ -14,6 +14,7 @@
 #include "graph_raster_piece.hpp"
 #include "edge_support_piece.hpp"
 #include "road_width_piece.hpp"
+#include "graph_clean_piece.hpp"
 #include "geotiff_piece.hpp"
 
 namespace srh {
@@ -247,6 +248,10 @@ int launch_road_dist(const RoadDistParams& p, int pass, hipStream_t s);
 // The six width statistics of every edge over its centre line: one launch, 16 lanes per edge, eight int32 per edge.  E >= 1; the tables
 // are on the device and have been checked on the host (gr_tables_ok).  -2 for bad parameters.
 int launch_graph_edge_widths(const EdgeWidthParams& p, hipStream_t s);
+// Spur and small-component pruning of the graph (graph_clean.hip; the parameters in graph_clean_piece.hpp): step 0 .. 4 of a
+// pass — init, edges, chains, sums, decide — one launch each.  E >= 1; the tables are on the device and have been checked on the host
+// (gr_tables_ok).  -2 for bad parameters.
+int launch_graph_clean(const GraphCleanParams& p, int step, hipStream_t s);
 
 // A GeoTIFF's decompressed segments -> the raster (scene_tiff.hip; the parameters in geotiff_piece.hpp).  One launch.
 int launch_tiff_assemble(const TiffParams& p, hipStream_t s);

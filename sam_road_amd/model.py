@@ -369,6 +369,41 @@ class GraphRasterOps:
                                                     d2.data_ptr(), R, out.data_ptr(), SAMRoad._stream(dev)), "srh_graph_edge_widths")
         return out                                # the device tables were made on this stream and are read on it
 
+    @torch.no_grad()
+    def graph_clean(self, nodes, edges, spur_q=0, comp_q=0, rounds=1, state=None, out=None):
+        """Spur and small-component pruning with chain and component ids (srh_graph_clean; GRAPH_CLEAN, DESIGN.md §6s, the rule in
+        sam_road_amd/graph_clean.py): nodes int [N, 2] (row, col) and edges int [E, 2] on the HOST, checked by graph_raster.check_graph;
+        spur_q / comp_q the integer thresholds ceil(16 s) / ceil(16 c), 0 = not stated -> NEW tensors on the device (or `state` / `out`),
+        state uint8 [E] and out int32 [E, 4], equal to graph_clean_ref.  5 (rounds + 1) launches (none for E = 0) over a workspace of the
+        library context, nothing read back."""
+        from . import graph_clean as _gc
+        from . import graph_raster as _gr
+        ctx, dev = self._graph_ctx()
+        n, e = _gr.check_graph(nodes, edges)
+        rounds = _gc.check_rounds(rounds)
+        for name, q in (("spur_q", spur_q), ("comp_q", comp_q)):
+            if not _gc._is_int(q) or not 0 <= q < 2 ** 63:
+                raise ValueError(f"GRAPH_CLEAN: {name} must be an int >= 0, got {q!r}")
+        N, E = int(n.shape[0]), int(e.shape[0])
+        if N > _gc.MAX_ITEMS or E > _gc.MAX_ITEMS:
+            raise ValueError(f"GRAPH_CLEAN: at most 2^26 nodes and edges, got {N}, {E}")
+        if state is None:
+            state = torch.empty(E, dtype=torch.uint8, device=dev)
+        elif state.device != dev or state.dtype != torch.uint8 or state.numel() != E or not state.is_contiguous():
+            raise ValueError(f"state must be a contiguous uint8 tensor of {E} elements on {dev}")
+        if out is None:
+            out = torch.empty((E, 4), dtype=torch.int32, device=dev)
+        elif out.device != dev or out.dtype != torch.int32 or out.numel() != 4 * E or not out.is_contiguous():
+            raise ValueError(f"out must be a contiguous int32 tensor of {4 * E} elements on {dev}")
+        if E == 0:
+            return state, out
+        n_h, e_h = torch.from_numpy(n), torch.from_numpy(e)
+        n_d, e_d = n_h.to(dev), e_h.to(dev)
+        with torch.cuda.device(dev):
+            ctx.check(ctx.lib.srh_graph_clean(ctx.handle, n_h.data_ptr(), n_d.data_ptr(), N, e_h.data_ptr(), e_d.data_ptr(), E, int(spur_q), int(comp_q),
+                                              rounds, state.data_ptr(), out.data_ptr(), SAMRoad._stream(dev)), "srh_graph_clean")
+        return state, out                         # the device tables were made on this stream and are read on it
+
 
 class DeviceGraphOps(GraphRasterOps):
     """GraphRasterOps without a model: the entries need a device, not weights."""

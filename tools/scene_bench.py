@@ -46,6 +46,9 @@ The final map_decoder bias is lowered so that the random network yields sparse m
     python tools/scene_bench.py --road-width [R] [--scene 4096 --tiles 32]       # ROAD_WIDTH: the distance map and the per-edge statistics against their
                                                                     # references, the whole call, the three kernels alone, the same work on the host,
                                                                     # the pipelined loop without / with the key
+    python tools/scene_bench.py --graph-clean [S C] [--scene 4096 --tiles 32]    # GRAPH_CLEAN: state and out of the device against graph_clean_ref on the
+                                                                    # scene's own graph (the run ends if they differ), the kernels alone, the whole
+                                                                    # call, the host reference, the pipelined loop without / with the key
     python tools/scene_bench.py --viz [--scene 4096 --tiles 32]     # GRAPH_RASTER: "graph_raster" compares the device class map with graph_raster_ref
                                                                     # (the run ends if they differ), reports the device time of raster, composite and
                                                                     # compare beside pass 1 and the host reference, and the pipelined loop with PNG
@@ -734,6 +737,120 @@ def edge_support_report(args, net, cfg, img, iters=20):
     return rep
 
 
+def graph_clean_report(args, net, cfg, img, iters=20):
+    """--graph-clean [S C] (GRAPH_CLEAN; min_spur S and min_component C in px, default 12 and 60, 2 rounds): state and out of the device
+    against graph_clean_ref on this scene's own graph (the run ends if they differ); device ms of the 15 launches of a call (the profiler
+    rows, three groups) and of each kernel, ms of the whole call from host arrays (table upload, launches, the 17 E-byte download; wall
+    clock around a synchronised call) and of apply (that plus the kept graph and the attributes on the host), host ms of graph_clean_ref;
+    and ms per scene of the pipelined loop as the CLI runs it — mask PNGs on writer threads — without the key and with it (on a writer
+    thread, on a stream of its own), alternated.  The graph is the scene's own if the stand-in weights yield at least 1000 edges, else a
+    synthetic road grid of 32-px cells."""
+    import sam_road_amd.inferencer as inf
+    from concurrent.futures import ThreadPoolExecutor
+    from PIL import Image
+    import io
+    from sam_road_amd import graph_clean as gc
+    dev = next(net.parameters()).device
+    H, W = img.shape[:2]
+    s_px, c_px = args.graph_clean if args.graph_clean else (12.0, 60.0)
+    key = gc.graph_clean_key_of({"min_spur": s_px, "min_component": c_px, "rounds": 2, "drop_isolated": True})
+    spur_q, comp_q = gc.thresholds_q(key)
+    nodes, edges, _, _ = inf.infer_one_img(net, img, cfg)
+    own = edges.shape[0] >= 1000
+    if not own:
+        nodes, edges = road_grid(H, W, 32, 1)
+    rep = {"graph": "the scene's own" if own else "synthetic road grid, 32-px cells", "nodes": int(nodes.shape[0]), "edges": int(edges.shape[0]),
+           "min_spur_px": s_px, "min_component_px": c_px, "rounds": key.rounds, "launches_per_call": 5 * (key.rounds + 1)}
+    host = []
+    for _ in range(3):
+        t0 = time.perf_counter()
+        want = gc.graph_clean_ref(nodes, edges, spur_q, comp_q, key.rounds)
+        host.append(round(1e3 * (time.perf_counter() - t0), 1))
+    rep["host_ms_graph_clean_ref_three_runs"] = host
+    got = gc.clean(nodes, edges, key, net=net)
+    if not (np.array_equal(got[0], want[0]) and np.array_equal(got[1], want[1])):
+        raise SystemExit(f"the device differs from graph_clean_ref on {int(((got[0] != want[0]) | (got[1] != want[1]).any(axis=1)).sum())} edges")
+    kept = want[1][want[0] == 0]
+    rep.update(equals_graph_clean_ref=True, dropped=int((want[0] != 0).sum()), dropped_as_spur=int(((want[0] & 1) == 1).sum()),
+               dropped_as_small=int(((want[0] & 2) == 2).sum()), chains_kept=int(np.unique(kept[:, 0]).size), components_kept=int(np.unique(kept[:, 1]).size),
+               edges_of_the_largest_component=int(np.bincount(kept[:, 1]).max()) if kept.size else 0)
+
+    def wall_ms(fn):
+        fn()
+        ms = []
+        for _ in range(iters):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            fn()
+            ms.append(1e3 * (time.perf_counter() - t0))
+        ms.sort()
+        return {"median": round(ms[len(ms) // 2], 4), "min_max": [round(ms[0], 4), round(ms[-1], 4)]}
+
+    result = (nodes, edges, np.zeros((1, 1), np.uint8), np.zeros((1, 1), np.uint8))
+    rep["whole_call_ms_from_host_arrays"] = wall_ms(lambda: gc.clean(nodes, edges, key, net=net))
+    rep["apply_ms_from_host_arrays"] = wall_ms(lambda: gc.apply(key, result, net=net))
+    t0 = time.perf_counter()
+    (n1, e1, _, _), attrs = gc.apply_ref(key, result)
+    table = gc.table_of(attrs)
+    t1 = time.perf_counter()
+    doc = gc.polylines_geojson(n1, e1, table)
+    rep["host_ms_polylines_geojson"] = round(1e3 * (time.perf_counter() - t1), 1)
+    rep["polylines"] = len(doc["features"])
+    ctx, _ = net._weights(dev)
+    groups, kernels = [], {}
+    for _ in range(3):                                     # three groups of `iters` calls: the run-to-run span of the kernel time
+        ctx.profile_read()
+        ctx.profile_enable(True)
+        for _ in range(iters):
+            net.graph_clean(nodes, edges, spur_q=spur_q, comp_q=comp_q, rounds=key.rounds)
+        torch.cuda.synchronize()
+        rows = {r["name"]: r["ms"] / iters for r in ctx.profile_read() if r["launches"] and r["name"].startswith("graph_clean_")}
+        ctx.profile_enable(False)
+        groups.append(round(sum(rows.values()), 4))
+        kernels = {k: round(v, 4) for k, v in rows.items()}
+    rep["kernel_ms_per_call_three_groups"] = groups
+    rep["kernel_ms_per_call_by_kernel_last_group"] = kernels
+    if args.no_pipelined:
+        return rep
+    stream = torch.cuda.Stream(dev)
+
+    def png(a):
+        Image.fromarray(a).save(io.BytesIO(), format="PNG", compress_level=1)
+
+    stage = []
+
+    def finish(res):
+        t0 = time.perf_counter()
+        with torch.cuda.stream(stream):
+            gc.apply(key, res, net=net)
+        stage.append(1e3 * (time.perf_counter() - t0))
+
+    def piped(on, n=12, writers=3):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        with ThreadPoolExecutor(writers) as pool:
+            futs = []
+            for res in inf.infer_imgs(net, (img for _ in range(n)), cfg):
+                futs += [pool.submit(png, res[2]), pool.submit(png, res[3])]
+                if on:
+                    futs.append(pool.submit(finish, res))
+            for f in futs:
+                f.result()
+        torch.cuda.synchronize()
+        return round(1e3 * (time.perf_counter() - t0) / n, 2)
+
+    for on in (False, True):
+        piped(on, 3)
+    stage.clear()
+    runs = {"without_2_writers": [], "without": [], "with": []}      # the CLI adds a writer thread with the key: both pools, so the thread is not mistaken for the key
+    for _ in range(3):
+        for name, on, writers in (("without_2_writers", False, 2), ("without", False, 3), ("with", True, 3)):
+            runs[name].append(piped(on, writers=writers))
+    rep["pipelined_ms_per_scene_runs_of_12_alternated"] = runs
+    rep["writer_thread_ms_per_scene_median_apply"] = round(sorted(stage)[len(stage) // 2], 2)
+    return rep
+
+
 def road_width_report(args, net, cfg, img, iters=20):
     """--road-width [R] (ROAD_WIDTH): the device distance map against road_dist_ref and the device statistics against road_width_ref on
     this scene size (the run ends if they differ); ms of the whole apply call from host arrays (mask and table upload, three kernels, the
@@ -1125,6 +1242,9 @@ def main():
     ap.add_argument("--road-width", type=int, nargs="?", const=32, default=None, metavar="R",
                     help="ROAD_WIDTH: time the distance map at max_radius R (default 32) and the per-edge statistics on this scene and the pipelined loop "
                          "without / with the key, alternated")
+    ap.add_argument("--graph-clean", type=float, nargs="*", default=None, metavar="PX",
+                    help="GRAPH_CLEAN: compare the device with graph_clean_ref on this scene's own graph and time the kernels, the whole call, the host "
+                         "reference and the pipelined loop without / with the key; optional: min_spur and min_component in px (default 12 60)")
     ap.add_argument("--float", type=int, default=None, metavar="C",
                     help="SCENE_FLOAT: the scene arrives as a float32 scene of C bands (bands 0..2 hold the synthetic RGB / 255, the rest noise); "
                          "the three launches, the pipelined loop with a fixed range and with a percentile stretch and the host reference are timed")
@@ -1248,6 +1368,11 @@ def main():
         if world > 1 or args.scenes is not None or args.valid_frac is not None or args.scale is not None or args.bands is not None:
             ap.error("--road-width times one unmasked u8 scene on one GPU (not with --scenes, --valid-frac, --scale or --bands)")
         print(json.dumps({"scene": f"synthetic {H}x{W}", "infer_batch_size": args.batch, "road_width": road_width_report(args, net, cfg, img)}))
+        return
+    if args.graph_clean is not None:
+        if world > 1 or args.scenes is not None or args.valid_frac is not None or args.scale is not None or args.bands is not None or len(args.graph_clean) not in (0, 2):
+            ap.error("--graph-clean [S C] times one unmasked u8 scene on one GPU (not with --scenes, --valid-frac, --scale or --bands)")
+        print(json.dumps({"scene": f"synthetic {H}x{W}", "infer_batch_size": args.batch, "graph_clean": graph_clean_report(args, net, cfg, img)}))
         return
     if args.float is not None:
         if world > 1 or args.scenes is not None or args.valid_frac is not None or args.scale is not None or args.bands is not None:
